@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — front-end frames/sec (ORB + LSD/LBD extract + match) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--batch B] [--unique U]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--batch B] [--unique U] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of B synthetic 640x480 frames that are already resident in HBM: ORB extract
 (1000 kp, 8 levels), LSD+LBD extract (<=200 lines), and matching against the previous frame's features (SearchForInitialization +
@@ -10,12 +10,18 @@ one rank per GPU) every rank processes its own B frames (weak scaling, frames ar
 are gathered to rank 0 once per step through the library's own RCCL exchange (sslam_group_gather_dev: ncclSend / ncclRecv), overlapped
 with the next step's kernels; no other collective exists on the path.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of one timed
+step) and the config block.  A plain run sets up, warms up, times the --steps steps and prints that line; nothing else runs on the GPU.
+--full adds the measurements that take time or runs of their own (per-kernel HIP-event timing during the timed steps and the legs after them):
   roofline        dominant kernel: algorithmic bytes (SURVEY.md §8(d) / DESIGN.md) over the HIP-event launch duration; whole pipeline
                   with §8(d)'s own 18 566 506 B/frame next to the per-kernel table's sum
   cpu_baseline    the CPU oracle (restatement of the reference path, "port"), one core, bounded sample, -O3 -march=native built on this box
   latency         single-frame H2D -> kernels -> D2H through the host entry points (what the drop-in shim calls per frame), p50/p90
   pcie_inclusive  sslam_frontend_batch: host images in, host records out (pinned and pageable)
+  other_workloads BASELINE configs[3] and the headline step under decision D11's variant 0, each in a child process
+  config.gather   (--gpus N) what RCCL delivered to rank 0 in the last step against rank 0's own records, and every rank's wall time
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs); the inputs are seeded, so two builds can
+be compared output for output.
 """
 import argparse, json, os, sys, time
 
@@ -151,25 +157,74 @@ def other_walls(kernel, avg_launch_ms, B, ms_per_step, workload, hbm_frac):
 
 def synth_frames(w, h, U, rank):
     """U distinct seeded scenes per rank (+ their warped previous frames): object count and noise vary from frame to frame, so the LSD core's
-    content-dependent work varies too.  Cached in /tmp (generation costs ~0.2 s per 640x480 frame)."""
-    import numpy as np
+    content-dependent work varies too.  Generation costs ~0.3 s per 640x480 frame, almost all of it in numpy calls that release the GIL, so the
+    frames are made on up to 16 threads; every frame depends on its own seed only, so the bytes do not depend on the thread count."""
+    from concurrent.futures import ThreadPoolExecutor
     from synth import synth_frame, warp_prev
-    cache = "/tmp/sslam_bench_frames_%dx%d_%d_r%d.npz" % (w, h, U, rank)
-    if os.path.exists(cache):
-        z = np.load(cache)
-        return list(z["cur"]), list(z["prev"])
     area = (w * h) / (640 * 480)
-    cur = []
-    for i in range(U):
+
+    def one(i):
         k = i % 8      # eight kinds of scene: the default density (the round-1 frames), sparser / denser, more noise
         ns, nst, noise = [(60, 40, 2.0), (35, 25, 2.0), (90, 60, 2.0), (60, 40, 3.5), (45, 70, 1.0), (75, 30, 2.5), (60, 40, 2.0), (50, 50, 2.0)][k]
-        cur.append(synth_frame(2000 + rank * 1000 + i, w, h, nshapes=int(ns * area), nstrokes=int(nst * area), noise=noise))
-    prev = [warp_prev(f) for f in cur]
-    try:
-        np.savez(cache, cur=np.stack(cur), prev=np.stack(prev))
-    except Exception:
-        pass
-    return cur, prev
+        f = synth_frame(2000 + rank * 1000 + i, w, h, nshapes=int(ns * area), nstrokes=int(nst * area), noise=noise)
+        return f, warp_prev(f)
+    with ThreadPoolExecutor(max(1, min(U, 16, len(os.sched_getaffinity(0))))) as ex:
+        pairs = list(ex.map(one, range(U)))
+    return [c for c, _ in pairs], [p for _, p in pairs]
+
+
+DUMP_BUDGET = 60 << 20      # bytes of .npy data --dump-outputs may write (<= 64 MB at any workload and batch)
+DUMP_MAX_FRAMES = 128
+
+
+def dump_outputs(fe, pipe, d, B):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step, as DIR/<name>.npy (float32; float64 for the line
+    equations and the fields of the struct records).  Per-frame counts for all B frames; the per-frame arrays (keypoints, descriptors, keylines, LBD descriptors,
+    line equations, matches) for a fixed, seeded sample of frames (frame_index.npy), as many as fit in DUMP_BUDGET.  Rows past a frame's count
+    are set to 0: the caller is handed the first n rows only.  Struct records (cv::KeyPoint, KeyLine) become one column per field."""
+    import numpy as np, torch
+    os.makedirs(d, exist_ok=True)
+    c, p = pipe.feat["cur"], pipe.feat["prev"]
+    cap, lcap = pipe.cap, pipe.lcap
+    per_frame = cap * (7 * 8 + 32 * 4) + (cap * 7 * 4 if pipe.with_match else 0)
+    if pipe.with_lines:
+        per_frame += lcap * (17 * 8 + 32 * 4 + 3 * 8) + (lcap * 2 * 4 if pipe.with_match else 0)
+    S = max(1, min(B, DUMP_MAX_FRAMES, (DUMP_BUDGET - 4 * 4 * B - 8 * DUMP_MAX_FRAMES) // per_frame))
+    idx = np.sort(np.random.default_rng(0).choice(B, size=S, replace=False))
+    sel = torch.from_numpy(idx).to(c["n"].device)
+    get = lambda t: t.index_select(0, sel).cpu().numpy()
+
+    def rows(a, cnt):      # zero the rows at and past each frame's count
+        a = np.array(a)
+        a[np.arange(a.shape[1])[None, :] >= cnt[:, None]] = 0
+        return a
+
+    def fields(a, dt):     # [S, rows, k] words -> [S, rows, fields] float64
+        s = np.ascontiguousarray(a).view(dt)[..., 0]
+        return np.stack([s[f].astype(np.float64) for f in dt.names], -1)
+    out = {"frame_index": idx.astype(np.float64)}
+    n, n_prev = get(c["n"]), get(p["n"])
+    out["keypoint_counts"] = c["n"].cpu().numpy()
+    out["keypoints"] = rows(fields(get(c["kp"]), fe.KP_DTYPE), n)
+    out["descriptors"] = rows(get(c["desc"]), n)
+    if pipe.with_match:
+        out["orb_match_counts"] = pipe.nmatch.cpu().numpy()
+        out["orb_matches12"] = rows(get(pipe.m12), n_prev)
+        out["orb_prev_matched"] = rows(get(pipe.pm), n_prev)
+        out["knn2_index"] = rows(get(pipe.knn_idx), n_prev)
+        out["knn2_distance"] = rows(get(pipe.knn_dist), n_prev)
+    if pipe.with_lines:
+        nl = get(c["nl"])
+        out["line_counts"] = c["nl"].cpu().numpy()
+        out["keylines"] = rows(fields(get(c["kl"]), fe.KL_DTYPE), nl)
+        out["line_descriptors"] = rows(get(c["ldesc"]), nl)
+        out["line_functions"] = rows(get(c["linefn"]), nl)
+        if pipe.with_match:
+            out["line_pair_counts"] = pipe.nlpairs.cpu().numpy()
+            out["line_pairs"] = rows(get(pipe.lpairs), get(pipe.nlpairs))
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+    return {"dir": d, "frames_sampled": int(S), "arrays": sorted(out), "bytes": int(sum(a.size * (8 if a.dtype == np.float64 else 4) for a in out.values()))}
 
 
 def cpu_baseline(frames_cur, frames_prev, budget_s=12.0, max_frames=600, with_lines=True, with_match=True, nref=8):
@@ -392,8 +447,11 @@ def self_launch(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="also the per-kernel timing / roofline, CPU baseline, latency and PCIe-inclusive legs, other workloads and "
+                                                          "the multi-rank gather check (the --no-* options below switch parts of it off); default: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
     ap.add_argument("--batch", type=int, default=0, help="frames per step per GPU (default: the workload's)")
     ap.add_argument("--unique", type=int, default=0, help="distinct synthetic frames per rank, tiled to the batch (default: the workload's, 64 for c3)")
@@ -405,8 +463,10 @@ def main():
     ap.add_argument("--nfa-stream-leg", action="store_true", help="(child process of the default run) single-frame line extraction with SSLAM_NFA_STREAM=0 (the NFA stage behind the core) beside the default path")
     ap.add_argument("--lsd-nfa-variant", type=int, default=-1, help="decision D11 (sslam_lines_set_nfa_variant): 0 = log_gamma(n + 1), the default of rounds 1-4; 1 = (double(n) + 1), the default since round 5; -1: the library's default")
     ap.add_argument("--self-launch", action="store_true", help="start the ranks from this process even for --gpus 1 (what --gpus N > 1 does by itself when no launcher set RANK): the N = 1 test of the multi-rank path, RCCL exchange included")
-    ap.add_argument("--no-other-workloads", action="store_true", help="the default run appends a short pass of BASELINE configs[3] (1280x960 / 2000 kp / 400 lines) as other_workloads.c4; this skips it")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full appends a short pass of BASELINE configs[3] (1280x960 / 2000 kp / 400 lines) as other_workloads.c4; this skips it")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.nfa_stream_leg:
         nfa_stream_leg()
         return
@@ -513,7 +573,8 @@ def main():
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    if not args.no_profile:
+    profile = args.full and not args.no_profile
+    if profile:
         fe.lib().sslam_profile_enable(ctx.h, 1)
     if gather is not None:
         gather.wait_s = 0.0; gather.waits = 0
@@ -527,10 +588,12 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    fe.lib().sslam_profile_enable(ctx.h, 0)
-    prof = pipeline.profile_drain(fe, ctx) if not args.no_profile else {}
+    prof = {}
+    if profile:
+        fe.lib().sslam_profile_enable(ctx.h, 0)
+        prof = pipeline.profile_drain(fe, ctx)
     per_rank = None
-    if dist is not None:
+    if dist is not None and args.full:
         # every rank's own wall time and how long it stood still for the exchange: rank 0 prints them (a slow rank or an exchange that is
         # not hidden behind the next step shows here, not in the max-over-ranks figure)
         mine = torch.tensor([dt, gather.wait_s if gather is not None else 0.0], dtype=torch.float64, device=dev)
@@ -538,14 +601,16 @@ def main():
         dist.all_gather(allr, mine)
         per_rank = [{"rank": r, "wall_s": float(a[0].item()), "frames_per_s": B * args.steps / float(a[0].item()), "gather_wait_ms_per_step": float(a[1].item()) * 1e3 / max(args.steps, 1)}
                     for r, a in enumerate(allr)]
+    if dist is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    dumped = dump_outputs(fe, pipe, args.dump_outputs, B) if args.dump_outputs and rank == 0 else None
 
     # the dominant kernel alone: two more steps on ONE stream (kernels back to back), so that the roofline block also carries a duration that
     # is not stretched by the other branch's kernels sharing the chip (outside the timed region; rank 0's own GPU)
     prof_iso = {}
-    if not args.no_profile and not args.no_overlap and gather is None:
+    if profile and not args.no_overlap and gather is None:
         fe.lib().sslam_profile_enable(ctx.h, 1)
         for _ in range(2):
             pipe.step(cur, overlap=False)
@@ -554,7 +619,7 @@ def main():
         prof_iso = pipeline.profile_drain(fe, ctx)
 
     gather_info = None
-    if rank == 0 and gather is not None:
+    if rank == 0 and gather is not None and args.full:
         # what RCCL delivered for the last step: rank 0's own records must be in it byte for byte (global frame i = local i // world on rank i % world);
         # reported in the JSON line (config.gather_check), never fatal for the measurement
         try:
@@ -632,10 +697,10 @@ def main():
                                                   "note": "frac uses SURVEY.md §8(d)'s own byte total; the per-kernel table (DESIGN.md §4) is what this implementation moves"},
                                "kernels_ms_per_step": {k: v[0] / args.steps for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])},
                                "kernels_note": "HIP-event durations per kernel; with the two branches on two streams kernels of different branches overlap, so the durations include the sharing and their sum exceeds ms_per_step (run with --no-overlap for isolated durations)" if not args.no_overlap else "kernels run back to back on one stream"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], ref = cpu_baseline(cur_np, prev_np, with_lines=with_lines, with_match=wl["match"])
             out["cpu_baseline"]["parity_vs_gpu"] = parity_vs_gpu(ref, pipe.feat["cur"], with_lines)
-        if world == 1 and not args.no_extras and args.workload in ("c3", "c2", "c4"):
+        if args.full and world == 1 and not args.no_extras and args.workload in ("c3", "c2", "c4"):
             # the extra legs build their own extractors: the resident batch (175 GB at the default size) is released first
             pipe.close(); pipe = None
             del cur, prev
@@ -646,14 +711,14 @@ def main():
                     out["pcie_inclusive"] = pcie_leg(fe, ctx, cur_np, with_lines, n=18432 if W == 640 else 3072, chunk=0 if W == 640 else 1024, prev_frames=prev_np)
             except Exception as e:
                 out["latency_error"] = str(e)[:300]
-        if world == 1 and args.workload == "c3" and not args.no_extras and not args.no_other_workloads:
+        if args.full and world == 1 and args.workload == "c3" and not args.no_extras and not args.no_other_workloads:
             # BASELINE configs[3] (1280x960, 2000 kp, 400 lines: the "rocprof HBM-GB/s run") in the driver's own bench run: a short pass of the
             # same harness in a child process (this process holds no batch any more), its headline numbers appended to this line
             import subprocess
             try:
                 child_env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                                                "SSLAM_FORCE_COLLECTIVE", "TORCHELASTIC_RUN_ID")}      # a plain single-process run, whatever launched this one
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "c4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pcie"],
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--workload", "c4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pcie"],
                                    capture_output=True, text=True, timeout=900, env=child_env)
                 line = [l for l in r.stdout.splitlines() if l.startswith("{")]
                 c4 = json.loads(line[-1])
@@ -666,7 +731,7 @@ def main():
                 out["other_workloads"] = {"c4": {"error": str(e)[:300]}}
             try:      # trend continuity: the same step under decision D11's variant 0 (nfa()'s first term = log_gamma(n + 1): the default of rounds 1-4, whose bench lines r01-r04 are)
                 if args.lsd_nfa_variant < 0:
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extras", "--no-other-workloads", "--lsd-nfa-variant", "0"],
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extras", "--no-other-workloads", "--lsd-nfa-variant", "0"],
                                        capture_output=True, text=True, timeout=600, env=child_env)
                     v0 = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
                     out["other_workloads"]["c3_lsd_nfa_variant_0"] = {
@@ -682,6 +747,8 @@ def main():
                 out["latency_nfa_behind_core"] = json.loads(r.stdout.strip().splitlines()[-1])
             except Exception as e:
                 out["latency_nfa_behind_core"] = {"error": str(e)[:300]}
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         print(json.dumps(out))
     if gather is not None:
         gather.wait()

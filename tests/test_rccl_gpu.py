@@ -1,6 +1,6 @@
 """GPU: the exchange step of the sharded mode over RCCL.  The GPU box has one device, so the launch is the
 driver's own (`python -m torch.distributed.run --nproc-per-node 1 ... bench.py`) with SSLAM_FORCE_COLLECTIVE=1: the process
-group is nccl (= RCCL), every step's packed records go through dist.gather on the device, and bench.py reports (config.gather_check) whether what
+group is nccl (= RCCL), every step's packed records go through dist.gather on the device, and bench.py --full reports (config.gather_check) whether what
 rank 0 receives equals its own packed results.  World sizes > 1 are covered on gloo in test_dist_cpu.py."""
 import json, os, subprocess, sys
 import pytest
@@ -15,7 +15,7 @@ def test_bench_under_torchrun_with_rccl_gather():
     port = 29600 + (os.getpid() % 300)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64",
-           "--no-cpu-baseline", "--no-other-workloads"]
+           "--full", "--no-cpu-baseline", "--no-other-workloads"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -31,7 +31,7 @@ def test_bench_launches_its_own_ranks():
     with N = 1 forced through it (--self-launch): torch.distributed.run on 127.0.0.1, one rank, the RCCL exchange inside every step, ONE JSON line from rank 0 that
     carries n_gpus, the per-rank wall times, gather_check and the communicator's rank count, exit code 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "SSLAM_FORCE_COLLECTIVE")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--self-launch", "--steps", "2", "--warmup", "1", "--batch", "64", "--no-cpu-baseline", "--no-other-workloads"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--self-launch", "--steps", "2", "--warmup", "1", "--batch", "64", "--full", "--no-cpu-baseline", "--no-other-workloads"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -42,7 +42,7 @@ def test_bench_launches_its_own_ranks():
     assert out["config"]["gather_check"] is True and g["self_launched"] is True and g["rccl_ranks"] == 1
     assert len(g["per_rank"]) == 1 and g["per_rank"][0]["wall_s"] > 0
     # BASELINE configs[4] (8 frames dealt over the GPUs, H2D + extract + match + RCCL gather inside the step) through the same launch path
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--self-launch", "--workload", "c5", "--steps", "3", "--warmup", "1"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--self-launch", "--workload", "c5", "--steps", "3", "--warmup", "1", "--full"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     c5 = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert c5["n_gpus"] == 1 and c5["scaling"] == "strong" and c5["config"]["global_batch"] == 8 and c5["config"]["gather_check"] is True

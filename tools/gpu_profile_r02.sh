@@ -3,10 +3,10 @@
 # "rocprof HBM-GB/s run" of BASELINE configs[3]), per-kernel instruction table.  Counters in their own passes, no trace domains mixed in.
 set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02; mkdir -p $O
-cd $R && timeout 900 python bench.py > $O/bench_r02.json 2> $O/bench_r02.err; tail -c 300 $O/bench_r02.err
-cd $R && timeout 600 python bench.py --no-overlap --no-cpu-baseline --no-extras > $O/bench_r02_one_stream.json 2>/dev/null
-cd $R && timeout 600 python bench.py --workload c4 --no-cpu-baseline > $O/bench_r02_c4.json 2>/dev/null
-cd $R && timeout 600 python bench.py --unique 8 --no-overlap --no-cpu-baseline --no-extras > $O/bench_r02_8frames_one_stream.json 2>/dev/null
+cd $R && timeout 900 python bench.py --full > $O/bench_r02.json 2> $O/bench_r02.err; tail -c 300 $O/bench_r02.err
+cd $R && timeout 600 python bench.py --full --no-overlap --no-cpu-baseline --no-extras > $O/bench_r02_one_stream.json 2>/dev/null
+cd $R && timeout 600 python bench.py --full --workload c4 --no-cpu-baseline > $O/bench_r02_c4.json 2>/dev/null
+cd $R && timeout 600 python bench.py --full --unique 8 --no-overlap --no-cpu-baseline --no-extras > $O/bench_r02_8frames_one_stream.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/kt && timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt -- python $R/bench.py --no-cpu-baseline --no-extras --no-profile > $O/kt.log 2>&1
 rm -rf $O/kt1 && timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt1 -- python $R/bench.py --no-overlap --no-cpu-baseline --no-extras --no-profile > $O/kt1.log 2>&1

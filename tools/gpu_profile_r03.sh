@@ -20,9 +20,9 @@ for wl in c3 c4; do
 done
 cp $O/pmc_traffic_c3.json $R/profiles/pmc_traffic.json; cp $O/pmc_traffic_c4.json $R/profiles/pmc_traffic_c4.json
 rm -rf $O/pmc_c3_FETCH_SIZE $O/pmc_c3_WRITE_SIZE $O/pmc_c4_FETCH_SIZE $O/pmc_c4_WRITE_SIZE
-timeout 900 python bench.py > $O/bench_r03.json 2> $O/bench_r03.err; tail -c 600 $O/bench_r03.err
-timeout 600 python bench.py --no-overlap --no-cpu-baseline --no-extras > $O/bench_r03_one_stream.json 2>/dev/null
-timeout 600 python bench.py --workload c4 --no-cpu-baseline > $O/bench_r03_c4.json 2>/dev/null
+timeout 900 python bench.py --full > $O/bench_r03.json 2> $O/bench_r03.err; tail -c 600 $O/bench_r03.err
+timeout 600 python bench.py --full --no-overlap --no-cpu-baseline --no-extras > $O/bench_r03_one_stream.json 2>/dev/null
+timeout 600 python bench.py --full --workload c4 --no-cpu-baseline > $O/bench_r03_c4.json 2>/dev/null
 cd /tmp
 rm -rf $O/kt && timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt -- python $R/bench.py --no-cpu-baseline --no-extras --no-profile > $O/kt.log 2>&1
 rm -rf $O/kt1 && timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt1 -- python $R/bench.py --no-overlap --no-cpu-baseline --no-extras --no-profile > $O/kt1.log 2>&1

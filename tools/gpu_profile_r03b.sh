@@ -6,7 +6,7 @@ set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03; mkdir -p $O
 cd $R
 timeout 1800 python -m pytest tests -q -m gpu > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
-timeout 900 python bench.py > $O/bench_r03.json 2> $O/bench_r03.err; tail -c 300 $O/bench_r03.err
+timeout 900 python bench.py --full > $O/bench_r03.json 2> $O/bench_r03.err; tail -c 300 $O/bench_r03.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/lat && cd $R && timeout 300 rocprofv3 --kernel-trace --stats -d $O/lat -- python tools/latency_probe.py > $O/lat.log 2>&1
 python tools/rocpd_summary.py $O/lat $O/kernel_trace_single_frame.txt > /dev/null; rm -rf $O/lat
@@ -18,7 +18,7 @@ head -8 $O/kernel_trace_single_frame.txt
 python -c "
 import json
 d=json.load(open('$O/bench_r03.json')); print(round(d['value']), d['ms_per_step'], d['roofline']['frac'], d['roofline']['traffic']); print(d['latency']['lines_extract_hipEvent'], d['latency']['lsd_core']); print({k: v for k, v in d['pcie_inclusive'].items() if 'per_s' in k or 'matches' in k})"
-cd $R && timeout 600 python bench.py --workload c4 --no-cpu-baseline > $O/bench_r03_c4.json 2>/dev/null
+cd $R && timeout 600 python bench.py --full --workload c4 --no-cpu-baseline > $O/bench_r03_c4.json 2>/dev/null
 python -c "
 import json
 d=json.load(open('$O/bench_r03_c4.json')); print('c4', round(d['value']), d['ms_per_step'], d['latency']['lines_extract_hipEvent'], d['latency']['lsd_core'][:40])"

@@ -16,8 +16,8 @@ python tools/make_pmc_traffic.py $O/pmc_c3_FETCH_SIZE $O/pmc_c3_WRITE_SIZE $b 3 
 cp $O/pmc_traffic_c3.json $R/profiles/pmc_traffic.json
 rm -rf $O/pmc_c3_FETCH_SIZE $O/pmc_c3_WRITE_SIZE
 timeout 1500 python -m pytest tests -q -m gpu --durations=8 > $O/pytest_gpu.txt 2>&1; tail -14 $O/pytest_gpu.txt
-timeout 1200 python bench.py > $O/bench_r04.json 2> $O/bench_r04.err; tail -c 300 $O/bench_r04.err
-timeout 400 python bench.py --no-overlap --no-cpu-baseline --no-extras --no-other-workloads > $O/bench_r04_one_stream.json 2>/dev/null
+timeout 1200 python bench.py --full > $O/bench_r04.json 2> $O/bench_r04.err; tail -c 300 $O/bench_r04.err
+timeout 400 python bench.py --full --no-overlap --no-cpu-baseline --no-extras --no-other-workloads > $O/bench_r04_one_stream.json 2>/dev/null
 cd /tmp
 rm -rf $O/kt && timeout 400 rocprofv3 --kernel-trace --stats -d $O/kt -- python $R/bench.py --no-cpu-baseline --no-extras --no-profile --no-other-workloads > $O/kt.log 2>&1
 rm -rf $O/kt1 && timeout 400 rocprofv3 --kernel-trace --stats -d $O/kt1 -- python $R/bench.py --no-overlap --no-cpu-baseline --no-extras --no-profile --no-other-workloads > $O/kt1.log 2>&1

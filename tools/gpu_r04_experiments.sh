@@ -9,11 +9,11 @@ a)
 # round 4, first GPU call: fused NFA launch + k_keylines LDS fix -- parity (fused form forced on the small test batches), then A/B bench lines
 O=$R/gpurun_out/r04a; mkdir -p $O
 SSLAM_NFA_FUSED=2 timeout 900 python -m pytest tests/test_lines_gpu.py tests/test_configs_gpu.py tests/test_batch_gpu.py tests/test_pin_gpu.py -x -q -m gpu > $O/pytest_fused.txt 2>&1; tail -5 $O/pytest_fused.txt
-timeout 600 python bench.py --no-cpu-baseline --no-extras > $O/bench_fused.json 2> $O/bench_fused.err; tail -c 300 $O/bench_fused.err
-SSLAM_NFA_FUSED=0 timeout 600 python bench.py --no-cpu-baseline --no-extras > $O/bench_unfused.json 2>/dev/null
-SSLAM_LIB=$R/structure-slam-pointline_amd/lib/variants/nfa4.so timeout 600 python bench.py --no-cpu-baseline --no-extras > $O/bench_fused_mw4.json 2>/dev/null
-timeout 600 python bench.py --no-overlap --no-cpu-baseline --no-extras > $O/bench_fused_one_stream.json 2>/dev/null
-SSLAM_LIB=$R/structure-slam-pointline_amd/lib/variants/nfa4.so timeout 600 python bench.py --no-overlap --no-cpu-baseline --no-extras > $O/bench_fused_mw4_one_stream.json 2>/dev/null
+timeout 600 python bench.py --full --no-cpu-baseline --no-extras > $O/bench_fused.json 2> $O/bench_fused.err; tail -c 300 $O/bench_fused.err
+SSLAM_NFA_FUSED=0 timeout 600 python bench.py --full --no-cpu-baseline --no-extras > $O/bench_unfused.json 2>/dev/null
+SSLAM_LIB=$R/structure-slam-pointline_amd/lib/variants/nfa4.so timeout 600 python bench.py --full --no-cpu-baseline --no-extras > $O/bench_fused_mw4.json 2>/dev/null
+timeout 600 python bench.py --full --no-overlap --no-cpu-baseline --no-extras > $O/bench_fused_one_stream.json 2>/dev/null
+SSLAM_LIB=$R/structure-slam-pointline_amd/lib/variants/nfa4.so timeout 600 python bench.py --full --no-overlap --no-cpu-baseline --no-extras > $O/bench_fused_mw4_one_stream.json 2>/dev/null
 python - <<'PY'
 import json
 for n in ('bench_fused','bench_unfused','bench_fused_mw4','bench_fused_one_stream','bench_fused_mw4_one_stream'):
@@ -28,7 +28,7 @@ b)
 O=$R/gpurun_out/r04b; mkdir -p $O
 timeout 900 python -m pytest tests/test_group_gpu.py tests/test_pin_gpu.py -x -q -m gpu > $O/pytest_group.txt 2>&1; tail -15 $O/pytest_group.txt
 timeout 900 python -m pytest tests/test_stress_gpu.py -x -q -m gpu -s > $O/pytest_stress.txt 2>&1; tail -8 $O/pytest_stress.txt
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.err
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.err
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r04b/bench.json'))
@@ -46,9 +46,9 @@ for v in "def:" "old:SSLAM_NFA_FUSED=0" "old256:SSLAM_NFA_FUSED=0 SSLAM_COUNT_WA
   n=${v%%:*}; e=${v#*:}
   env $e timeout 200 python tools/latency_probe.py > $O/lat_$n.txt 2>&1; tail -1 $O/lat_$n.txt
 done
-timeout 300 python bench.py --no-cpu-baseline --no-extras --no-overlap > $O/bench_one_stream.json 2>/dev/null
-SSLAM_SFI_BATCH=global timeout 300 python bench.py --no-cpu-baseline --no-extras --no-overlap > $O/bench_one_stream_sfi_global.json 2>/dev/null
-timeout 300 python bench.py --no-cpu-baseline --no-extras > $O/bench_two_streams.json 2>/dev/null
+timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-overlap > $O/bench_one_stream.json 2>/dev/null
+SSLAM_SFI_BATCH=global timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-overlap > $O/bench_one_stream_sfi_global.json 2>/dev/null
+timeout 300 python bench.py --full --no-cpu-baseline --no-extras > $O/bench_two_streams.json 2>/dev/null
 python - <<'PY'
 import json
 for n in ('bench_one_stream','bench_one_stream_sfi_global','bench_two_streams'):
@@ -65,11 +65,11 @@ timeout 420 python -m pytest tests/test_group_gpu.py -x -q -m gpu > $O/pytest_gr
 V=$R/structure-slam-pointline_amd/lib/variants
 for v in "w6:" "w7:SSLAM_LIB=$V/core7.so" "w8:SSLAM_LIB=$V/core8.so"; do
   n=${v%%:*}; e=${v#*:}
-  env $e timeout 300 python bench.py --no-cpu-baseline --no-extras > $O/bench_$n.json 2>/dev/null
-  env $e timeout 300 python bench.py --no-cpu-baseline --no-extras --no-overlap > $O/bench_${n}_one.json 2>/dev/null
+  env $e timeout 300 python bench.py --full --no-cpu-baseline --no-extras > $O/bench_$n.json 2>/dev/null
+  env $e timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-overlap > $O/bench_${n}_one.json 2>/dev/null
 done
-SSLAM_LIB=$V/core7.so timeout 300 python bench.py --no-cpu-baseline --no-extras --batch 14336 > $O/bench_w7_B14336.json 2>/dev/null
-SSLAM_LIB=$V/core8.so timeout 300 python bench.py --no-cpu-baseline --no-extras --batch 16384 > $O/bench_w8_B16384.json 2>/dev/null
+SSLAM_LIB=$V/core7.so timeout 300 python bench.py --full --no-cpu-baseline --no-extras --batch 14336 > $O/bench_w7_B14336.json 2>/dev/null
+SSLAM_LIB=$V/core8.so timeout 300 python bench.py --full --no-cpu-baseline --no-extras --batch 16384 > $O/bench_w8_B16384.json 2>/dev/null
 SSLAM_LIB=$V/core7.so timeout 300 python -m pytest tests/test_lines_gpu.py tests/test_batch_gpu.py -x -q -m gpu > $O/pytest_w7.txt 2>&1; tail -2 $O/pytest_w7.txt
 python - <<'PY'
 import json, glob
@@ -100,15 +100,15 @@ g)
 O=$R/gpurun_out/r04g; mkdir -p $O
 timeout 900 python -m pytest tests/test_orb_gpu.py tests/test_lines_gpu.py tests/test_configs_gpu.py tests/test_batch_gpu.py tests/test_shim_gpu.py tests/test_pin_gpu.py tests/test_group_gpu.py -x -q -m gpu > $O/pytest.txt 2>&1; tail -5 $O/pytest.txt
 SSLAM_ORB_BLUR_VARIANT=1 timeout 300 python -m pytest tests/test_shim_gpu.py -x -q -m gpu -k end_to_end > $O/pytest_shim_v1.txt 2>&1; tail -3 $O/pytest_shim_v1.txt
-timeout 300 python bench.py --no-cpu-baseline --no-extras > $O/bench.json 2>/dev/null; python -c "
+timeout 300 python bench.py --full --no-cpu-baseline --no-extras > $O/bench.json 2>/dev/null; python -c "
 import json; d=json.load(open('$O/bench.json')); print(round(d['value']), d['ms_per_step'])"
 ;;
 h)
 # round 4, call h: the counting sort on per-segment lists of defined pixels (k_lsd_grad / k_lsd_hist / k_lsd_scatter): parity, then the two bench lines
 O=$R/gpurun_out/r04h; mkdir -p $O
 timeout 700 python -m pytest tests/test_lines_gpu.py tests/test_configs_gpu.py tests/test_batch_gpu.py tests/test_edge_gpu.py tests/test_pin_gpu.py -x -q -m gpu > $O/pytest_lines.txt 2>&1; tail -6 $O/pytest_lines.txt
-timeout 400 python bench.py --no-cpu-baseline --no-extras --no-other-workloads > $O/bench_two_streams.json 2> $O/bench.err; tail -c 300 $O/bench.err
-timeout 400 python bench.py --no-cpu-baseline --no-extras --no-other-workloads --no-overlap > $O/bench_one_stream.json 2>/dev/null
+timeout 400 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads > $O/bench_two_streams.json 2> $O/bench.err; tail -c 300 $O/bench.err
+timeout 400 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads --no-overlap > $O/bench_one_stream.json 2>/dev/null
 python - <<'PY'
 import json
 for n in ('bench_two_streams','bench_one_stream'):
@@ -124,7 +124,7 @@ O=$R/gpurun_out/r04i; mkdir -p $O
 for n in base gw g8w g6w gr4 gr16 gw8; do
   L=$R/structure-slam-pointline_amd/lib/variants/$n.so; [ $n = base ] && L=$R/structure-slam-pointline_amd/lib/libsslam_frontend.so
   [ -f $L ] || continue
-  SSLAM_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-extras --no-other-workloads --no-overlap --steps 3 --warmup 1 > $O/bench_$n.json 2>/dev/null
+  SSLAM_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads --no-overlap --steps 3 --warmup 1 > $O/bench_$n.json 2>/dev/null
   python - <<PY
 import json
 try:
@@ -152,7 +152,7 @@ k)
 # round 4, call k: the core capped at 5 / 4 waves per SIMD (LDS padding) so that point-branch waves find slots during its first round -- two-stream bench lines
 O=$R/gpurun_out/r04k; mkdir -p $O
 for pad in 0 8192 10240; do
-  SSLAM_LSD_LDS_PAD=$pad timeout 300 python bench.py --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 > $O/bench_pad$pad.json 2>/dev/null
+  SSLAM_LSD_LDS_PAD=$pad timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 > $O/bench_pad$pad.json 2>/dev/null
   python - <<PY
 import json
 try:
@@ -166,7 +166,7 @@ l)
 # round 4, call l: persistent workgroups for the sequential core (SSLAM_LSD_PERSIST=G): G < wave slots leaves room for the point branch during the whole launch
 O=$R/gpurun_out/r04l; mkdir -p $O
 for g in ${GRIDS:-0 5120 4096 3072 2048}; do
-  SSLAM_LSD_PERSIST=$g timeout 300 python bench.py --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 > $O/bench_g$g.json 2>/dev/null
+  SSLAM_LSD_PERSIST=$g timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 > $O/bench_g$g.json 2>/dev/null
   python - <<PY
 import json
 try:
@@ -183,7 +183,7 @@ timeout 600 python -m pytest tests/test_match_gpu.py tests/test_batch_gpu.py -x 
 SSLAM_KNN2_BATCH=mfma2 timeout 600 python -m pytest tests/test_match_gpu.py tests/test_batch_gpu.py -x -q -m gpu -k "knn2 or batch" > $O/pytest_mfma2.txt 2>&1; tail -6 $O/pytest_mfma2.txt
 for v in mfma mfma2 popc; do
   for ov in "" "--no-overlap"; do
-    SSLAM_KNN2_BATCH=$v timeout 300 python bench.py --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 $ov > $O/bench_$v$ov.json 2>/dev/null
+    SSLAM_KNN2_BATCH=$v timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 $ov > $O/bench_$v$ov.json 2>/dev/null
     python - <<PY
 import json
 try:
@@ -201,7 +201,7 @@ timeout 600 python -m pytest tests/test_orb_gpu.py tests/test_batch_gpu.py tests
 for v in mfma dnomfma; do
  L=$R/structure-slam-pointline_amd/lib/libsslam_frontend.so; [ $v = dnomfma ] && L=$R/structure-slam-pointline_amd/lib/variants/dnomfma.so
  for ov in "" "--no-overlap"; do
-  SSLAM_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 $ov > $O/bench_$v$ov.json 2>/dev/null
+  SSLAM_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 $ov > $O/bench_$v$ov.json 2>/dev/null
   python - <<PY
 import json
 try:
@@ -216,7 +216,7 @@ o)
 # round 4, call o: where k_blur_sobel runs (prologue / behind the NFA stage) x where the point branch waits for the core event (before the pyramid / behind it)
 O=$R/gpurun_out/r04o; mkdir -p $O
 for sob in early late; do for pc in 1 pyr; do
-  SSLAM_LBD_SOBEL=$sob SSLAM_POINTS_AT_CORE=$pc timeout 300 python bench.py --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 > $O/bench_${sob}_$pc.json 2>/dev/null
+  SSLAM_LBD_SOBEL=$sob SSLAM_POINTS_AT_CORE=$pc timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 > $O/bench_${sob}_$pc.json 2>/dev/null
   python - <<PY
 import json
 try:
@@ -231,7 +231,7 @@ p)
 O=$R/gpurun_out/r04p; mkdir -p $O
 timeout 700 python -m pytest tests/test_orb_gpu.py tests/test_lines_gpu.py tests/test_batch_gpu.py tests/test_configs_gpu.py tests/test_edge_gpu.py -x -q -m gpu > $O/pytest.txt 2>&1; tail -6 $O/pytest.txt
 for ov in "" "--no-overlap"; do
-  timeout 300 python bench.py --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 $ov > $O/bench$ov.json 2>/dev/null
+  timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 $ov > $O/bench$ov.json 2>/dev/null
   python - <<PY
 import json
 try:
@@ -245,7 +245,7 @@ q)
 # round 4, call q: frames per step (rounds of the sequential core per launch): 12288 (two rounds of 6144 wave slots), 18432, 24576
 O=$R/gpurun_out/r04q; mkdir -p $O
 for b in ${BATCHES:-12288 18432 24576}; do
-  timeout 400 python bench.py --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 --batch $b > $O/bench_b$b.json 2> $O/bench_b$b.err
+  timeout 400 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads --steps 3 --warmup 1 --batch $b > $O/bench_b$b.json 2> $O/bench_b$b.err
   python - <<PY
 import json
 try:
@@ -263,7 +263,7 @@ timeout 600 python -m pytest tests/test_lines_gpu.py tests/test_orb_gpu.py tests
 for n in base ra1 ra2; do
   L=$R/structure-slam-pointline_amd/lib/variants/$n.so; [ $n = base ] && L=$R/structure-slam-pointline_amd/lib/libsslam_frontend.so
   [ -f $L ] || continue
-  SSLAM_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-extras --no-other-workloads --no-overlap --steps 3 --warmup 1 > $O/bench_$n.json 2>/dev/null
+  SSLAM_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads --no-overlap --steps 3 --warmup 1 > $O/bench_$n.json 2>/dev/null
   python - <<PY
 import json
 try:
@@ -282,7 +282,7 @@ SSLAM_LIB=$V timeout 600 python -m pytest tests/test_lines_gpu.py tests/test_con
 for n in base nolicm; do
   L=$V; [ $n = base ] && L=$R/structure-slam-pointline_amd/lib/libsslam_frontend.so
   for ov in "--no-overlap" ""; do
-  SSLAM_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-extras --no-other-workloads $ov --steps 3 --warmup 1 > $O/bench_$n$ov.json 2>/dev/null
+  SSLAM_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads $ov --steps 3 --warmup 1 > $O/bench_$n$ov.json 2>/dev/null
   python - <<PY
 import json
 try:
@@ -301,7 +301,7 @@ timeout 600 python -m pytest tests/test_lines_gpu.py tests/test_configs_gpu.py t
 for n in base unpacked; do
   L=$R/structure-slam-pointline_amd/lib/variants/$n.so; [ $n = base ] && L=$R/structure-slam-pointline_amd/lib/libsslam_frontend.so
   for ov in "--no-overlap" ""; do
-  SSLAM_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-extras --no-other-workloads $ov --steps 3 --warmup 1 > $O/bench_$n$ov.json 2>/dev/null
+  SSLAM_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-extras --no-other-workloads $ov --steps 3 --warmup 1 > $O/bench_$n$ov.json 2>/dev/null
   python - <<PY
 import json
 try:

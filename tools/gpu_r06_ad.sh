@@ -14,7 +14,7 @@ two defer_c X=1
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/kt; (cd $R && timeout 200 rocprofv3 --kernel-trace --stats -d $O/kt -- tools/step_check 12288 5 2 > $O/kt.log 2>&1; python tools/rocpd_timeline.py $O/kt $R/profiles/r06_final_kernel_trace_one_stream.txt $O/timeline_defer.txt; rm -rf $O/kt)
 cd $R
-timeout 900 python bench.py --no-cpu-baseline --no-other-workloads > $O/bench.json 2> $O/bench.err; tail -c 200 $O/bench.err; python -c "
+timeout 900 python bench.py --full --no-cpu-baseline --no-other-workloads > $O/bench.json 2> $O/bench.err; tail -c 200 $O/bench.err; python -c "
 import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print(round(d['value']), d['ms_per_step'], d['config'].get('gather_check'), d.get('cpu_baseline'))"
-SSLAM_LBD_DEFER=0 timeout 900 python bench.py --no-cpu-baseline --no-other-workloads --no-extras > $O/bench_nodefer.json 2> $O/bench_nodefer.err; python -c "
+SSLAM_LBD_DEFER=0 timeout 900 python bench.py --full --no-cpu-baseline --no-other-workloads --no-extras > $O/bench_nodefer.json 2> $O/bench_nodefer.err; python -c "
 import json; d=json.loads(open('$O/bench_nodefer.json').read().strip().splitlines()[-1]); print(round(d['value']), d['ms_per_step'])"

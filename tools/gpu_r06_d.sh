@@ -19,13 +19,13 @@ rm -rf $O/kt; (cd $R && timeout 200 rocprofv3 --kernel-trace --stats -d $O/kt --
 cd $R
 timeout 60 tools/gather_probe 16 6 > $O/gather_probe.json 2>&1; cat $O/gather_probe.json
 timeout 1200 python -m pytest tests -q -m gpu -x --durations=8 > $O/pytest_gpu.txt 2>&1; echo "rc=$?" >> $O/pytest_gpu.txt; tail -16 $O/pytest_gpu.txt
-timeout 600 python bench.py --no-other-workloads --no-pcie > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; python - <<'PY'
+timeout 600 python bench.py --full --no-other-workloads --no-pcie > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; python - <<'PY'
 import json
 d = json.loads(open('gpurun_out/r06d/bench.json').read().strip().splitlines()[-1])
 print(round(d['value']), d['ms_per_step'], d['roofline']['bound'], d['roofline']['frac'], d['roofline']['bound_note'])
 print(json.dumps(d['roofline']['issue'])[:600]); print(json.dumps(d['roofline']['random_sector'])[:900]); print(d['cpu_baseline']['value'], d['cpu_baseline']['ms_per_frame'], d['cpu_baseline']['parity_vs_gpu'])
 PY
-for m in pyr 1; do SSLAM_POINTS_AT_CORE=$m timeout 600 python bench.py --workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/bench_c4_$m.json 2> $O/bench_c4_$m.err; python - <<PY
+for m in pyr 1; do SSLAM_POINTS_AT_CORE=$m timeout 600 python bench.py --full --workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/bench_c4_$m.json 2> $O/bench_c4_$m.err; python - <<PY
 import json
 d = json.loads(open('gpurun_out/r06d/bench_c4_$m.json').read().strip().splitlines()[-1]); print('c4 gate $m', round(d['value']), d['ms_per_step'])
 PY

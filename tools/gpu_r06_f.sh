@@ -9,7 +9,7 @@ run sobel_main SSLAM_LBD_SOBEL_MAIN=1
 run default_again
 STEP_PROFILE=1 timeout 100 tools/step_check 12288 3 1 1 > $O/step_one_stream.txt 2>&1; head -2 $O/step_one_stream.txt | cut -c1-420
 SSLAM_LBD_SOBEL_MAIN=1 STEP_PROFILE=1 timeout 100 tools/step_check 12288 3 1 1 > $O/step_one_stream_sobel_main.txt 2>&1; head -2 $O/step_one_stream_sobel_main.txt | cut -c1-420
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; python - <<'PY'
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; python - <<'PY'
 import json
 d = json.loads(open('gpurun_out/r06f/bench.json').read().strip().splitlines()[-1])
 print(round(d['value']), d['ms_per_step'], d['roofline']['bound'], d['roofline']['frac'], d['latency']['lines_extract_hipEvent'])

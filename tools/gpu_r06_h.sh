@@ -17,7 +17,7 @@ run line_high STEP_LINE_PRIO=-1
 run line_high_point_low STEP_LINE_PRIO=-1 STEP_POINT_PRIO=1
 HOST_BATCH_BENCH_FRAMES=1 timeout 300 python tools/bench_host_batch.py 24576 0 > $O/host_default.txt 2>&1; tail -4 $O/host_default.txt | cut -c1-200
 HOST_BATCH_BENCH_FRAMES=1 timeout 300 python tools/bench_host_batch.py 18432 0 > $O/host_default_18432.txt 2>&1; tail -4 $O/host_default_18432.txt | cut -c1-200
-timeout 900 python bench.py --no-other-workloads > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; python - <<'PY'
+timeout 900 python bench.py --full --no-other-workloads > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; python - <<'PY'
 import json
 d = json.loads(open('gpurun_out/r06h/bench.json').read().strip().splitlines()[-1])
 print(round(d['value']), d['ms_per_step'], d['roofline']['bound'], d['latency']['lines_extract_hipEvent'])

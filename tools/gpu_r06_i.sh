@@ -5,7 +5,7 @@ set -x
 R=$GRAFT_REPO_ROOT; cd $R
 O=$R/gpurun_out/r06i; mkdir -p $O
 for v in 1 0; do SSLAM_LSD_SPILLFREE=$v timeout 300 python tools/small_batch_probe.py 96 128 256 512 1024 2048 3072 4096 > $O/small_batches_spillfree$v.txt 2>&1; tail -8 $O/small_batches_spillfree$v.txt; done
-for v in 1 0; do SSLAM_LSD_SPILLFREE=$v timeout 600 python bench.py --workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/bench_c4_spillfree$v.json 2> $O/bench_c4_$v.err; python - <<PY
+for v in 1 0; do SSLAM_LSD_SPILLFREE=$v timeout 600 python bench.py --full --workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/bench_c4_spillfree$v.json 2> $O/bench_c4_$v.err; python - <<PY
 import json
 d = json.loads(open('gpurun_out/r06i/bench_c4_spillfree$v.json').read().strip().splitlines()[-1]); print('c4 spillfree $v', round(d['value']), d['ms_per_step'], d['roofline']['kernels_ms_per_step'].get('k_lsd_regions'))
 PY
