@@ -447,6 +447,38 @@ int sslam_frontend_batch_match(sslam_orb* orb, sslam_lines* lines, const uint8_t
                                sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out, int32_t* nl_out, int lcap, const sslam_batch_match* match);
 
 
+/* ---- camera model: Frame::UndistortKeyPoints / Frame::ComputeImageBounds (src/Frame.cc:483-543) ----------------------------------------
+ * The pinhole + Brown-Conrady model Tracking::Tracking reads from the settings file (src/Tracking.cc:48-72): K = fx, fy, cx, cy and
+ * DistCoef = k1, k2, p1, p2 (+ k3 only when it is non-zero; k3 = 0 and a missing k3 give the same result).  The undistortion is
+ * cv::undistortPoints(pts, pts, K, DistCoef, noArray(), K) restated in fp64 (DESIGN.md decision D13: five fixed iterations).  As in the
+ * reference, ONLY k1 decides whether anything happens: k1 == 0 leaves every point where it is (mvKeysUn = mvKeys) and the bounds are
+ * (0, w, 0, h), whatever k2, p1, p2, k3 hold.  Line features are never undistorted (the reference has no mvKeylinesUn step). */
+typedef struct sslam_camera { float fx, fy, cx, cy, k1, k2, p1, p2, k3; } sslam_camera;      /* src/Tracking.cc:48-72; k3 = 0 when absent */
+/* Frame::ComputeImageBounds (src/Frame.cc:515-543): bounds_out = {mnMinX, mnMaxX, mnMinY, mnMaxY} of a w x h image, from the undistorted
+ * corners (0,0), (w,0), (0,h), (w,h).  Host-only: needs no device and no context. */
+int sslam_camera_image_bounds(const sslam_camera* cam, int w, int h, float bounds_out[4]);
+/* Frame::UndistortKeyPoints (src/Frame.cc:483-513): kp_un[i] = kp[i] with pt.x, pt.y undistorted; size, angle, response, octave and class_id
+ * are copied unchanged (:507-510).  Host pointers, synchronous; kp_un == kp is allowed. */
+int sslam_undistort_keypoints(sslam_ctx* ctx, const sslam_camera* cam, const sslam_keypoint* kp, int n, sslam_keypoint* kp_un);
+/* Batch/device form over the layout of sslam_orb_extract_batch_dev: frame f = rows [f*cap, f*cap + d_counts[f]) of d_kp -> the same rows of
+ * d_kp_un; rows at or past a frame's count are not touched.  d_kp_un == d_kp (in place) is allowed.  With k1 == 0 it is a device copy of
+ * the valid rows.  Enqueued on `stream`. */
+int sslam_undistort_keypoints_batch_dev(sslam_ctx* ctx, const sslam_camera* cam, const sslam_keypoint* d_kp, const int32_t* d_counts,
+                                        int nframes, int cap, sslam_keypoint* d_kp_un, void* stream);
+/* The camera of the Frame an extractor feeds (NULL clears it, the default).  With a camera set, sslam_frame_from_orb snapshots the UNDISTORTED
+ * keypoints of the last sslam_orb_extract -- the mvKeysUn the Frame constructor hands the matchers (src/Frame.cc:95) -- while
+ * sslam_orb_extract itself keeps returning mvKeys. */
+int sslam_orb_set_camera(sslam_orb* orb, const sslam_camera* cam);
+/* sslam_frontend_batch_match (match may be NULL: sslam_frontend_batch) for a camera with lens distortion: kp_out stays mvKeys, byte-equal to
+ * what sslam_frontend_batch_match returns, and kpun_out[n*cap] receives mvKeysUn (rows past a frame's count unspecified).  With `match`,
+ * vbPrevMatched and SearchForInitialization take mvKeysUn of both frames, as src/Tracking.cc:340-342 and src/ORBmatcher.cc:408-523 do;
+ * match->bounds are used as passed -- pass sslam_camera_image_bounds(cam, w, h).  The 2-NN and the line matcher are unchanged.  The
+ * undistorted rows travel beside the raw ones, the predecessor carried across chunk boundaries included. */
+int sslam_frontend_batch_match_camera(sslam_orb* orb, sslam_lines* lines, const sslam_camera* cam, const uint8_t* images, int n, int w, int h,
+                                      size_t stride, size_t image_stride, int chunk, sslam_keypoint* kp_out, sslam_keypoint* kpun_out,
+                                      uint8_t* desc_out, int32_t* nkp_out, int cap, sslam_keyline* kl_out, uint8_t* ldesc_out,
+                                      double* linefn_out, int32_t* nl_out, int lcap, const sslam_batch_match* match);
+
 /* ---- multi-GPU batch mode (SURVEY.md §8(b) "sslam_group_create + sslam_frontend_batch_sharded", §8(e)) ----------------------
  * north_star: "a batch-of-frames mode shards independent images across the 8 GPUs of one node with RCCL over xGMI only for the final
  * keypoint/line gather".  Frames are independent units: global frame i lives on GPU i % G.  Each GPU runs the single-GPU path on its

@@ -16,8 +16,12 @@
 //   * sslam_frontend_batch_match adds the match stage of BASELINE configs[2] ("extract + Hamming match vs previous frame"): frame i is
 //     matched against frame i-1 of the call -- ORBmatcher::SearchForInitialization, the dense Hamming 2-NN and the LSD line matcher, the
 //     three launches pipeline.py times for resident frames.  The device arrays of a chunk carry one extra frame in front (the last frame
-//     of the chunk before it), so "previous" and "current" are the same arrays one frame apart and the *_batch_dev matchers run unchanged.
+//     of the chunk before it), so "previous" and "current" are the same arrays one frame apart and the *_batch_dev matchers run unchanged;
+//   * sslam_frontend_batch_match_camera adds Frame::UndistortKeyPoints (src/Frame.cc:483-513) behind the extraction: the undistorted rows
+//     (mvKeysUn) live beside the raw ones in their own array of C + 1 frames, the carried predecessor included, and the match stage reads
+//     them; without a camera none of this is allocated, launched or copied.
 #include "common.h"
+#include "camera.h"
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
@@ -86,11 +90,12 @@ struct CopyPool {
 struct Slot {
     DevBuf dIn, dKp, dDesc, dN, dKl, dLd, dFn, dNl, dStatus;
     DevBuf dPm, dM12, dNm, dKnnI, dKnnD, dLp, dNlp;      // match stage: vbPrevMatched, vnMatches12, counts, 2-NN, line pairs
+    DevBuf dKpUn;                                        // camera form: mvKeysUn, laid out like dKp
     HostPinned hIn, hOut, hStatus;
     hipEvent_t evIn = nullptr, evPoint = nullptr, evLines = nullptr, evOut = nullptr;
     int first = 0, count = 0;            // frames of the chunk in flight
     void release() {
-        dIn.release(); dKp.release(); dDesc.release(); dN.release(); dKl.release(); dLd.release(); dFn.release(); dNl.release(); dStatus.release(); dPm.release(); dM12.release(); dNm.release(); dKnnI.release(); dKnnD.release(); dLp.release(); dNlp.release(); hIn.release(); hOut.release(); hStatus.release();
+        dIn.release(); dKp.release(); dDesc.release(); dN.release(); dKl.release(); dLd.release(); dFn.release(); dNl.release(); dStatus.release(); dPm.release(); dM12.release(); dNm.release(); dKnnI.release(); dKnnD.release(); dLp.release(); dNlp.release(); dKpUn.release(); hIn.release(); hOut.release(); hStatus.release();
         for (hipEvent_t* e : {&evIn, &evPoint, &evLines, &evOut}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
     }
 };
@@ -114,9 +119,11 @@ void free_batch_cache(void* p) { delete (BatchCache*)p; }
 namespace {
 int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t* images, int n, int w, int h, size_t stride, size_t image_stride, int chunk,
                sslam_keypoint* kp_out, uint8_t* desc_out, int32_t* nkp_out, int cap,
-               sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out, int32_t* nl_out, int lcap, const sslam_batch_match* M) {
+               sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out, int32_t* nl_out, int lcap, const sslam_batch_match* M,
+               const sslam_camera* cam = nullptr, sslam_keypoint* kpun_out = nullptr) {
     sslam_ctx* ctx = orb ? sslam_orb_context(orb) : nullptr;
     if (!orb || !ctx || n < 0 || w <= 0 || h <= 0 || stride < (size_t)w || cap <= 0 || (n > 0 && (!images || !kp_out || !desc_out || !nkp_out)) ||
+        (cam && (cam->fx == 0.0f || cam->fy == 0.0f || (n > 0 && !kpun_out))) ||
         (lines && (sslam_lines_context(lines) != ctx || lcap <= 0 || (n > 0 && (!kl_out || !ldesc_out || !linefn_out || !nl_out)))) || (n > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w) ||
         (M && n > 0 && (!M->init_matches12 || !M->init_nmatches || (M->knn_idx == nullptr) != (M->knn_dist == nullptr) || (lines && (!M->line_pairs || !M->line_npairs))))) {
         set_error("%s: invalid arguments", fn); return SSLAM_ERR_INVALID;
@@ -126,13 +133,14 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
     SSLAM_HIP(hipSetDevice(ctx->device));
     const size_t fpx = (size_t)w * h;
     const bool knn = M && M->knn_idx, lmatch = M && lines;
+    const bool U = cam != nullptr;      // camera form: mvKeysUn beside mvKeys
     int C = std::min(n, chunk > 0 ? chunk : 6144);
     if (chunk <= 0) {      // the default follows the core's wave slots, but never asks for more than a third of the free device memory
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
             // per frame: the ORB workspace (pyramid + three candidate planes ~ 4.2 B per pixel), the LSD / LBD workspace (0.64 x 28 B of planes, order list and
             // region spill per pixel, 4 B of Sobel pairs, ~1.4 MB of rectangle / NFA records), the two slots of inputs and outputs
-            const size_t perFrame = 6 * fpx + (lines ? 25 * fpx + 1500000 : 0) + 2 * fpx + (size_t)cap * (60 * 3 + (M ? 12 + 20 + (knn ? 32 + 256 : 0) : 0)) + (lines ? (size_t)lcap * 124 * 3 : 0) + 65536;
+            const size_t perFrame = 6 * fpx + (lines ? 25 * fpx + 1500000 : 0) + 2 * fpx + (size_t)cap * (60 * 3 + (U ? 28 * 3 : 0) + (M ? 12 + 20 + (knn ? 32 + 256 : 0) : 0)) + (lines ? (size_t)lcap * 124 * 3 : 0) + 65536;
             const size_t fit = freeB / 3 / std::max<size_t>(perFrame, 1);
             if ((size_t)C > fit) C = (int)std::max<size_t>(fit, 1);      // little free memory (another process on the GPU, very large frames): smaller chunks, down to one frame; only then can an allocation fail
         }
@@ -143,7 +151,8 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
     const size_t oKp = take(sizeof(sslam_keypoint) * (size_t)C * cap), oDesc = take(32 * (size_t)C * cap), oN = take(4 * (size_t)C),
                  oKl = take(lines ? sizeof(sslam_keyline) * (size_t)C * lcap : 0), oLd = take(lines ? 32 * (size_t)C * lcap : 0), oFn = take(lines ? 24 * (size_t)C * lcap : 0),
                  oNl = take(lines ? 4 * (size_t)C : 0), oM12 = take(M ? 4 * (size_t)C * cap : 0), oNm = take(M ? 4 * (size_t)C : 0),
-                 oKi = take(knn ? 8 * (size_t)C * cap : 0), oKd = take(knn ? 8 * (size_t)C * cap : 0), oLp = take(lmatch ? 8 * (size_t)C * lcap : 0), oNlp = take(lmatch ? 4 * (size_t)C : 0);
+                 oKi = take(knn ? 8 * (size_t)C * cap : 0), oKd = take(knn ? 8 * (size_t)C * cap : 0), oLp = take(lmatch ? 8 * (size_t)C * lcap : 0), oNlp = take(lmatch ? 4 * (size_t)C : 0),
+                 oKpUn = take(U ? sizeof(sslam_keypoint) * (size_t)C * cap : 0);
     const size_t outBytes = o;
     // pinned (hipHostMalloc / hipHostRegister) caller memory is copied from / to directly; pageable memory goes through the pinned staging
     auto is_pinned = [](const void* q) {
@@ -152,7 +161,7 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
         return a.type == hipMemoryTypeHost;
     };
     const bool inDirect = stride == (size_t)w && (n == 1 || image_stride == fpx) && is_pinned(images);
-    const bool outDirect = is_pinned(kp_out) && is_pinned(desc_out) && is_pinned(nkp_out) &&
+    const bool outDirect = is_pinned(kp_out) && is_pinned(desc_out) && is_pinned(nkp_out) && (!U || is_pinned(kpun_out)) &&
                            (!lines || (is_pinned(kl_out) && is_pinned(ldesc_out) && is_pinned(linefn_out) && is_pinned(nl_out))) &&
                            (!M || (is_pinned(M->init_matches12) && is_pinned(M->init_nmatches) && (!knn || (is_pinned(M->knn_idx) && is_pinned(M->knn_dist))) &&
                                    (!lmatch || (is_pinned(M->line_pairs) && is_pinned(M->line_npairs)))));
@@ -178,6 +187,7 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
         if (M && ((rc = s.dPm.ensure(8 * (size_t)C * cap)) || (rc = s.dM12.ensure(4 * (size_t)C * cap)) || (rc = s.dNm.ensure(4 * (size_t)C)) ||
                   (knn && ((rc = s.dKnnI.ensure(8 * (size_t)C * cap)) || (rc = s.dKnnD.ensure(8 * (size_t)C * cap)))) ||
                   (lmatch && ((rc = s.dLp.ensure(8 * (size_t)C * lcap)) || (rc = s.dNlp.ensure(4 * (size_t)C)))))) return rc;
+        if (U && (rc = s.dKpUn.ensure(sizeof(sslam_keypoint) * F1 * cap))) return rc;
         for (hipEvent_t* e : {&s.evIn, &s.evPoint, &s.evLines, &s.evOut})
             if (!*e && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { set_error("%s: hipEventCreate failed", fn); return SSLAM_ERR_HIP; }
         if (n <= C) break;                 // one chunk: the second slot is never used
@@ -208,6 +218,7 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
             std::memcpy(kp_out + g * cap, H + oKp + sizeof(sslam_keypoint) * (size_t)a * cap, sizeof(sslam_keypoint) * c * cap);
             std::memcpy(desc_out + 32 * g * cap, H + oDesc + 32 * (size_t)a * cap, 32 * c * cap);
             std::memcpy(nkp_out + g, H + oN + 4 * (size_t)a, 4 * c);
+            if (U) std::memcpy(kpun_out + g * cap, H + oKpUn + sizeof(sslam_keypoint) * (size_t)a * cap, sizeof(sslam_keypoint) * c * cap);
             if (lines) {
                 std::memcpy(kl_out + g * lcap, H + oKl + sizeof(sslam_keyline) * (size_t)a * lcap, sizeof(sslam_keyline) * c * lcap);
                 std::memcpy(ldesc_out + 32 * g * lcap, H + oLd + 32 * (size_t)a * lcap, 32 * c * lcap);
@@ -251,6 +262,7 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
         // the chunk's frames start one frame into the feature arrays
         sslam_keypoint* dKp = s.dKp.as<sslam_keypoint>() + cap; uint8_t* dDesc = s.dDesc.as<uint8_t>() + 32 * (size_t)cap; int32_t* dN = s.dN.as<int32_t>() + 1;
         uint8_t* dLd = lines ? s.dLd.as<uint8_t>() + 32 * (size_t)lcap : nullptr; int32_t* dNl = lines ? s.dNl.as<int32_t>() + 1 : nullptr;
+        sslam_keypoint* dKpUn = U ? s.dKpUn.as<sslam_keypoint>() + cap : nullptr;
         if (M) {
             // frame 0 of the array = the frame in front of this chunk: the last frame of the chunk before (the other slot, same streams: ordered
             // behind its extraction), or no frame at all for the first chunk of the call (count 0: nothing matches)
@@ -261,7 +273,8 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
                 const Slot& q = slot[(k + 1) & 1]; const size_t last = (size_t)C;      // every chunk but the last one is full
                 ok = hipMemcpyAsync(s.dKp.p, q.dKp.as<sslam_keypoint>() + last * cap, sizeof(sslam_keypoint) * (size_t)cap, hipMemcpyDeviceToDevice, stP) == hipSuccess &&
                      hipMemcpyAsync(s.dDesc.p, q.dDesc.as<uint8_t>() + 32 * last * cap, 32 * (size_t)cap, hipMemcpyDeviceToDevice, stP) == hipSuccess &&
-                     hipMemcpyAsync(s.dN.p, q.dN.as<int32_t>() + last, 4, hipMemcpyDeviceToDevice, stP) == hipSuccess;
+                     hipMemcpyAsync(s.dN.p, q.dN.as<int32_t>() + last, 4, hipMemcpyDeviceToDevice, stP) == hipSuccess &&
+                     (!U || hipMemcpyAsync(s.dKpUn.p, q.dKpUn.as<sslam_keypoint>() + last * cap, sizeof(sslam_keypoint) * (size_t)cap, hipMemcpyDeviceToDevice, stP) == hipSuccess);
                 if (ok && lines) ok = hipMemcpyAsync(s.dLd.p, q.dLd.as<uint8_t>() + 32 * last * lcap, 32 * (size_t)lcap, hipMemcpyDeviceToDevice, stLn) == hipSuccess &&
                                       hipMemcpyAsync(s.dNl.p, q.dNl.as<int32_t>() + last, 4, hipMemcpyDeviceToDevice, stLn) == hipSuccess;
             }
@@ -278,11 +291,13 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
         if (twoStreams && (hipEventRecord(s.evLines, stL) != hipSuccess || (!guestForm && hipStreamWaitEvent(stP, B.evCore, 0) != hipSuccess))) { set_error("%s: event failed", fn); rc = SSLAM_ERR_HIP; break; }
         if ((rc = sslam_orb_extract_batch_dev(orb, s.dIn.as<uint8_t>(), w, h, (size_t)w, fpx, c, dKp, dDesc, dN, cap, stP))) break;
         if ((rc = sslam_orb_batch_status_dev(orb, cap, s.dStatus.as<int32_t>(), stP))) break;
+        if (U && (rc = undistort_launch(ctx, *cam, dKp, dN, 0, c, cap, dKpUn, stP))) break;       // Frame::UndistortKeyPoints (src/Frame.cc:95)
         if (M) {      // previous frame = F1 (query), current frame = F2 (train), as Tracking::MonocularInitialization calls it (src/Tracking.cc:330-345)
             const size_t rows = (size_t)c * cap;
-            hipLaunchKernelGGL(k_prev_matched_init, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stP, s.dKp.as<sslam_keypoint>(), rows, s.dPm.as<float2>());
+            const sslam_keypoint* kpm = U ? s.dKpUn.as<sslam_keypoint>() : s.dKp.as<sslam_keypoint>();      // the matchers read mvKeysUn
+            hipLaunchKernelGGL(k_prev_matched_init, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stP, kpm, rows, s.dPm.as<float2>());
             if (hipGetLastError() != hipSuccess) { set_error("%s: launch failed", fn); rc = SSLAM_ERR_HIP; break; }
-            if ((rc = sslam_orb_search_for_initialization_batch_dev(ctx, s.dKp.as<sslam_keypoint>(), s.dDesc.as<uint8_t>(), s.dN.as<int32_t>(), dKp, dDesc, dN, cap, c, s.dPm.as<float>(),
+            if ((rc = sslam_orb_search_for_initialization_batch_dev(ctx, kpm, s.dDesc.as<uint8_t>(), s.dN.as<int32_t>(), U ? dKpUn : dKp, dDesc, dN, cap, c, s.dPm.as<float>(),
                                                                     s.dM12.as<int32_t>(), s.dNm.as<int32_t>(), M->window_size, M->nnratio, M->check_orientation, M->bounds, stP))) break;
             if (knn && (rc = sslam_hamming_knn2_batch_dev(ctx, s.dDesc.as<uint8_t>(), s.dN.as<int32_t>(), dDesc, dN, cap, c, s.dKnnI.as<int32_t>(), s.dKnnD.as<int32_t>(), stP))) break;
         }
@@ -299,6 +314,7 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
         down(kp_out + g * cap, oKp, dKp, sizeof(sslam_keypoint) * (size_t)c * cap);
         down(desc_out + 32 * g * cap, oDesc, dDesc, 32 * (size_t)c * cap);
         down(nkp_out + g, oN, dN, 4 * (size_t)c);
+        if (U) down(kpun_out + g * cap, oKpUn, dKpUn, sizeof(sslam_keypoint) * (size_t)c * cap);
         if (ok) ok = hipMemcpyAsync(s.hStatus.p, s.dStatus.p, 32, hipMemcpyDeviceToHost, cpOut) == hipSuccess;
         if (lines) {
             down(kl_out + g * lcap, oKl, s.dKl.p, sizeof(sslam_keyline) * (size_t)c * lcap);
@@ -337,6 +353,15 @@ extern "C" int sslam_frontend_batch_match(sslam_orb* orb, sslam_lines* lines, co
                                           sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out, int32_t* nl_out, int lcap, const sslam_batch_match* match) {
     if (!match) { set_error("sslam_frontend_batch_match: invalid arguments"); return SSLAM_ERR_INVALID; }
     return batch_impl("sslam_frontend_batch_match", orb, lines, images, n, w, h, stride, image_stride, chunk, kp_out, desc_out, nkp_out, cap, kl_out, ldesc_out, linefn_out, nl_out, lcap, match);
+}
+
+extern "C" int sslam_frontend_batch_match_camera(sslam_orb* orb, sslam_lines* lines, const sslam_camera* cam, const uint8_t* images, int n, int w, int h,
+                                                 size_t stride, size_t image_stride, int chunk, sslam_keypoint* kp_out, sslam_keypoint* kpun_out,
+                                                 uint8_t* desc_out, int32_t* nkp_out, int cap, sslam_keyline* kl_out, uint8_t* ldesc_out,
+                                                 double* linefn_out, int32_t* nl_out, int lcap, const sslam_batch_match* match) {
+    if (!cam) { set_error("sslam_frontend_batch_match_camera: invalid arguments"); return SSLAM_ERR_INVALID; }
+    return batch_impl("sslam_frontend_batch_match_camera", orb, lines, images, n, w, h, stride, image_stride, chunk, kp_out, desc_out, nkp_out, cap,
+                      kl_out, ldesc_out, linefn_out, nl_out, lcap, match, cam, kpun_out);
 }
 
 // Releases the staging buffers, streams and events sslam_frontend_batch keeps per context between calls (they are also released with the context).

@@ -16,6 +16,7 @@
 //   * orientation + blur + rBRIEF run fused, one wave per keypoint, on a 43x43 patch
 //     staged in LDS (no blurred image in HBM).
 #include "common.h"
+#include "camera.h"
 #include <cmath>
 #include <algorithm>
 
@@ -927,6 +928,7 @@ struct sslam_orb {
     bool constsUploaded = false;
     int blurVariant = 0;            // sslam_orb_set_blur_variant
     hipEvent_t gateEvent = nullptr;         // sslam_orb_set_gate_event
+    bool hasCamera = false; sslam_camera camera{};      // sslam_orb_set_camera: sslam_frame_from_orb snapshots mvKeysUn
     DevBuf dToep; int toepVariant = -1, toepSum = 0;      // the blur's band matrix as matrix-core operands, for the taps of blurVariant
 };
 
@@ -1400,7 +1402,23 @@ extern "C" int sslam_frame_from_orb(sslam_orb* o, const float bounds[4], sslam_f
     if (!o || !bounds || !out) { set_error("sslam_frame_from_orb: invalid arguments"); return SSLAM_ERR_INVALID; }
     if (o->lastN < 0) { set_error("sslam_frame_from_orb: no sslam_orb_extract call to snapshot"); return SSLAM_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lk(o->ctx->mu);
-    return sslam_frame_from_device(o->ctx, 0, o->dKp.p, o->dDesc.as<uint8_t>(), o->lastN, bounds, out);
+    int rc = sslam_frame_from_device(o->ctx, 0, o->dKp.p, o->dDesc.as<uint8_t>(), o->lastN, bounds, out);
+    if (rc || !o->hasCamera || o->camera.k1 == 0.0f || o->lastN == 0) return rc;
+    // Frame::UndistortKeyPoints (src/Frame.cc:483-513) on the snapshot, in place: the handle holds mvKeysUn
+    sslam_keypoint* d = (*out)->feats.as<sslam_keypoint>();
+    hipError_t e = hipSuccess;
+    if ((rc = undistort_launch(o->ctx, o->camera, d, nullptr, o->lastN, 1, o->lastN, d, o->ctx->stream)) == SSLAM_OK &&
+        (e = hipStreamSynchronize(o->ctx->stream)) != hipSuccess) { set_error("sslam_frame_from_orb: %s", hipGetErrorString(e)); rc = SSLAM_ERR_HIP; }
+    if (rc) { sslam_frame_destroy(*out); *out = nullptr; }
+    return rc;
+}
+
+extern "C" int sslam_orb_set_camera(sslam_orb* o, const sslam_camera* cam) {
+    if (!o || (cam && (cam->fx == 0.0f || cam->fy == 0.0f))) { set_error("sslam_orb_set_camera: invalid arguments"); return SSLAM_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lk(o->ctx->mu);
+    o->hasCamera = cam != nullptr;
+    o->camera = cam ? *cam : sslam_camera{};
+    return SSLAM_OK;
 }
 
 extern "C" sslam_ctx* sslam_orb_context(sslam_orb* o) { return o ? o->ctx : nullptr; }

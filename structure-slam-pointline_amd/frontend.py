@@ -196,6 +196,18 @@ class Context:
                                     _p(pairs), cap, C.byref(n), C.byref(mad), C.byref(mad12)))
         return pairs[:n.value].copy(), mad.value, mad12.value
 
+    # ---- camera model ---------------------------------------------------------
+    def undistort_keypoints(self, cam, kp):
+        """Frame::UndistortKeyPoints (sslam_undistort_keypoints): a copy of the keypoint records with pt.x / pt.y undistorted (mvKeysUn)"""
+        kp = np.ascontiguousarray(kp, KP_DTYPE)
+        out = np.empty_like(kp)
+        _chk(lib().sslam_undistort_keypoints(self.h, C.byref(cam), _p(kp), len(kp), _p(out)))
+        return out
+
+    def undistort_keypoints_batch_dev(self, cam, d_kp, d_counts, nframes, cap, d_kp_un, stream=None):
+        """sslam_undistort_keypoints_batch_dev on device buffers laid out like sslam_orb_extract_batch_dev's (d_kp_un may be d_kp)"""
+        _chk(lib().sslam_undistort_keypoints_batch_dev(self.h, C.byref(cam), _p(d_kp), _p(d_counts), int(nframes), int(cap), _p(d_kp_un), C.c_void_p(stream or 0)))
+
 
 class Vocabulary:
     """Device-resident DBoW2 vocabulary tree (sslam_vocab_*): CSR children lists in DBoW2's node numbering."""
@@ -382,6 +394,50 @@ def frontend_batch_match_raw(orb, lines, images, out, mout, chunk=0, window=100,
     return out, mout
 
 
+class Camera(C.Structure):
+    """sslam_camera (include/sslam_frontend.h): K and DistCoef as Tracking::Tracking reads them (src/Tracking.cc:48-72); k3 = 0 when absent"""
+    _fields_ = [(f, C.c_float) for f in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+
+def camera_image_bounds(cam, w, h):
+    """Frame::ComputeImageBounds (sslam_camera_image_bounds, host-only): (mnMinX, mnMaxX, mnMinY, mnMaxY) as float32 values"""
+    b = (C.c_float * 4)()
+    _chk(lib().sslam_camera_image_bounds(C.byref(cam), int(w), int(h), b))
+    return tuple(np.float32(v) for v in b)
+
+
+def frontend_batch_camera_alloc(n, cap, lcap, pinned=False):
+    """the result arrays of sslam_frontend_batch_match_camera: frontend_batch_alloc's seven plus kpun[n, cap] (mvKeysUn)"""
+    if not pinned:
+        kpun = np.empty((n, cap), KP_DTYPE); kpun.view(np.uint8).reshape(-1)[::4096] = 0
+    else:
+        import torch
+        nbytes = n * cap * KP_DTYPE.itemsize
+        kpun = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=True).numpy()[:nbytes].view(KP_DTYPE).reshape(n, cap)
+    return frontend_batch_alloc(n, cap, lcap, pinned=pinned) + (kpun,)
+
+
+def frontend_batch_match_camera_raw(orb, lines, cam, images, out, mout=None, chunk=0, window=100, nnratio=0.9, check_orientation=True, bounds=None,
+                                    line_gate_scale=0.5, line_ratio_mode=False):
+    """sslam_frontend_batch_match_camera into arrays from frontend_batch_camera_alloc (and frontend_batch_match_alloc, or mout=None for no match
+    stage); bounds default to camera_image_bounds(cam, w, h), what the frame's mnMinX .. mnMaxY are"""
+    n, h, w = images.shape
+    kp, desc, nk, kl, ld, fn, nl, kpun = out
+    M = None
+    if mout is not None:
+        m12, nm, ki, kd, lp, nlp = mout
+        M = BatchMatch()
+        M.window_size = int(window); M.nnratio = float(nnratio); M.check_orientation = int(bool(check_orientation))
+        M.bounds = (C.c_float * 4)(*(bounds if bounds is not None else camera_image_bounds(cam, w, h)))
+        M.line_gate_scale = float(line_gate_scale); M.line_ratio_mode = int(bool(line_ratio_mode))
+        vp = lambda a: a.ctypes.data if a is not None else None
+        M.init_matches12 = vp(m12); M.init_nmatches = vp(nm); M.knn_idx = vp(ki); M.knn_dist = vp(kd); M.line_pairs = vp(lp); M.line_npairs = vp(nlp)
+    _chk(lib().sslam_frontend_batch_match_camera(orb.h, lines.h if lines is not None else None, C.byref(cam), _p(images), n, w, h, C.c_size_t(w),
+                                                 C.c_size_t(w * h), int(chunk), _p(kp), _p(kpun), _p(desc), _p(nk), orb.cap, _p(kl), _p(ld), _p(fn), _p(nl),
+                                                 int(kl.shape[1]), C.byref(M) if M is not None else None))
+    return out, mout
+
+
 def frontend_batch(orb, lines, images, chunk=0, max_lines=None, pinned=False):
     """sslam_frontend_batch: images = uint8 array [n, h, w] in HOST memory -> per-frame (keypoints, descriptors, keylines, line descriptors,
     line functions) lists; `lines` may be None (ORB only).  pinned=True allocates the result arrays in pinned memory (torch), so that the
@@ -423,6 +479,10 @@ class OrbExtractor:
     def set_gate_event(self, hip_event):
         """hipEvent_t handle (int) every following batch call waits for between its pyramid kernels and the rest; 0 / None clears it (sslam_orb_set_gate_event)"""
         _chk(lib().sslam_orb_set_gate_event(self.h, C.c_void_p(int(hip_event or 0))))
+
+    def set_camera(self, cam):
+        """sslam_orb_set_camera: with a Camera, Frame(ctx, orb=self) holds the undistorted keypoints (mvKeysUn); None clears it"""
+        _chk(lib().sslam_orb_set_camera(self.h, C.byref(cam) if cam is not None else None))
 
     def scales(self):
         n = self.nlevels
