@@ -235,7 +235,7 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
         s.count = 0;
         return SSLAM_OK;
     };
-    const bool twoStreams = lines != nullptr && getenv("SSLAM_BATCH_ONE_STREAM") == nullptr;
+    const bool twoStreams = lines != nullptr;
     if (lines) (void)sslam_lines_set_core_event(lines, twoStreams ? (void*)B.evCore : nullptr);
     int k = 0;
     for (int f0 = 0; f0 < n && rc == SSLAM_OK; f0 += C, ++k) {

@@ -21,7 +21,7 @@
 #include <algorithm>
 
 namespace sslam { int launch_nfa_stream(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, uint8_t* clArea, size_t clFrameBytes,
-                                        size_t stageOff, int nframes, int waves, long long spinTicks, size_t ldsPad, int takeMax, int sleepReps, const char* scope); }      // lines_nfa.hip
+                                        size_t stageOff, int nframes, int waves, long long spinTicks, bool besideCore); }      // lines_nfa.hip
 namespace sslam { int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes); }      // lines_nfa.hip
 
 using namespace sslam;
@@ -290,24 +290,76 @@ static int lines_host_seed_order(sslam_lines* L, uint8_t* ws, int nframes, hipSt
     return SSLAM_OK;
 }
 
+// The environment knobs of the line path, read on every call (tests and bench.py set them between calls), here and nowhere else in this unit.
+struct LinesKnobs {
+    int lone;                   // SSLAM_LSD_FLAVOUR: 1 = "cl" / "lat" (lone waves where the cluster form does not apply), 0 = "thr"; -1 (unset): lone waves below 1 024 frames
+    bool cluster;               // the cluster form where it applies; false under SSLAM_LSD_CLUSTER=0 or a SSLAM_LSD_FLAVOUR other than "cl"
+    int persist;                // SSLAM_LSD_PERSIST=g: the guest form's grid (0: lines_guest_form's own)
+    int clWgs, clWindow, clSmap;      // the cluster form (lsd_cluster.h): SSLAM_CL_WGS = workgroups per frame (4 waves each); SSLAM_CL_WINDOW = how many sub-chunks of 16 seed
+                                      // positions the helpers may run ahead (-1: no helpers at all, the main wave alone), + 1 << 20 under SSLAM_CL_NO_FEEDER (the main wave
+                                      // fetches everything itself); SSLAM_CL_SMAP = cell size (log2) of the shared map that steers the helpers' seed choice (-1: none)
+    int nfaStreamWaves;         // SSLAM_NFA_STREAM: consumer waves per frame of the NFA stage next to the cluster form (0: the stage behind the core, the round-4 default)
+    long long nfaSpinTicks;     // SSLAM_NFA_STREAM_TICKS: how long a consumer wave waits without progress before it leaves its blocks to the launch behind the core
+};
+static LinesKnobs lines_knobs() {
+    // 50 ms of the 100 MHz clock (ten single-frame cores) of waiting; 0.2 s in round 5: on a GPU shared with another process the consumers can be resident before the producer,
+    // and the wait was the spike
+    LinesKnobs K{-1, true, 0, 10, 640 / CL_SUB, 0, 16, 5000000};
+    if (const char* e = getenv("SSLAM_LSD_FLAVOUR")) { K.lone = e[0] == 'l' || e[0] == 'c'; K.cluster = e[0] == 'c'; }
+    if (const char* e = getenv("SSLAM_LSD_CLUSTER")) K.cluster = K.cluster && atoi(e) != 0;
+    if (const char* e = getenv("SSLAM_LSD_PERSIST")) { const int g = atoi(e) & ~7; if (g >= 8) K.persist = g; }
+    if (const char* e = getenv("SSLAM_CL_WGS")) K.clWgs = std::max(1, std::min(CL_MAXWG, atoi(e)));
+    if (const char* e = getenv("SSLAM_CL_WINDOW")) K.clWindow = std::max(-1, atoi(e));
+    if (getenv("SSLAM_CL_NO_FEEDER") && K.clWindow >= 0) K.clWindow |= 1 << 20;
+    if (const char* e = getenv("SSLAM_CL_SMAP")) K.clSmap = atoi(e);
+    if (const char* e = getenv("SSLAM_NFA_STREAM")) { const int n = atoi(e); K.nfaStreamWaves = std::max(0, std::min(64, n == 1 ? 16 : n)); }
+    if (const char* e = getenv("SSLAM_NFA_STREAM_TICKS")) K.nfaSpinTicks = std::max(0ll, atoll(e));
+    return K;
+}
+
 // Whether a batch of `nframes` runs the sequential core in its guest form (lsd_regions.h): a co-running branch was announced (sslam_lines_set_core_event) and the batch is
 // at least two rounds of the persistent grid of 18 (16 for smaller batches) workgroups per compute unit.  18: two SIMDs of a compute unit hold five core waves and keep 32
 // registers free, two hold four and keep 128 -- since k_fast_cells needs 29 registers (round 6, call AQ) its waves fit into either, and the core's fifth wave on half of the
 // SIMDs pays: 151.3 -> 149.3 ms per step (with the 51-register FAST: 153.2).  17 / 19 / 20 per compute unit: 150.8 / 149.4 / 150.0.
-static bool lines_guest_form(const sslam_lines* L, int nframes, int* grid_out) {
+static bool lines_guest_form(const sslam_lines* L, int nframes, const LinesKnobs& K, int* grid_out) {
     int grid = 18 * L->ctx->num_cus;
     if (2 * grid > nframes) grid = 16 * L->ctx->num_cus;
-    bool guest = L->coreEvent != nullptr;
-    if (const char* e = getenv("SSLAM_LSD_GUEST")) guest = atoi(e) != 0;
-    if (const char* e = getenv("SSLAM_LSD_PERSIST")) { const int g = atoi(e) & ~7; if (g >= 8) grid = g; }
+    if (K.persist) grid = K.persist;
     if (grid_out) *grid_out = grid;
     // at least two full rounds of the persistent grid: a batch of 1.5 grids (sslam_frontend_batch's chunks of 6 144 frames) would run half of the slots twice and the
     // other half once -- measured on the bench's frame sequence, 24 576 frames through host memory: 61.1 k frames/s in this form against 66.0 k in the other (profiles/r06g_*)
-    return guest && nframes >= 1024 && 2 * grid <= nframes;
+    return L->coreEvent != nullptr && nframes >= 1024 && 2 * grid <= nframes;
 }
 extern "C" int sslam_lines_core_guest_form(sslam_lines* L, int nframes) {
     if (!L || nframes <= 0) return 0;
-    return lines_guest_form(L, nframes, nullptr) ? 1 : 0;
+    return lines_guest_form(L, nframes, lines_knobs(), nullptr) ? 1 : 0;
+}
+
+// The launch forms of the sequential core (lsd_regions.h, lsd_cluster.h)
+enum class CoreForm {
+    ClusterStream,      // k_lsd_regions_cl<1>, the NFA stage next to it on the side stream (k_nfa_stream)
+    Cluster,            // k_lsd_regions_cl<0>, the NFA stage behind it (SSLAM_NFA_STREAM=0)
+    Lone,               // k_lsd_regions<true, 4>, one wave per frame: the shortest chain
+    Guest,              // k_lsd_regions<false, 4> on a persistent grid (lines_guest_form)
+    PerFrame,           // k_lsd_regions<false, 4>, one workgroup per frame
+    SixWave,            // k_lsd_regions<false, 6>, one workgroup per frame
+};
+
+// Up to 64 frames (one to eight per XCD, four workgroups each) of up to 2 048 x 1 024 scaled pixels take the cluster form -- helper waves on several
+// compute units, results through global memory, monotonic pixel map (lsd_cluster.h).  Per call, cluster form against the multi-wave form of rounds 2-4 (tools/small_batch_probe.py,
+// round 3): 1 frame 5.9 / 7.9 ms, 8: 8.5 / 11.2, 16: 9.0 / 11.9, 24: 9.4 / 12.6, 32: 10.3 / 13.1, 64: 13.5 / 15.7, 96: 21.6 / 15.9
+constexpr int CL_MAXFRAMES = 64;
+
+// Which form a call takes.  Lone waves below 1 024 frames: at most one wave per SIMD is resident, so the instantiation that spills nothing costs no occupancy.  A caller that
+// announced a branch running beside the core (sslam_lines_set_core_event: the bench step's point branch waits for that event) gets the guest form: 16 - 18 persistent workgroups
+// per compute unit of the four-wave instantiation, a third of the registers free for the other branch's waves.  Otherwise up to 16 frames per compute unit (four waves per SIMD
+// anyway; BASELINE configs[3]: 3 072 frames) take the spill-free instantiation, larger batches the six-wave one.  grid: the guest form's grid.
+static CoreForm lines_core_form(const sslam_lines* L, const LsdPlan& P, int nframes, const LinesKnobs& K, int* grid) {
+    if (K.cluster && nframes <= CL_MAXFRAMES && P.sw <= TorusGlobal::XMASK + 1 && P.sh <= TorusGlobal::YMASK + 1)
+        return K.nfaStreamWaves ? CoreForm::ClusterStream : CoreForm::Cluster;
+    if (K.lone >= 0 ? K.lone != 0 : nframes < 1024) return CoreForm::Lone;
+    if (lines_guest_form(L, nframes, K, grid)) return CoreForm::Guest;
+    return nframes <= 16 * L->ctx->num_cus ? CoreForm::PerFrame : CoreForm::SixWave;
 }
 
 extern "C" int sslam_lines_destroy(sslam_lines* L) {
@@ -322,12 +374,173 @@ extern "C" int sslam_lines_destroy(sslam_lines* L) {
     return SSLAM_OK;
 }
 
+// One call of sslam_lines_extract_batch_dev: what its stages share
+struct LinesCall {
+    sslam_lines* L; const LsdPlan& P; const uint8_t* images; size_t pitch, imageStride; int nframes; hipStream_t st; uint8_t* ws;
+};
+
+// Work forked onto the side stream (L->nfaStream) is joined into `st` on EVERY way out of sslam_lines_extract_batch_dev -- also the early error returns: the caller may reuse
+// or free the workspace as soon as `st` is idle, and the side stream's kernels write into it
+struct SideJoin {
+    sslam_lines* L; hipStream_t st; bool forked = false, joined = false;
+    void join() { if (forked && !joined) { (void)hipEventRecord(L->nfaJoin, L->nfaStream); (void)hipStreamWaitEvent(st, L->nfaJoin, 0); joined = true; } }
+    ~SideJoin() { join(); }
+};
+
+static int lines_side_stream_ready(sslam_lines* L) {
+    if (!L->nfaStream) {
+        SSLAM_HIP(hipStreamCreateWithFlags(&L->nfaStream, hipStreamNonBlocking));
+        SSLAM_HIP(hipEventCreateWithFlags(&L->nfaFork, hipEventDisableTiming));
+        SSLAM_HIP(hipEventCreateWithFlags(&L->nfaJoin, hipEventDisableTiming));
+    }
+    return SSLAM_OK;
+}
+
+// LBD's gradient image: blur(5, 1) + Sobel of the SOURCE, fused; it does not depend on the segments
+static void lines_blur_sobel(const LinesCall& c, hipStream_t s) {
+    const LsdPlan& P = c.P;
+    sslam::ProfScope _ps(c.L->ctx, "k_blur_sobel", s);
+    hipLaunchKernelGGL(k_blur_sobel, dim3((((P.w + 3) / 4) * ((P.h + STRIP - 1) / STRIP) + 255) / 256, c.nframes), dim3(256), 0, s, c.images, c.pitch, c.imageStride, P.w, P.h,
+                       (unsigned*)(c.ws + P.offDxy), P.frameBytes, c.L->dTaps.as<int>() + 8);
+}
+
+// The prologue: blur(7, 0.75) -> 0.8x -> gradient, then the seeds in order.  The fused blur + gradient kernel where the plan admits it (lines_build_plan) and the tile-sorted
+// runs where a sorted entry's packing fits (scaled image up to 2048 x 2048); k_blur7 + k_lsd_grad and k_lsd_hist + k_lsd_scatter for every other geometry.
+static int lines_prologue(const LinesCall& c) {
+    sslam_lines* L = c.L; const LsdPlan& P = c.P; hipStream_t st = c.st;
+    const int* taps = L->dTaps.as<int>();
+    const int* tabX = L->dTabs.as<int>() + P.tabX; const int* tabY = L->dTabs.as<int>() + P.tabY;
+    const int mode = (P.lsdResize ? 1 : 0) | (L->seedOrder ? 2 : 0);      // the gradient kernels' template argument
+    const bool fused = L->fusedGeometry && GRAD_ROWS == 8 && ((uintptr_t)c.images & 3) == 0 && (c.pitch & 3) == 0 && (c.imageStride & 3) == 0 && c.pitch <= 0x7FFFFFFF;
+    if (fused) {
+        static decltype(&k_lsd_grad_fused<0>) const kGradFused[4] = {k_lsd_grad_fused<0>, k_lsd_grad_fused<1>, k_lsd_grad_fused<2>, k_lsd_grad_fused<3>};
+        sslam::ProfScope _ps(L->ctx, "k_lsd_grad", st);
+        const dim3 gg(P.nXB, (P.sh + 31) / 32, c.nframes);      // (frame-walking workgroups -- a grid of 1 024 / 2 048 -- were measured for this kernel too, call U: 171 / 175 ms per step against 158; the kernel keeps its frame loop, the grid covers the batch)
+        hipLaunchKernelGGL(kGradFused[mode], gg, dim3(64, 4), 0, st, c.images, c.pitch, c.imageStride, c.ws, P, L->dGtab.as<float4>(), tabX, tabY, taps, c.nframes);
+    } else {
+        static decltype(&k_lsd_grad<0>) const kGrad[4] = {k_lsd_grad<0>, k_lsd_grad<1>, k_lsd_grad<2>, k_lsd_grad<3>};
+        const size_t bpitch = ((size_t)P.w + 63) & ~(size_t)63;
+        { sslam::ProfScope _ps(L->ctx, "k_blur7", st); hipLaunchKernelGGL(k_blur7, dim3((((P.w + 3) / 4) * ((P.h + STRIP - 1) / STRIP) + 255) / 256, c.nframes), dim3(256), 0, st, c.images, c.pitch, c.imageStride,
+                           c.ws + P.offBlur, bpitch, P.frameBytes, P.w, P.h, taps); }
+        { sslam::ProfScope _ps(L->ctx, "k_lsd_grad", st);
+          const dim3 gg(P.nXB, (P.sh + 4 * GRAD_ROWS - 1) / (4 * GRAD_ROWS), c.nframes);
+          hipLaunchKernelGGL(kGrad[mode], gg, dim3(64, 4), 0, st, c.ws, P, L->dGtab.as<float4>(), bpitch, tabX, tabY); }
+    }
+    if (L->seedOrder) return lines_host_seed_order(L, c.ws, c.nframes, st);
+    const bool runs = P.sw <= (1 << SORT_XY_BITS) && P.sh <= (1 << SORT_XY_BITS);
+    const dim3 sg(sort_grid(P.nTiles, c.nframes));
+    { sslam::ProfScope _ps(L->ctx, "k_lsd_hist", st); hipLaunchKernelGGL(runs ? k_lsd_hist_sort : k_lsd_hist, sg, dim3(64), 0, st, c.ws, P, c.nframes); }
+    { sslam::ProfScope _ps(L->ctx, "k_lsd_scan", st); hipLaunchKernelGGL(k_lsd_scan, dim3(c.nframes), dim3(1024), 0, st, c.ws, P); }
+    { sslam::ProfScope _ps(L->ctx, "k_lsd_scatter", st); hipLaunchKernelGGL(runs ? k_lsd_scatter_runs : k_lsd_scatter, sg, dim3(64), 0, st, c.ws, P, c.nframes); }
+    return SSLAM_OK;
+}
+
+// The cluster form of the core.  streamNfa: the NFA stage runs NEXT TO the core on the side stream, on the rectangles the main wave has published so far (lsd_nfa.h,
+// k_nfa_stream) -- the default since round 5 (whole GPU suite with the knob exported, single frames 6.02 / 7.18 -> 5.76 / 6.89 ms p50 / p90, calls of 2 .. 64 frames
+// -8 .. -24 %: profiles/r05a_*).  *nfaStageOff: where the frames' rectangles for that stage lie in a cluster slot.
+static int lines_core_cluster(const LinesCall& c, const LinesKnobs& K, bool streamNfa, SideJoin& side, size_t* nfaStageOff) {
+    sslam_lines* L = c.L; const LsdPlan& P = c.P; const int nframes = c.nframes; hipStream_t st = c.st;
+    int rc;
+    const bool bigFrame = P.sw > TorusFrame::XMASK + 1 || P.sh > TorusFrame::YMASK + 1;      // the main wave's bitmap in global memory instead of LDS
+    const int window = K.clWindow, clShift = K.clSmap;
+    int nWG = K.clWgs;
+    const int clSpecWords = clShift < 0 ? 0 : (((P.sw + (1 << clShift) - 1) >> clShift) * ((P.sh + (1 << clShift) - 1) >> clShift) + 31) / 32;
+    const size_t maxSubs = ((size_t)P.npx + CL_SUB - 1) / CL_SUB;
+    const size_t zeroBytes = 512 + ((maxSubs * sizeof(ClSub) + 511) & ~(size_t)511) + 4 * (size_t)((clSpecWords + 127) & ~127) + (bigFrame ? 4 * (size_t)TorusGlobal::WORDS : 0);      // control block, sub-chunk states / flags, shared map (+ the main wave's bitmap)
+    if (nframes > 8) nWG = std::max(2, std::min(nWG, 32 / ((nframes + 7) / 8)));      // the frames of an XCD share its 32 compute units
+    // per frame: the zeroed head, two result records per seed position, one 256 KB list arena per HELPER THAT EXISTS ((nWG - 1) x CL_HPW: 27 by default;
+    // rounds 1-3 sized it for 64), and the rectangles of the streaming NFA stage.  One slot per frame of the call: blocks with b >= nframes return at once, so the
+    // XCD-aligned grid needs no padding slots (a single 640x480 frame held 8 slots of 30 MB before).
+    const size_t stageOff = zeroBytes + maxSubs * CL_RES * sizeof(ClRec) + 4 * (size_t)CL_ARENA * (size_t)std::max(1, (nWG - 1) * CL_HPW);      // (k_lsd_regions_cl<1>: cl.candStage)
+    const size_t clFrame = align_up(stageOff + (streamNfa ? sizeof(double) * 12 * (size_t)MAX_SEG : 0), 4096);
+    L->clFrame = clFrame; L->clSlots = nframes;
+    const size_t clSlots = (size_t)nframes;
+    if (L->dCl.cap < clFrame * clSlots) { SSLAM_HIP(hipStreamSynchronize(st)); if ((rc = L->dCl.ensure(clFrame * clSlots))) return rc; }
+    for (int f = 0; f < nframes; ++f) SSLAM_HIP(hipMemsetAsync(L->dCl.as<uint8_t>() + (size_t)f * clFrame, 0, zeroBytes, st));
+    const size_t clLds = sizeof(unsigned) * std::max((size_t)QCAP + 4 + (bigFrame ? 0 : TorusFrame::WORDS) + CL_SCAN + CL_RING_WORDS, (size_t)CL_HPW * (CL_LIST + ClTorus::WORDS));      // the main wave's workgroup / a helper workgroup
+    const auto kern = streamNfa ? k_lsd_regions_cl<1> : k_lsd_regions_cl<0>;
+    const dim3 grd(8 * nWG * ((nframes + 7) / 8));
+    SSLAM_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clLds));
+    if (!streamNfa) {
+        hipLaunchKernelGGL(kern, grd, dim3(64 * CL_WAVES), clLds, st, c.ws, P, L->dCl.as<uint8_t>(), clFrame, nframes, nWG, clSpecWords, clShift, window);
+        return SSLAM_OK;
+    }
+    if ((rc = lines_side_stream_ready(L))) return rc;
+    SSLAM_HIP(hipEventRecord(L->nfaFork, st));      // (the prologue's planes and the zeroed slot heads are what the consumers need)
+    hipLaunchKernelGGL(kern, grd, dim3(64 * CL_WAVES), clLds, st, c.ws, P, L->dCl.as<uint8_t>(), clFrame, nframes, nWG, clSpecWords, clShift, window);
+    SSLAM_HIP(hipStreamWaitEvent(L->nfaStream, L->nfaFork, 0));
+    side.forked = true;
+    // LBD's gradient image depends on the source alone: on the second stream it runs under the core instead of behind the NFA stage (28 us of a single frame's
+    // 5.4 ms; the join in the tail orders it before k_lbd.  Behind the NFA stage instead: 5.43 -> 5.38 ms p50, GPU call I)
+    lines_blur_sobel(c, L->nfaStream);
+    if ((rc = sslam::launch_nfa_stream(L->ctx, L->nfaStream, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), clFrame, stageOff, nframes, K.nfaStreamWaves, K.nfaSpinTicks, true))) return rc;
+    *nfaStageOff = stageOff;
+    return SSLAM_OK;
+}
+
+// The sequential core in the form lines_core_form chose, between the core gate / event of the caller
+static int lines_core(const LinesCall& c, const LinesKnobs& K, CoreForm form, int grid, SideJoin& side, size_t* nfaStageOff) {
+    sslam_lines* L = c.L; const LsdPlan& P = c.P; const int nframes = c.nframes; hipStream_t st = c.st;
+    static_assert(sizeof(unsigned) * (QCAP + 4) <= 48 * 1024, "k_lsd_regions: the region queue must fit the default dynamic LDS limit (SSLAM_LSD_QCAP)");
+    const size_t lds = sizeof(unsigned) * (QCAP + 4);      // + the sink slot behind the queue (region_grow_w)
+    if (L->coreWait) SSLAM_HIP(hipStreamWaitEvent(st, L->coreWait, 0));      // (sslam_lines_set_core_gate: another extractor's core has the wave slots until then)
+    if (L->coreEvent) SSLAM_HIP(hipEventRecord(L->coreEvent, st));
+    {
+        sslam::ProfScope _ps(L->ctx, "k_lsd_regions", st);
+        const double* lgam = L->dLgam.as<double>();
+        switch (form) {
+            case CoreForm::ClusterStream:
+            case CoreForm::Cluster: { const int rc = lines_core_cluster(c, K, form == CoreForm::ClusterStream, side, nfaStageOff); if (rc) return rc; break; }
+            case CoreForm::Lone: hipLaunchKernelGGL((k_lsd_regions<true, 4>), dim3(nframes), dim3(64), lds, st, c.ws, P, lgam, nframes); break;
+            case CoreForm::Guest: hipLaunchKernelGGL((k_lsd_regions<false, 4>), dim3(grid), dim3(64), lds, st, c.ws, P, lgam, nframes); break;
+            case CoreForm::PerFrame: hipLaunchKernelGGL((k_lsd_regions<false, 4>), dim3(nframes), dim3(64), lds, st, c.ws, P, lgam, nframes); break;
+            case CoreForm::SixWave: hipLaunchKernelGGL((k_lsd_regions<false, 6>), dim3(nframes), dim3(64), lds, st, c.ws, P, lgam, nframes); break;
+        }
+    }
+    if (L->coreDone) SSLAM_HIP(hipEventRecord(L->coreDone, st));
+    return SSLAM_OK;
+}
+
+// The tail: the NFA stage, the output lines, LBD's gradient image and the descriptors
+static int lines_tail(const LinesCall& c, CoreForm form, size_t nfaStageOff, SideJoin& side, sslam_keyline* d_kl, uint8_t* d_ldesc, double* d_linefn, int32_t* d_counts, int cap) {
+    sslam_lines* L = c.L; const LsdPlan& P = c.P; const int nframes = c.nframes; hipStream_t st = c.st;
+    int rc;
+    // LBD's gradient image needs the source alone and is bandwidth-bound; the NFA stage behind the core is latency-bound (a third of the vector pipes busy): on the side
+    // stream the one runs beside the other instead of behind it -- for a caller WITHOUT a branch of its own beside this one (no core event): 187.5 against 190.1 ms per
+    // one-stream step.  With the point branch still running there (two-stream step) the pair costs 3.5 ms instead (164.1 against 160.2: k_blur_sobel and k_nfa_all are 56 KB
+    // and 54 KB of code, together more than the 64 KB instruction cache two compute units share, beside a third kernel); profiles/r06f_*.  (LBD's blur + Sobel as one more
+    // guest under the core, on the side stream, was measured too: its 126-VGPR waves take the slots FAST needs -- 167.7 ms per step against 160.8 with the kernel in the
+    // tail; profiles/r06d_*.)  The side stream runs k_blur_sobel whenever it was forked: here, or under the streaming NFA stage (lines_core_cluster).
+    if (!side.forked && nframes >= 1024 && !L->coreEvent) {
+        if ((rc = lines_side_stream_ready(L))) return rc;
+        SSLAM_HIP(hipEventRecord(L->nfaFork, st));
+        SSLAM_HIP(hipStreamWaitEvent(L->nfaStream, L->nfaFork, 0));
+        side.forked = true;
+        lines_blur_sobel(c, L->nfaStream);
+    }
+    // the NFA stage: its kernels and launch forms live in lines_nfa.hip, a translation unit of its own (compiled with -mllvm -disable-machine-licm)
+    if (form == CoreForm::ClusterStream) {      // what the concurrent consumers left (nothing, unless they gave up waiting): the same kernel behind both, everything published, no waiting
+        side.join();
+        if ((rc = sslam::launch_nfa_stream(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), L->clFrame, nfaStageOff, nframes, 16, 0, false))) return rc;
+    } else if ((rc = sslam::launch_nfa_stage(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), nframes))) return rc;
+    { sslam::ProfScope _ps(L->ctx, "k_keylines", st); hipLaunchKernelGGL(k_keylines, dim3(nframes), dim3(256), 0, st, c.ws, P, L->maxLines, d_kl, d_linefn, d_counts, cap); }
+    if (!side.forked) lines_blur_sobel(c, st);
+    side.join();
+    {   // the walk's conversion form (lbd.h): images of up to 16 384 pixels a side; the previous form beyond
+        const bool rpi = P.w <= 16384 && P.h <= 16384;
+        sslam::ProfScope _ps(L->ctx, "k_lbd", st);
+        hipLaunchKernelGGL(rpi ? k_lbd<true> : k_lbd<false>, dim3(std::min(L->maxLines, cap), nframes), dim3(64), 0, st, c.ws, P, d_kl, d_counts, d_ldesc, cap);
+    }
+    return SSLAM_OK;
+}
+
 extern "C" int sslam_lines_extract_batch_dev(sslam_lines* L, const uint8_t* d_images, int w, int h, size_t pitch, size_t image_stride,
                                              int nframes, sslam_keyline* d_kl, uint8_t* d_ldesc, double* d_linefn, int32_t* d_counts,
                                              int cap, void* stream_) {
     if (!L || !d_images || !d_kl || !d_ldesc || !d_linefn || !d_counts || w <= 0 || h <= 0 || nframes <= 0 || cap <= 0 || pitch < (size_t)w) {
         set_error("sslam_lines_extract_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
+    const LinesKnobs K = lines_knobs();
     std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);      // plan, workspace and profile records are shared state
     SSLAM_HIP(hipSetDevice(L->ctx->device));
     hipStream_t st = stream_ ? (hipStream_t)stream_ : L->ctx->stream;
@@ -357,199 +570,15 @@ extern "C" int sslam_lines_extract_batch_dev(sslam_lines* L, const uint8_t* d_im
         if ((rc = L->dWs.ensure(P.frameBytes * (size_t)nframes))) return rc;
         L->wsFrames = nframes;
     }
-    uint8_t* ws = L->dWs.as<uint8_t>();
-    const size_t bpitch = ((size_t)w + 63) & ~(size_t)63;
-    const int* taps = L->dTaps.as<int>();
-    { sslam::ProfScope _ps(L->ctx, "k_zero_misc", st); hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, ws, P); }
-    // LBD's gradient image (sigma-1 blur + Sobel of the SOURCE) does not depend on the segments; SSLAM_LBD_SOBEL=early launches it here, in
-    // the prologue (8 ms with the chip to itself instead of 35 ms under the point branch) -- measured: the step does not respond to where a
-    // kernel runs, only to how long the kernels take alone (194.1 vs 191.4 ms; docs/history/DESIGN_rounds_1-4.md 5g), so it stays behind the NFA stage
-    static const bool sobelEarly = [] { const char* e = getenv("SSLAM_LBD_SOBEL"); return e && !strcmp(e, "early"); }();
-    bool sobelDone = false;
-    auto launch_blur_sobel = [&](hipStream_t s) {
-        sslam::ProfScope _ps(L->ctx, "k_blur_sobel", s);
-        hipLaunchKernelGGL(k_blur_sobel, dim3((((w + 3) / 4) * ((h + STRIP - 1) / STRIP) + 255) / 256, nframes), dim3(256), 0, s, d_images, pitch, image_stride, w, h,
-                           (unsigned*)(ws + P.offDxy), P.frameBytes, taps + 8);
-        sobelDone = true;
-    };
-    if (sobelEarly) launch_blur_sobel(st);
-    // Work forked onto the side stream (L->nfaStream) is joined into `st` on EVERY way out of this function -- also the early error returns: the caller may reuse or
-    // free the workspace as soon as `st` is idle, and the side stream's kernels write into it
-    struct SideJoin {
-        sslam_lines* L; hipStream_t st; bool forked = false, joined = false;
-        void join() { if (forked && !joined) { (void)hipEventRecord(L->nfaJoin, L->nfaStream); (void)hipStreamWaitEvent(st, L->nfaJoin, 0); joined = true; } }
-        ~SideJoin() { join(); }
-    } side{L, st};
-    auto side_stream_ready = [&]() -> int {
-        if (!L->nfaStream) {
-            SSLAM_HIP(hipStreamCreateWithFlags(&L->nfaStream, hipStreamNonBlocking));
-            SSLAM_HIP(hipEventCreateWithFlags(&L->nfaFork, hipEventDisableTiming));
-            SSLAM_HIP(hipEventCreateWithFlags(&L->nfaJoin, hipEventDisableTiming));
-        }
-        return SSLAM_OK;
-    };
-    // LSD: blur(7, 0.75) -> 0.8x -> gradient; one kernel where the geometry allows (SSLAM_LSD_FUSED=0: always two, A/B)
-    const bool fused = L->fusedGeometry && GRAD_ROWS == 8 && ((uintptr_t)d_images & 3) == 0 && (pitch & 3) == 0 && (image_stride & 3) == 0 && pitch <= 0x7FFFFFFF &&
-                       !(getenv("SSLAM_LSD_FUSED") && atoi(getenv("SSLAM_LSD_FUSED")) == 0);
-    if (fused) {
-      sslam::ProfScope _ps(L->ctx, "k_lsd_grad", st);
-      const dim3 gg(P.nXB, (P.sh + 31) / 32, nframes);      // (frame-walking workgroups -- a grid of 1 024 / 2 048 -- were measured for this kernel too, call U: 171 / 175 ms per step against 158; the kernel keeps its frame loop, the grid covers the batch)
-      const int* tabX = L->dTabs.as<int>() + P.tabX; const int* tabY = L->dTabs.as<int>() + P.tabY;
-      switch ((P.lsdResize ? 1 : 0) | (L->seedOrder ? 2 : 0)) {
-          case 0: hipLaunchKernelGGL(k_lsd_grad_fused<0>, gg, dim3(64, 4), 0, st, d_images, pitch, image_stride, ws, P, L->dGtab.as<float4>(), tabX, tabY, taps, nframes); break;
-          case 1: hipLaunchKernelGGL(k_lsd_grad_fused<1>, gg, dim3(64, 4), 0, st, d_images, pitch, image_stride, ws, P, L->dGtab.as<float4>(), tabX, tabY, taps, nframes); break;
-          case 2: hipLaunchKernelGGL(k_lsd_grad_fused<2>, gg, dim3(64, 4), 0, st, d_images, pitch, image_stride, ws, P, L->dGtab.as<float4>(), tabX, tabY, taps, nframes); break;
-          default: hipLaunchKernelGGL(k_lsd_grad_fused<3>, gg, dim3(64, 4), 0, st, d_images, pitch, image_stride, ws, P, L->dGtab.as<float4>(), tabX, tabY, taps, nframes); break;
-      }
-    } else {
-    { sslam::ProfScope _ps(L->ctx, "k_blur7", st); hipLaunchKernelGGL(k_blur7, dim3((((w + 3) / 4) * ((h + STRIP - 1) / STRIP) + 255) / 256, nframes), dim3(256), 0, st, d_images, pitch, image_stride,
-                       ws + P.offBlur, bpitch, P.frameBytes, w, h, taps); }
-    { sslam::ProfScope _ps(L->ctx, "k_lsd_grad", st);
-      const dim3 gg(P.nXB, (P.sh + 4 * GRAD_ROWS - 1) / (4 * GRAD_ROWS), nframes);
-      const int* tabX = L->dTabs.as<int>() + P.tabX; const int* tabY = L->dTabs.as<int>() + P.tabY;
-      switch ((P.lsdResize ? 1 : 0) | (L->seedOrder ? 2 : 0)) {
-          case 0: hipLaunchKernelGGL(k_lsd_grad<0>, gg, dim3(64, 4), 0, st, ws, P, L->dGtab.as<float4>(), bpitch, tabX, tabY); break;
-          case 1: hipLaunchKernelGGL(k_lsd_grad<1>, gg, dim3(64, 4), 0, st, ws, P, L->dGtab.as<float4>(), bpitch, tabX, tabY); break;
-          case 2: hipLaunchKernelGGL(k_lsd_grad<2>, gg, dim3(64, 4), 0, st, ws, P, L->dGtab.as<float4>(), bpitch, tabX, tabY); break;
-          default: hipLaunchKernelGGL(k_lsd_grad<3>, gg, dim3(64, 4), 0, st, ws, P, L->dGtab.as<float4>(), bpitch, tabX, tabY); break;
-      } }
-    }
-    if (L->seedOrder) { if ((rc = lines_host_seed_order(L, ws, nframes, st))) return rc; }
-    else {
-    // tile-sorted runs (lsd_front.h) where a sorted entry's packing fits (scaled image up to 2048 x 2048); SSLAM_LSD_SORT_RUNS=0: the round-1-5 kernels (A/B)
-    const bool runs = P.sw <= (1 << SORT_XY_BITS) && P.sh <= (1 << SORT_XY_BITS) && !(getenv("SSLAM_LSD_SORT_RUNS") && atoi(getenv("SSLAM_LSD_SORT_RUNS")) == 0);
-    if (runs) {
-    { sslam::ProfScope _ps(L->ctx, "k_lsd_hist", st); hipLaunchKernelGGL(k_lsd_hist_sort, dim3(sort_grid(P.nTiles, nframes)), dim3(64), 0, st, ws, P, nframes); }
-    { sslam::ProfScope _ps(L->ctx, "k_lsd_scan", st); hipLaunchKernelGGL(k_lsd_scan, dim3(nframes), dim3(1024), 0, st, ws, P); }
-    { sslam::ProfScope _ps(L->ctx, "k_lsd_scatter", st); hipLaunchKernelGGL(k_lsd_scatter_runs, dim3(sort_grid(P.nTiles, nframes)), dim3(64), 0, st, ws, P, nframes); }
-    } else {
-    { sslam::ProfScope _ps(L->ctx, "k_lsd_hist", st); hipLaunchKernelGGL(k_lsd_hist, dim3(sort_grid(P.nTiles, nframes)), dim3(64), 0, st, ws, P, nframes); }
-    { sslam::ProfScope _ps(L->ctx, "k_lsd_scan", st); hipLaunchKernelGGL(k_lsd_scan, dim3(nframes), dim3(1024), 0, st, ws, P); }
-    { sslam::ProfScope _ps(L->ctx, "k_lsd_scatter", st); hipLaunchKernelGGL(k_lsd_scatter, dim3(sort_grid(P.nTiles, nframes)), dim3(64), 0, st, ws, P, nframes); }
-    }
-    }
-    bool nfaStreamed = false; size_t nfaStageOff = 0;
-    {
-        size_t lds = sizeof(unsigned) * (QCAP + 4);      // + the sink slot behind the queue (region_grow_w)
-        if (const char* e = getenv("SSLAM_LSD_LDS_PAD")) lds = std::max(lds, (size_t)atoi(e));      // experiment knob: cap resident region workgroups per CU
-        if (lds > 48 * 1024) {
-            SSLAM_HIP(hipFuncSetAttribute((const void*)k_lsd_regions<true, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            SSLAM_HIP(hipFuncSetAttribute((const void*)k_lsd_regions<false, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            SSLAM_HIP(hipFuncSetAttribute((const void*)k_lsd_regions<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            SSLAM_HIP(hipFuncSetAttribute((const void*)k_lsd_regions<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        if (L->coreWait) SSLAM_HIP(hipStreamWaitEvent(st, L->coreWait, 0));      // (sslam_lines_set_core_gate: another extractor's core has the wave slots until then)
-        if (L->coreEvent) SSLAM_HIP(hipEventRecord(L->coreEvent, st));
-        sslam::ProfScope _ps(L->ctx, "k_lsd_regions", st);
-        bool lone = nframes < 1024;
-        const bool spillFree = !(getenv("SSLAM_LSD_SPILLFREE") && atoi(getenv("SSLAM_LSD_SPILLFREE")) == 0);
-        if (const char* e = getenv("SSLAM_LSD_FLAVOUR")) lone = e[0] == 'l' || e[0] == 'c';      // experiment knob: "cl" / "lat" / "thr"
-        // Up to 64 frames (one to eight per XCD) whose frame-wide bitmap fits the main wave's LDS: the cluster form -- helper waves on several compute
-        // units, results through global memory, monotonic pixel map (lsd_cluster.h).  SSLAM_LSD_CLUSTER=0 (or SSLAM_LSD_FLAVOUR=lat) takes lone
-        // waves instead; SSLAM_CL_WGS = workgroups per frame (4 waves each), SSLAM_CL_WINDOW = how many sub-chunks of 16 seed positions the
-        // helpers may run ahead, SSLAM_CL_SMAP = cell size (log2) of the shared map that steers their seed choice (-1: none).
-        int CL_MAXFRAMES = 64;      // up to eight frames per XCD, four workgroups each.  Per call, cluster form against the multi-wave form of rounds 2-4 (tools/small_batch_probe.py, round 3):
-                                    // 1 frame 5.9 / 7.9 ms, 8: 8.5 / 11.2, 16: 9.0 / 11.9, 24: 9.4 / 12.6, 32: 10.3 / 13.1, 64: 13.5 / 15.7, 96: 21.6 / 15.9
-        if (const char* e = getenv("SSLAM_CL_MAXFRAMES")) CL_MAXFRAMES = std::max(1, std::min(128, atoi(e)));      // experiment knob
-        const bool bigFrame = P.sw > TorusFrame::XMASK + 1 || P.sh > TorusFrame::YMASK + 1;      // the main wave's bitmap in global memory instead of LDS
-        bool cluster = nframes <= CL_MAXFRAMES && P.sw <= TorusGlobal::XMASK + 1 && P.sh <= TorusGlobal::YMASK + 1;
-        if (const char* e = getenv("SSLAM_LSD_FLAVOUR")) cluster = cluster && e[0] == 'c';      // "cl" / "lat" / "thr"
-        if (const char* e = getenv("SSLAM_LSD_CLUSTER")) cluster = cluster && atoi(e) != 0;
-        if (cluster) {
-            int nWG = 10, window = 0, clShift = 0;
-            if (const char* e = getenv("SSLAM_CL_WGS")) nWG = std::max(1, std::min(CL_MAXWG, atoi(e)));
-            if (const char* e = getenv("SSLAM_CL_WINDOW")) window = std::max(-1, atoi(e)); else window = 640 / CL_SUB;      // in sub-chunks (640 seed positions); -1: no helpers at all (the main wave alone)
-            if (const char* e = getenv("SSLAM_CL_SMAP")) clShift = atoi(e);
-            if (getenv("SSLAM_CL_NO_FEEDER") && window >= 0) window |= 1 << 20;      // experiment knob: the main wave fetches everything itself
-            const int clSpecWords = clShift < 0 ? 0 : (((P.sw + (1 << clShift) - 1) >> clShift) * ((P.sh + (1 << clShift) - 1) >> clShift) + 31) / 32;
-            const size_t maxSubs = ((size_t)P.npx + CL_SUB - 1) / CL_SUB;
-            const size_t zeroBytes = 512 + ((maxSubs * sizeof(ClSub) + 511) & ~(size_t)511) + 4 * (size_t)((clSpecWords + 127) & ~127) + (bigFrame ? 4 * (size_t)TorusGlobal::WORDS : 0);      // control block, sub-chunk states / flags, shared map (+ the main wave's bitmap)
-            if (nframes > 8) nWG = std::max(2, std::min(nWG, 32 / ((nframes + 7) / 8)));      // the frames of an XCD share its 32 compute units
-            // per frame: the zeroed head, two result records per seed position, one 256 KB list arena per HELPER THAT EXISTS ((nWG - 1) x CL_HPW: 27 by default;
-            // rounds 1-3 sized it for 64).  One slot per frame of the call: blocks with b >= nframes return at once, so the XCD-aligned grid needs no padding slots
-            // (a single 640x480 frame held 8 slots of 30 MB before).
-            // The NFA stage runs NEXT TO the core on a second stream, on the rectangles the main wave has published so far (lsd_nfa.h, k_nfa_stream) -- the default since round 5
-            // (whole GPU suite with the knob exported, single frames 6.02 / 7.18 -> 5.76 / 6.89 ms p50 / p90, calls of 2 .. 64 frames -8 .. -24 %: profiles/r05a_*).
-            // SSLAM_NFA_STREAM=0: the stage behind the core as one launch (the round-4 default); =n > 1: n consumer waves per frame (default 16)
-            int nfaStreamWaves = 16;
-            if (const char* e = getenv("SSLAM_NFA_STREAM")) { nfaStreamWaves = atoi(e); if (nfaStreamWaves == 1) nfaStreamWaves = 16; nfaStreamWaves = std::max(0, std::min(64, nfaStreamWaves)); }
-            const size_t stageOff = zeroBytes + maxSubs * CL_RES * sizeof(ClRec) + 4 * (size_t)CL_ARENA * (size_t)std::max(1, (nWG - 1) * CL_HPW);      // (k_lsd_regions_cl_stream: cl.candStage)
-            const size_t clFrame = align_up(stageOff + (nfaStreamWaves ? sizeof(double) * 12 * (size_t)MAX_SEG : 0), 4096);
-            L->clFrame = clFrame; L->clSlots = nframes;
-            const size_t clSlots = (size_t)nframes;
-            if (L->dCl.cap < clFrame * clSlots) { SSLAM_HIP(hipStreamSynchronize(st)); if ((rc = L->dCl.ensure(clFrame * clSlots))) return rc; }
-            for (int f = 0; f < nframes; ++f) SSLAM_HIP(hipMemsetAsync(L->dCl.as<uint8_t>() + (size_t)f * clFrame, 0, zeroBytes, st));
-            const size_t clLds = sizeof(unsigned) * std::max((size_t)QCAP + 4 + (bigFrame ? 0 : TorusFrame::WORDS) + CL_SCAN + CL_RING_WORDS, (size_t)CL_HPW * (CL_LIST + ClTorus::WORDS));      // the main wave's workgroup / a helper workgroup
-            SSLAM_HIP(hipFuncSetAttribute((const void*)k_lsd_regions_cl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clLds));
-            if (nfaStreamWaves) {
-                if ((rc = side_stream_ready())) return rc;
-                long long spinTicks = 5000000;       // 50 ms of the 100 MHz clock (ten single-frame cores): a consumer wave that has seen no progress for that long leaves its blocks to the launch behind the core
-                                                      // (0.2 s in round 5: on a GPU shared with another process the consumers can be resident before the producer, and the wait was the spike)
-                if (const char* e = getenv("SSLAM_NFA_STREAM_TICKS")) spinTicks = std::max(0ll, atoll(e));
-                size_t nfaLdsPad = 40 * 1024;        // (lines_nfa.hip: keeps the consumers off the main wave's and the helpers' compute units)
-                int nfaTakeMax = NFA_STREAM_BLOCK;   // rectangles per claim at most (lsd_nfa.h)
-                if (const char* e = getenv("SSLAM_NFA_STREAM_TAKE")) nfaTakeMax = atoi(e);
-                int nfaSleep = 1;                     // s_sleep(127) between two polls of a waiting consumer (lsd_nfa.h)
-                if (const char* e = getenv("SSLAM_NFA_STREAM_SLEEP")) nfaSleep = std::max(0, std::min(64, atoi(e)));
-                if (const char* e = getenv("SSLAM_NFA_STREAM_LDS")) nfaLdsPad = (size_t)std::max(0, std::min(48 * 1024, atoi(e)));
-                SSLAM_HIP(hipEventRecord(L->nfaFork, st));      // (the prologue's planes and the zeroed slot heads are what the consumers need)
-                SSLAM_HIP(hipFuncSetAttribute((const void*)k_lsd_regions_cl_stream, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clLds));
-                hipLaunchKernelGGL(k_lsd_regions_cl_stream, dim3(8 * nWG * ((nframes + 7) / 8)), dim3(64 * CL_WAVES), clLds, st, ws, P, L->dCl.as<uint8_t>(), clFrame, nframes, nWG, clSpecWords, clShift, window);
-                SSLAM_HIP(hipStreamWaitEvent(L->nfaStream, L->nfaFork, 0));
-                side.forked = true;
-                // LBD's gradient image depends on the source alone: on the second stream it runs under the core instead of behind the NFA stage (28 us of a single frame's
-                // 5.4 ms; the join below orders it before k_lbd)
-                if (!sobelDone && !getenv("SSLAM_LBD_SOBEL_MAIN")) launch_blur_sobel(L->nfaStream);      // (the knob: A/B, GPU call I -- 5.43 -> 5.38 ms p50)
-                if ((rc = sslam::launch_nfa_stream(L->ctx, L->nfaStream, ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), clFrame, stageOff, nframes, nfaStreamWaves, spinTicks, nfaLdsPad, nfaTakeMax, nfaSleep, nullptr))) return rc;
-                nfaStreamed = true; nfaStageOff = stageOff;
-            } else
-            hipLaunchKernelGGL(k_lsd_regions_cl, dim3(8 * nWG * ((nframes + 7) / 8)), dim3(64 * CL_WAVES), clLds, st, ws, P, L->dCl.as<uint8_t>(), clFrame, nframes, nWG, clSpecWords, clShift, window);
-        } else if (lone) {      // lone waves: shortest chain.  At most one wave per SIMD is resident, so the instantiation that spills nothing costs no occupancy (SSLAM_LSD_SPILLFREE=0: the six-wave one, A/B)
-            if (spillFree) hipLaunchKernelGGL((k_lsd_regions<true, 4>), dim3(nframes), dim3(64), lds, st, ws, P, L->dLgam.as<double>(), nframes);
-            else hipLaunchKernelGGL((k_lsd_regions<true, 6>), dim3(nframes), dim3(64), lds, st, ws, P, L->dLgam.as<double>(), nframes);
-        } else {
-            // A caller that announced a branch running beside the core (sslam_lines_set_core_event: the bench step's point branch waits for that event) gets the GUEST form
-            // (lsd_regions.h): 16 - 18 persistent workgroups per compute unit of the four-wave instantiation, a third of the registers free for the other branch's waves.
-            // SSLAM_LSD_GUEST=0 / 1 overrides (A/B), SSLAM_LSD_PERSIST=g sets the grid.  (LBD's blur + Sobel as one more guest under the core, on the side stream, was
-            // measured too: its 126-VGPR waves take the slots FAST needs -- 167.7 ms per step against 160.8 with the kernel in the tail; profiles/r06d_*.)
-            int grid = 0;
-            if (lines_guest_form(L, nframes, &grid)) hipLaunchKernelGGL((k_lsd_regions<false, 4>), dim3(grid), dim3(64), lds, st, ws, P, L->dLgam.as<double>(), nframes);
-            else if (spillFree && nframes <= 16 * L->ctx->num_cus)      // up to four waves per SIMD anyway (BASELINE configs[3]: 3 072 frames): the spill-free instantiation, one workgroup per frame
-                hipLaunchKernelGGL((k_lsd_regions<false, 4>), dim3(nframes), dim3(64), lds, st, ws, P, L->dLgam.as<double>(), nframes);
-            else hipLaunchKernelGGL((k_lsd_regions<false, 6>), dim3(nframes), dim3(64), lds, st, ws, P, L->dLgam.as<double>(), nframes);
-        }
-    }
-    if (L->coreDone) SSLAM_HIP(hipEventRecord(L->coreDone, st));
-    // LBD's gradient image needs the source alone and is bandwidth-bound; the NFA stage behind the core is latency-bound (a third of the vector pipes busy): on the side
-    // stream the one runs beside the other instead of behind it -- for a caller WITHOUT a branch of its own beside this one (no core event): 187.5 against 190.1 ms per
-    // one-stream step.  With the point branch still running there (two-stream step) the pair costs 3.5 ms instead (164.1 against 160.2: k_blur_sobel and k_nfa_all are 56 KB
-    // and 54 KB of code, together more than the 64 KB instruction cache two compute units share, beside a third kernel); profiles/r06f_*.  SSLAM_LBD_SOBEL_MAIN=1: always behind.
-    if (!sobelDone && !side.forked && nframes >= 1024 && !L->coreEvent && !getenv("SSLAM_LBD_SOBEL_MAIN")) {
-        if ((rc = side_stream_ready())) return rc;
-        SSLAM_HIP(hipEventRecord(L->nfaFork, st));
-        SSLAM_HIP(hipStreamWaitEvent(L->nfaStream, L->nfaFork, 0));
-        side.forked = true;
-        launch_blur_sobel(L->nfaStream);
-    }
-    // the NFA stage: its kernels and launch forms live in lines_nfa.hip, a translation unit of its own (compiled with -mllvm -disable-machine-licm)
-    if (nfaStreamed) {      // what the concurrent consumers left (nothing, unless they gave up waiting): the same kernel behind both, everything published, no waiting
-        side.join();
-        const int rc2 = sslam::launch_nfa_stream(L->ctx, st, ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), L->clFrame, nfaStageOff, nframes, 16, 0, 0, NFA_STREAM_BLOCK, 1, "k_nfa_stream");
-        if (rc2) return rc2;
-    } else
-    { const int rc = sslam::launch_nfa_stage(L->ctx, st, ws, &P, sizeof(P), L->dLgam.as<double>(), nframes); if (rc) return rc; }
-    { sslam::ProfScope _ps(L->ctx, "k_keylines", st); hipLaunchKernelGGL(k_keylines, dim3(nframes), dim3(256), 0, st, ws, P, L->maxLines, d_kl, d_linefn, d_counts, cap); }
-    // LBD: blur(5, 1) + Sobel fused (SSLAM_LBD_SOBEL=early: in the prologue) -> bands
-    if (!sobelDone) launch_blur_sobel(st);
-    side.join();
-    {   // the walk's conversion form (lbd.h): images of up to 16 384 pixels a side; SSLAM_LBD_RPI=0 forces the previous form (A/B, tests)
-        const bool rpiOff = getenv("SSLAM_LBD_RPI") && atoi(getenv("SSLAM_LBD_RPI")) == 0;
-        const bool rpi = !rpiOff && P.w <= 16384 && P.h <= 16384;
-        sslam::ProfScope _ps(L->ctx, "k_lbd", st);
-        const dim3 grd(std::min(L->maxLines, cap), nframes);
-        if (rpi) hipLaunchKernelGGL(k_lbd<true>, grd, dim3(64), 0, st, ws, P, d_kl, d_counts, d_ldesc, cap);
-        else hipLaunchKernelGGL(k_lbd<false>, grd, dim3(64), 0, st, ws, P, d_kl, d_counts, d_ldesc, cap);
-    }
+    const LinesCall c{L, P, d_images, pitch, image_stride, nframes, st, L->dWs.as<uint8_t>()};
+    { sslam::ProfScope _ps(L->ctx, "k_zero_misc", st); hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c.ws, P); }
+    SideJoin side{L, st};
+    if ((rc = lines_prologue(c))) return rc;
+    int grid = 0;
+    const CoreForm form = lines_core_form(L, P, nframes, K, &grid);
+    size_t nfaStageOff = 0;
+    if ((rc = lines_core(c, K, form, grid, side, &nfaStageOff))) return rc;
+    if ((rc = lines_tail(c, form, nfaStageOff, side, d_kl, d_ldesc, d_linefn, d_counts, cap))) return rc;
     SSLAM_HIP(hipGetLastError());
     L->lastFrames = nframes;
     return SSLAM_OK;

@@ -696,6 +696,9 @@ __device__ void cl_helper(int h, uint8_t* __restrict__ ws, const LsdPlan& P, int
 
 // One frame = nWG workgroups of one XCD (blockIdx % 8 == frame % 8; role = (blockIdx / 8) % nWG; up to eight frames per XCD); dynamic LDS: per wave a list buffer of CL_LIST words and a
 // 256 x 256-bit torus, in front of them (role 0 only) the main wave's region queue and its frame-wide bitmap.
+// STREAM = 1: the main wave also streams its rectangles to a concurrent NFA stage (the default since round 5: cl_main<G, 1>, lsd_nfa.h: k_nfa_stream).  A template
+// kernel, not a shared inline body: each instantiation is compiled on its own and keeps the register assignment of the two copies it replaced.
+template <int STREAM>
 __global__ __launch_bounds__(64 * CL_WAVES) void k_lsd_regions_cl(uint8_t* __restrict__ ws, LsdPlan P, uint8_t* __restrict__ clArea, size_t clFrameBytes, int nframes, int nWG,
                                                                  int specWords, int specShift, int window) {
     extern __shared__ __align__(16) unsigned dynLds[];
@@ -703,7 +706,7 @@ __global__ __launch_bounds__(64 * CL_WAVES) void k_lsd_regions_cl(uint8_t* __res
     __shared__ float4 stashes[CL_WAVES][64];
     // blocks with the same (blockIdx % 8) share an XCD; an XCD hosts frames xcd, xcd + 8, xcd + 16, ... (nWG workgroups each)
     const int j = blockIdx.x >> 3, b = (blockIdx.x & 7) + 8 * (j / nWG), role = j % nWG, wave = threadIdx.x >> 6;
-    const bool nofeed = (window & (1 << 20)) != 0;      // (experiment knob: no feeder wave)
+    const bool nofeed = (window & (1 << 20)) != 0;      // (SSLAM_CL_NO_FEEDER: no feeder wave)
     if (window >= 0) window &= (1 << 20) - 1;
     if (b >= nframes) return;
     uint8_t* area = clArea + (size_t)b * clFrameBytes;
@@ -733,60 +736,11 @@ __global__ __launch_bounds__(64 * CL_WAVES) void k_lsd_regions_cl(uint8_t* __res
         ClSlot* ring = (ClSlot*)(dynLds + QCAP + 4 + bmWords + CL_SCAN);
         ClLocal* loc = (ClLocal*)(ring + CL_RING);
         if (wave == 0) {
-            if (bigFrame) cl_main<TorusGlobal, 0>(ws, P, b, dynLds, cl.bigBm, dynLds + QCAP + 4, red[0], stashes[0], cl, ring, loc);
-            else cl_main<TorusFrame, 0>(ws, P, b, dynLds, dynLds + QCAP + 4, dynLds + QCAP + 4 + TorusFrame::WORDS, red[0], stashes[0], cl, ring, loc);
+            if (bigFrame) cl_main<TorusGlobal, STREAM>(ws, P, b, dynLds, cl.bigBm, dynLds + QCAP + 4, red[0], stashes[0], cl, ring, loc);
+            else cl_main<TorusFrame, STREAM>(ws, P, b, dynLds, dynLds + QCAP + 4, dynLds + QCAP + 4 + TorusFrame::WORDS, red[0], stashes[0], cl, ring, loc);
         }
         else if (wave == 1 && !nofeed) cl_feeder(ws, P, b, cl, ring, loc);
         return;
     }
     else if (wave < CL_HPW) cl_helper((role - 1) * CL_HPW + wave, ws, P, b, cl, mine, mine + CL_LIST, stashes[wave], red[wave]);
 }
-
-// The same with the rectangles streamed to a concurrent NFA stage (the default since round 5: cl_main<G, true>, lsd_nfa.h: k_nfa_stream).  A copy of the kernel above rather
-// than a shared body: wrapped into a common inline function the default kernel came out with other register assignments, and the default kernel is the measured one.
-__global__ __launch_bounds__(64 * CL_WAVES) void k_lsd_regions_cl_stream(uint8_t* __restrict__ ws, LsdPlan P, uint8_t* __restrict__ clArea, size_t clFrameBytes, int nframes, int nWG,
-                                                                        int specWords, int specShift, int window) {
-    extern __shared__ __align__(16) unsigned dynLds[];
-    __shared__ double red[CL_WAVES][3 * 64];
-    __shared__ float4 stashes[CL_WAVES][64];
-    // blocks with the same (blockIdx % 8) share an XCD; an XCD hosts frames xcd, xcd + 8, xcd + 16, ... (nWG workgroups each)
-    const int j = blockIdx.x >> 3, b = (blockIdx.x & 7) + 8 * (j / nWG), role = j % nWG, wave = threadIdx.x >> 6;
-    const bool nofeed = (window & (1 << 20)) != 0;      // (experiment knob: no feeder wave)
-    if (window >= 0) window &= (1 << 20) - 1;
-    if (b >= nframes) return;
-    uint8_t* area = clArea + (size_t)b * clFrameBytes;
-    ClShared cl;
-    cl.ctl = (ClCtl*)area;
-    const size_t maxSubs = ((size_t)P.npx + CL_SUB - 1) / CL_SUB;
-    cl.sub = (ClSub*)(area + 512);
-    cl.specMap = (unsigned*)(area + 512 + ((maxSubs * sizeof(ClSub) + 511) & ~(size_t)511));
-    cl.bigBm = cl.specMap + ((specWords + 127) & ~127);      // (zeroed with the shared map when the frame is too large for the LDS bitmap; empty otherwise)
-    cl.rec = (ClRec*)(cl.bigBm + ((P.sw > TorusFrame::XMASK + 1 || P.sh > TorusFrame::YMASK + 1) ? TorusGlobal::WORDS : 0));
-    cl.arena = (unsigned*)(cl.rec + maxSubs * CL_RES);
-    cl.specShift = specShift; cl.specW = specShift >= 0 ? (P.sw + (1 << specShift) - 1) >> specShift : 0;
-    cl.nHelpers = (nWG - 1) * CL_HPW; cl.window = window;
-    unsigned* mine = dynLds + (size_t)wave * (CL_LIST + ClTorus::WORDS);      // (helper workgroups)
-    if (role != 0 && wave < CL_HPW) for (int i = threadIdx.x & 63; i < ClTorus::WORDS; i += 64) mine[CL_LIST + i] = 0u;
-    const bool bigFrame = P.sw > TorusFrame::XMASK + 1 || P.sh > TorusFrame::YMASK + 1;      // the main wave's bitmap lives in global memory (zeroed by the host)
-    const int bmWords = bigFrame ? 0 : TorusFrame::WORDS;
-    if (role == 0) {
-        for (int i = threadIdx.x; i < bmWords; i += blockDim.x) dynLds[QCAP + 4 + i] = 0u;
-        ClSlot* ring = (ClSlot*)(dynLds + QCAP + 4 + bmWords + CL_SCAN);
-        if (threadIdx.x < CL_RING) { ring[threadIdx.x].chunk = -1; ring[threadIdx.x].ready = 0; }
-        if (threadIdx.x == 0) { ClLocal* loc = (ClLocal*)(ring + CL_RING); loc->mainChunk = 0; loc->commitSeq = 0; loc->finished = 0; }
-    }
-    __syncthreads();
-    if (role == 0) {
-        // the main wave's workgroup: main wave + feeder.  No helpers here: their L1 invalidations cost the main wave 4 % (7.21 -> 6.89 ms)
-        ClSlot* ring = (ClSlot*)(dynLds + QCAP + 4 + bmWords + CL_SCAN);
-        ClLocal* loc = (ClLocal*)(ring + CL_RING);
-        if (wave == 0) {
-            if (bigFrame) cl_main<TorusGlobal, 1>(ws, P, b, dynLds, cl.bigBm, dynLds + QCAP + 4, red[0], stashes[0], cl, ring, loc);
-            else cl_main<TorusFrame, 1>(ws, P, b, dynLds, dynLds + QCAP + 4, dynLds + QCAP + 4 + TorusFrame::WORDS, red[0], stashes[0], cl, ring, loc);
-        }
-        else if (wave == 1 && !nofeed) cl_feeder(ws, P, b, cl, ring, loc);
-        return;
-    }
-    else if (wave < CL_HPW) cl_helper((role - 1) * CL_HPW + wave, ws, P, b, cl, mine, mine + CL_LIST, stashes[wave], red[wave]);
-}
-

@@ -120,7 +120,7 @@ extern "C" int sslam_orb_search_for_initialization_batch_dev(sslam_ctx* ctx,
     // a handful of pairs (the single call of Tracking::MonocularInitialization): the LDS-resident kernel, as long as a pair fits the CU's LDS
     const size_t ldsNeed = 64 + (size_t)cap * 15 * 4 + (size_t)cap * 2 * 4;      // per candidate 15 words (14 + the stamp of the speculative form), per F1 keypoint 2
     const char* sfiForm = getenv("SSLAM_SFI_FORM");      // test / experiment knob: "global", "lds" (one wave), default: sixteen speculative waves
-    if (npairs <= 8 && ldsNeed <= 150 * 1024 && !getenv("SSLAM_SFI_GLOBAL") && !(sfiForm && sfiForm[0] == 'g')) {
+    if (npairs <= 8 && ldsNeed <= 150 * 1024 && !(sfiForm && sfiForm[0] == 'g')) {
         const bool oneWave = sfiForm && sfiForm[0] == 'l';
         if (ldsNeed > 48 * 1024) SSLAM_HIP(hipFuncSetAttribute(oneWave ? (const void*)k_search_init_lds : (const void*)k_search_init_spec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsNeed));
         sslam::ProfScope _ps(ctx, "k_search_init", pick(ctx, stream));

@@ -1215,11 +1215,11 @@ extern "C" int sslam_orb_extract_batch_dev(sslam_orb* o, const uint8_t* d_images
     if ((rc = ensure_workspace(o, nframes))) return rc;
     Plan P = o->plan;
     uint8_t* pyr = o->dPyr.as<uint8_t>();
-    // level 0 in place when the caller's layout allows aligned dword loads (see Plan::img0); SSLAM_ORB_COPY_LEVEL0=1 forces the copy (A/B knob)
+    // level 0 in place when the caller's layout allows aligned dword loads (see Plan::img0)
     // The aligned dword reads of the kernels may touch the padding bytes [w, pitch) of a row: with padded rows the frames must therefore be whole pitch x h blocks
     // (image_stride >= pitch * h; include/sslam_frontend.h states it, and that the LAST frame's buffer must hold pitch * h bytes) -- a layout that does not say so is copied.
     const bool inPlace = ((uintptr_t)d_images & 3) == 0 && (pitch & 3) == 0 && (image_stride & 3) == 0 && pitch <= 0x7FFFFFFF &&
-                         (pitch == (size_t)w || image_stride >= pitch * (size_t)h) && !getenv("SSLAM_ORB_COPY_LEVEL0");
+                         (pitch == (size_t)w || image_stride >= pitch * (size_t)h);
     P.img0 = inPlace ? d_images : nullptr; P.img0Stride = image_stride; P.img0Pitch = (int)pitch;
     o->lastImg0 = d_images; o->lastImg0Pitch = pitch; o->lastImg0Stride = image_stride; o->lastInPlace = inPlace;
     if (!inPlace) {
@@ -1231,10 +1231,8 @@ extern "C" int sslam_orb_extract_batch_dev(sslam_orb* o, const uint8_t* d_images
         // Workgroups WALK THE FRAMES (round 6): everything a thread derives from its four output columns and its row -- three table entries, the source window, the byte
         // selectors and coefficient pairs -- is the same for every frame of the batch, so a grid of ~32 workgroups per compute unit whose workgroups step through the frames
         // computes it once: 9.0 -> 6.0 ms for the seven launches alone (10.2 -> 6.0 in the harness of call V), the two-stream step 158.3 -> 153.7 ms.
-        // SSLAM_RESIZE_GRID_WGS=n: about n workgroups per launch (0: one per frame and tile, the form of rounds 1-5).
-        int wantWgs = 32 * o->ctx->num_cus;
-        if (const char* e = getenv("SSLAM_RESIZE_GRID_WGS")) wantWgs = atoi(e);
-        const int gy = wantWgs > 0 ? std::max(1, std::min(nframes, wantWgs / (int)std::max(gx, 1u))) : nframes;
+        const int wantWgs = 32 * o->ctx->num_cus;
+        const int gy = std::max(1, std::min(nframes, wantWgs / (int)std::max(gx, 1u)));
         dim3 blk(256), grd(gx, gy);
         const bool fromImage = l == 1 && inPlace;
         { sslam::ProfScope _ps(o->ctx, "k_resize", st);

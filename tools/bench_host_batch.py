@@ -1,12 +1,11 @@
 """PCIe-inclusive batch rate: frames in HOST memory through sslam_frontend_batch (H2D + ORB + LSD/LBD + D2H, chunks overlapped, two branch
-streams), results back in host arrays that exist before the timed call.  usage: python tools/bench_host_batch.py [n] [chunk] [one-stream 0/1]"""
+streams), results back in host arrays that exist before the timed call.  usage: python tools/bench_host_batch.py [n] [chunk]"""
 import sys, os, time; sys.path.insert(0, 'tests')
 import numpy as np, torch, pkg
 torch.cuda.init()          # before the library's own context: torch's lazy initialisation fails after it on this stack
 from synth import synth_frame
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 18432
 chunk = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-if len(sys.argv) > 3 and sys.argv[3] == "1": os.environ["SSLAM_BATCH_ONE_STREAM"] = "1"
 fe = pkg.frontend(); ctx = fe.Context(0)
 orb = fe.OrbExtractor(ctx, 1000); lines = fe.LineExtractor(ctx, 200)
 if os.environ.get("HOST_BATCH_BENCH_FRAMES"):      # the bench's own sequence: 64 scenes of varied density, previous / current frame alternating (bench.py pcie_leg)

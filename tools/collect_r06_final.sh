@@ -11,5 +11,5 @@ cp $O/pmc_fetch_c3.txt $P/r06_final_pmc_fetch_c3_B12288.txt; cp $O/pmc_write_c3.
 cp $O/pmc_fetch_c4.txt $P/r06_final_pmc_fetch_c4_1280x960_B1024.txt; cp $O/pmc_write_c4.txt $P/r06_final_pmc_write_c4_1280x960_B1024.txt
 cp $O/sq1.txt $P/r06_final_pmc_sq_pass1.txt; cp $O/sq2.txt $P/r06_final_pmc_sq_pass2.txt; cp $O/sq3.txt $P/r06_final_pmc_sq_pass3_lanes.txt
 cp $O/pmc_sq_table.txt $P/r06_final_pmc_sq_table.txt; cp $O/tcp_table.txt $P/r06_final_tcp_table.txt
-for f in kernel_trace_one_stream kernel_trace_two_streams kernel_trace_single_frame timeline_two_streams step_one_stream step_two_streams step_two_streams_round5_schedule lat_check lat_check_1280 pytest_gpu fuzz_parity fuzz_matchers; do cp $O/$f.txt $P/r06_final_$f.txt; done
+for f in kernel_trace_one_stream kernel_trace_two_streams kernel_trace_single_frame timeline_two_streams step_one_stream step_two_streams lat_check lat_check_1280 pytest_gpu fuzz_parity fuzz_matchers; do cp $O/$f.txt $P/r06_final_$f.txt; done
 ls -la $P/r06_final_bench_B12288_two_streams.json $P/sq_instr.json

@@ -2,7 +2,7 @@
  * parity with the CPU oracle's precomputed answers.
  *     python tools/lat_check_prepare.py            (CPU: the bench's 64 frames -> tools/lat_frames.raw, the oracle's lines for them -> tools/lat_expected.bin)
  *     gcc -O2 -Iinclude tools/lat_check.c -Lstructure-slam-pointline_amd/lib -lsslam_frontend -Wl,-rpath,'$ORIGIN/../structure-slam-pointline_amd/lib' -o tools/lat_check
- *     tools/lat_check <reps> "" "SSLAM_NFA_STREAM=1" "SSLAM_NFA_STREAM=32,SSLAM_NFA_STREAM_LDS=0" ...
+ *     tools/lat_check <reps> "" "SSLAM_NFA_STREAM=0" "SSLAM_NFA_STREAM=32,SSLAM_NFA_STREAM_TICKS=0" ...
  * Each argument after <reps> is one setting: comma-separated NAME=VALUE pairs set for that run and unset afterwards ("" = the default path). */
 #include <stdio.h>
 #include <stdlib.h>

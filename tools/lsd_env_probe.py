@@ -1,5 +1,5 @@
 """Line-extraction kernel times for the bench's 64 varied frames (B = 6144) under the environment knobs given on the command line
-(NAME=VALUE ...); prints the top kernels.  Example: python tools/lsd_env_probe.py SSLAM_COUNT_WAVES=2"""
+(NAME=VALUE ...); prints the top kernels.  Example: python tools/lsd_env_probe.py SSLAM_NFA_FUSED=0"""
 import sys, os
 for a in sys.argv[1:]:
     k, v = a.split("=", 1); os.environ[k] = v

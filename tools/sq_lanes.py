@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Lane occupancy of the vector instructions per kernel from one rocprofv3 --pmc pass (tools/gpu_profile_r05_final.sh, the third SQ pass):
+"""Lane occupancy of the vector instructions per kernel from one rocprofv3 --pmc pass (round 5's final recipe, the third SQ pass):
    tools/sq_lanes.py <sq3.txt> [batch]     (the per-kernel sums of tools/rocpd_pmc_summary.py)
 lanes = SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU (the ratio rocprofiler-sdk calls AvgNumActiveThreads): how many of a wave's 64 lanes the EXEC mask enables per vector
 instruction, averaged over the kernel.  It counts ENABLED lanes: a wave-uniform computation that every lane executes for one pixel (the accept chain of k_lsd_regions) counts 64."""

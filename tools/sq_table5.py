@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel SQ table from the three rocprofv3 --pmc passes of tools/gpu_profile_r05_final.sh over `tools/step_check 3072 1 0 1` (one stream; previous-frame priming + 1 step):
+"""Per-kernel SQ table from the three rocprofv3 --pmc passes of round 5's final recipe over `tools/step_check 3072 1 0 1` (one stream; previous-frame priming + 1 step):
    tools/sq_table5.py <sq1.txt> <sq2.txt> <sq3.txt> [batch]      (the per-kernel sums of tools/rocpd_pmc_summary.py)
 GRBM_GUI_ACTIVE is summed over the 8 XCDs by rocprofv3, SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles (MI355X_MICROARCH.md).
   ms        GUI cycles of one pass / 8 XCDs / 2.4 GHz (the kernel with the chip to itself)
