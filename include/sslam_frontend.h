@@ -479,6 +479,35 @@ int sslam_frontend_batch_match_camera(sslam_orb* orb, sslam_lines* lines, const 
                                       uint8_t* desc_out, int32_t* nkp_out, int cap, sslam_keyline* kl_out, uint8_t* ldesc_out,
                                       double* linefn_out, int32_t* nl_out, int lcap, const sslam_batch_match* match);
 
+/* ---- colour frames: the cvtColor of Tracking::GrabImageMonocularWithPL (src/Tracking.cc:146-161) ----------------------------------------
+ *     if (mImGray.channels() == 3) cvtColor(mImGray, mImGray, mbRGB ? CV_RGB2GRAY : CV_BGR2GRAY);
+ *     else if (mImGray.channels() == 4) cvtColor(mImGray, mImGray, mbRGB ? CV_RGBA2GRAY : CV_BGRA2GRAY);
+ * on the device.  The format names the byte order of each pixel AS STORED (alpha is ignored): a caller that passes the bytes of its cv::Mat
+ * with mbRGB's choice (RGB / RGBA when Camera.RGB is 1) gets the reference's gray bytes, whatever order the bytes really are in.  Arithmetic:
+ * OpenCV 3.4's 8-bit RGB2Gray<uchar> table form, gray = (4899 R + 9617 G + 1868 B + 8192) >> 14 (DESIGN.md decision D14).
+ * Memory contract of every entry point below: the reads of a frame stay inside [frame, frame + pitch*(h-1) + w*cn) (cn = 1, 3 or 4 bytes per
+ * pixel), the writes touch only bytes [0, w) of each gray row; the padding of the output rows is left alone.  An unknown format, a pitch
+ * below w*cn (gray: below w) or frames that overlap (image_stride < pitch*(h-1) + w*cn, when nframes > 1) give SSLAM_ERR_INVALID. */
+enum { SSLAM_PIX_GRAY = 0, SSLAM_PIX_RGB = 1, SSLAM_PIX_BGR = 2, SSLAM_PIX_RGBA = 3, SSLAM_PIX_BGRA = 4 };
+/* One frame, host in, host out, through the device (synchronous): img = h rows of `stride` bytes, gray = h rows of `gray_stride` bytes.
+ * SSLAM_PIX_GRAY copies the w bytes of each row. */
+int sslam_gray_from_color(sslam_ctx* ctx, int format, const uint8_t* img, int w, int h, size_t stride, uint8_t* gray, size_t gray_stride);
+/* Device buffers: frame f of d_src at d_src + f*image_stride (row pitch `pitch`) -> d_gray + f*gray_image_stride (row pitch `gray_pitch`),
+ * one launch for the batch, enqueued on `stream` (NULL: the context stream).  SSLAM_PIX_GRAY is a pitched device copy. */
+int sslam_gray_from_color_batch_dev(sslam_ctx* ctx, int format, const uint8_t* d_src, int w, int h, size_t pitch, size_t image_stride, int nframes,
+                                    uint8_t* d_gray, size_t gray_pitch, size_t gray_image_stride, void* stream);
+/* sslam_frontend_batch_match_camera for colour frames in host memory: frame i of `format` at images + i*image_stride (row pitch `stride`, at
+ * least w*cn).  Each chunk is uploaded as it is stored (cn bytes per pixel) and converted on the device right behind its upload; both
+ * extractors then read the gray plane exactly as sslam_frontend_batch hands them its frames, so every output equals what the gray entry points
+ * return for the converted frames.  `cam` may be NULL (kpun_out is then not read or written: sslam_frontend_batch_match), and `match` may be
+ * NULL (no match stage: sslam_frontend_batch).  SSLAM_PIX_GRAY is byte-identical to sslam_frontend_batch / _match / _match_camera.  n == 1 is
+ * the single-frame colour call: one upload feeds both extractors.  The staging of pageable frames copies cn bytes per pixel; the host does
+ * not convert. */
+int sslam_frontend_batch_color(sslam_orb* orb, sslam_lines* lines, const sslam_camera* cam, int format, const uint8_t* images, int n, int w, int h,
+                               size_t stride, size_t image_stride, int chunk, sslam_keypoint* kp_out, sslam_keypoint* kpun_out, uint8_t* desc_out,
+                               int32_t* nkp_out, int cap, sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out, int32_t* nl_out, int lcap,
+                               const sslam_batch_match* match);
+
 /* ---- multi-GPU batch mode (SURVEY.md §8(b) "sslam_group_create + sslam_frontend_batch_sharded", §8(e)) ----------------------
  * north_star: "a batch-of-frames mode shards independent images across the 8 GPUs of one node with RCCL over xGMI only for the final
  * keypoint/line gather".  Frames are independent units: global frame i lives on GPU i % G.  Each GPU runs the single-GPU path on its

@@ -19,9 +19,13 @@
 //     of the chunk before it), so "previous" and "current" are the same arrays one frame apart and the *_batch_dev matchers run unchanged;
 //   * sslam_frontend_batch_match_camera adds Frame::UndistortKeyPoints (src/Frame.cc:483-513) behind the extraction: the undistorted rows
 //     (mvKeysUn) live beside the raw ones in their own array of C + 1 frames, the carried predecessor included, and the match stage reads
-//     them; without a camera none of this is allocated, launched or copied.
+//     them; without a camera none of this is allocated, launched or copied;
+//   * sslam_frontend_batch_color takes colour frames (Tracking::GrabImageMonocularWithPL, src/Tracking.cc:146-161): the slot's input holds cn
+//     bytes per pixel, k_gray_from_color writes the tight gray plane (dGray) on the upload stream right behind the H2D copy, before evIn is
+//     recorded, and both branches read that plane with the arguments they get for gray frames; with SSLAM_PIX_GRAY nothing of this exists.
 #include "common.h"
 #include "camera.h"
+#include "color.h"
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
@@ -91,11 +95,12 @@ struct Slot {
     DevBuf dIn, dKp, dDesc, dN, dKl, dLd, dFn, dNl, dStatus;
     DevBuf dPm, dM12, dNm, dKnnI, dKnnD, dLp, dNlp;      // match stage: vbPrevMatched, vnMatches12, counts, 2-NN, line pairs
     DevBuf dKpUn;                                        // camera form: mvKeysUn, laid out like dKp
+    DevBuf dGray;                                        // colour form: the chunk's gray planes (dIn then holds the colour frames)
     HostPinned hIn, hOut, hStatus;
     hipEvent_t evIn = nullptr, evPoint = nullptr, evLines = nullptr, evOut = nullptr;
     int first = 0, count = 0;            // frames of the chunk in flight
     void release() {
-        dIn.release(); dKp.release(); dDesc.release(); dN.release(); dKl.release(); dLd.release(); dFn.release(); dNl.release(); dStatus.release(); dPm.release(); dM12.release(); dNm.release(); dKnnI.release(); dKnnD.release(); dLp.release(); dNlp.release(); dKpUn.release(); hIn.release(); hOut.release(); hStatus.release();
+        dIn.release(); dKp.release(); dDesc.release(); dN.release(); dKl.release(); dLd.release(); dFn.release(); dNl.release(); dStatus.release(); dPm.release(); dM12.release(); dNm.release(); dKnnI.release(); dKnnD.release(); dLp.release(); dNlp.release(); dKpUn.release(); dGray.release(); hIn.release(); hOut.release(); hStatus.release();
         for (hipEvent_t* e : {&evIn, &evPoint, &evLines, &evOut}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
     }
 };
@@ -120,11 +125,13 @@ namespace {
 int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t* images, int n, int w, int h, size_t stride, size_t image_stride, int chunk,
                sslam_keypoint* kp_out, uint8_t* desc_out, int32_t* nkp_out, int cap,
                sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out, int32_t* nl_out, int lcap, const sslam_batch_match* M,
-               const sslam_camera* cam = nullptr, sslam_keypoint* kpun_out = nullptr) {
+               const sslam_camera* cam = nullptr, sslam_keypoint* kpun_out = nullptr, int format = SSLAM_PIX_GRAY) {
     sslam_ctx* ctx = orb ? sslam_orb_context(orb) : nullptr;
-    if (!orb || !ctx || n < 0 || w <= 0 || h <= 0 || stride < (size_t)w || cap <= 0 || (n > 0 && (!images || !kp_out || !desc_out || !nkp_out)) ||
+    const int cn = pix_channels(format);      // bytes per input pixel; 0: unknown format
+    if (!orb || !ctx || n < 0 || w <= 0 || h <= 0 || cn == 0 || stride < (size_t)w * cn || cap <= 0 || (n > 0 && (!images || !kp_out || !desc_out || !nkp_out)) ||
         (cam && (cam->fx == 0.0f || cam->fy == 0.0f || (n > 0 && !kpun_out))) ||
-        (lines && (sslam_lines_context(lines) != ctx || lcap <= 0 || (n > 0 && (!kl_out || !ldesc_out || !linefn_out || !nl_out)))) || (n > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w) ||
+        (cn > 1 && !gray_layout_ok(format, w, h, stride, image_stride, n)) ||
+        (lines && (sslam_lines_context(lines) != ctx || lcap <= 0 || (n > 0 && (!kl_out || !ldesc_out || !linefn_out || !nl_out)))) || (n > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w * cn) ||
         (M && n > 0 && (!M->init_matches12 || !M->init_nmatches || (M->knn_idx == nullptr) != (M->knn_dist == nullptr) || (lines && (!M->line_pairs || !M->line_npairs))))) {
         set_error("%s: invalid arguments", fn); return SSLAM_ERR_INVALID;
     }
@@ -134,13 +141,15 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
     const size_t fpx = (size_t)w * h;
     const bool knn = M && M->knn_idx, lmatch = M && lines;
     const bool U = cam != nullptr;      // camera form: mvKeysUn beside mvKeys
+    const bool colour = format != SSLAM_PIX_GRAY;      // colour form: cn bytes per pixel uploaded, converted into dGray on the device
+    const size_t fin = fpx * cn;        // input bytes per frame
     int C = std::min(n, chunk > 0 ? chunk : 6144);
     if (chunk <= 0) {      // the default follows the core's wave slots, but never asks for more than a third of the free device memory
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
             // per frame: the ORB workspace (pyramid + three candidate planes ~ 4.2 B per pixel), the LSD / LBD workspace (0.64 x 28 B of planes, order list and
-            // region spill per pixel, 4 B of Sobel pairs, ~1.4 MB of rectangle / NFA records), the two slots of inputs and outputs
-            const size_t perFrame = 6 * fpx + (lines ? 25 * fpx + 1500000 : 0) + 2 * fpx + (size_t)cap * (60 * 3 + (U ? 28 * 3 : 0) + (M ? 12 + 20 + (knn ? 32 + 256 : 0) : 0)) + (lines ? (size_t)lcap * 124 * 3 : 0) + 65536;
+            // region spill per pixel, 4 B of Sobel pairs, ~1.4 MB of rectangle / NFA records), the two slots of inputs (cn B per pixel, plus the gray plane of a colour frame) and outputs
+            const size_t perFrame = 6 * fpx + (lines ? 25 * fpx + 1500000 : 0) + 2 * fin + (colour ? 2 * fpx : 0) + (size_t)cap * (60 * 3 + (U ? 28 * 3 : 0) + (M ? 12 + 20 + (knn ? 32 + 256 : 0) : 0)) + (lines ? (size_t)lcap * 124 * 3 : 0) + 65536;
             const size_t fit = freeB / 3 / std::max<size_t>(perFrame, 1);
             if ((size_t)C > fit) C = (int)std::max<size_t>(fit, 1);      // little free memory (another process on the GPU, very large frames): smaller chunks, down to one frame; only then can an allocation fail
         }
@@ -160,7 +169,7 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
         if (!q || hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); return false; }
         return a.type == hipMemoryTypeHost;
     };
-    const bool inDirect = stride == (size_t)w && (n == 1 || image_stride == fpx) && is_pinned(images);
+    const bool inDirect = stride == (size_t)w * cn && (n == 1 || image_stride == fin) && is_pinned(images);
     const bool outDirect = is_pinned(kp_out) && is_pinned(desc_out) && is_pinned(nkp_out) && (!U || is_pinned(kpun_out)) &&
                            (!lines || (is_pinned(kl_out) && is_pinned(ldesc_out) && is_pinned(linefn_out) && is_pinned(nl_out))) &&
                            (!M || (is_pinned(M->init_matches12) && is_pinned(M->init_nmatches) && (!knn || (is_pinned(M->knn_idx) && is_pinned(M->knn_dist))) &&
@@ -180,14 +189,15 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
     for (int i = 0; i < 2; ++i) {
         Slot& s = slot[i];
         s.count = 0;
-        if ((rc = s.dIn.ensure(fpx * C)) || (rc = s.dKp.ensure(sizeof(sslam_keypoint) * F1 * cap)) || (rc = s.dDesc.ensure(32 * F1 * cap)) ||
-            (rc = s.dN.ensure(4 * F1)) || (rc = s.dStatus.ensure(32)) || (rc = s.hStatus.ensure(32)) || (!inDirect && (rc = s.hIn.ensure(fpx * C))) || (!outDirect && (rc = s.hOut.ensure(outBytes)))) return rc;
+        if ((rc = s.dIn.ensure(fin * C)) || (rc = s.dKp.ensure(sizeof(sslam_keypoint) * F1 * cap)) || (rc = s.dDesc.ensure(32 * F1 * cap)) ||
+            (rc = s.dN.ensure(4 * F1)) || (rc = s.dStatus.ensure(32)) || (rc = s.hStatus.ensure(32)) || (!inDirect && (rc = s.hIn.ensure(fin * C))) || (!outDirect && (rc = s.hOut.ensure(outBytes)))) return rc;
         if (lines && ((rc = s.dKl.ensure(sizeof(sslam_keyline) * (size_t)C * lcap)) || (rc = s.dLd.ensure(32 * F1 * lcap)) ||
                       (rc = s.dFn.ensure(24 * (size_t)C * lcap)) || (rc = s.dNl.ensure(4 * F1)))) return rc;
         if (M && ((rc = s.dPm.ensure(8 * (size_t)C * cap)) || (rc = s.dM12.ensure(4 * (size_t)C * cap)) || (rc = s.dNm.ensure(4 * (size_t)C)) ||
                   (knn && ((rc = s.dKnnI.ensure(8 * (size_t)C * cap)) || (rc = s.dKnnD.ensure(8 * (size_t)C * cap)))) ||
                   (lmatch && ((rc = s.dLp.ensure(8 * (size_t)C * lcap)) || (rc = s.dNlp.ensure(4 * (size_t)C)))))) return rc;
         if (U && (rc = s.dKpUn.ensure(sizeof(sslam_keypoint) * F1 * cap))) return rc;
+        if (colour && (rc = s.dGray.ensure(fpx * C))) return rc;
         for (hipEvent_t* e : {&s.evIn, &s.evPoint, &s.evLines, &s.evOut})
             if (!*e && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { set_error("%s: hipEventCreate failed", fn); return SSLAM_ERR_HIP; }
         if (n <= C) break;                 // one chunk: the second slot is never used
@@ -241,15 +251,15 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
     for (int f0 = 0; f0 < n && rc == SSLAM_OK; f0 += C, ++k) {
         Slot& s = slot[k & 1];
         const int c = std::min(C, n - f0);
-        const uint8_t* hin = images + (size_t)f0 * fpx;
+        const uint8_t* hin = images + (size_t)f0 * fin;
         if (!inDirect) {      // this chunk's frames -> the slot's pinned input buffer (its previous upload, chunk k-2, finished long ago: the kernels of k-2 ran behind it and its results are in)
             uint8_t* stage = s.hIn.as<uint8_t>();
             if (s.count && hipEventSynchronize(s.evIn) != hipSuccess) { set_error("%s: H2D failed", fn); rc = SSLAM_ERR_HIP; break; }
             pool->parallel_for(gStage, c, [=](int a, int b) {               // tight rows in the staging buffer
                 for (int i = a; i < b; ++i) {
                     const uint8_t* src = images + (size_t)(f0 + i) * image_stride;
-                    if (stride == (size_t)w) std::memcpy(stage + i * fpx, src, fpx);
-                    else for (int y = 0; y < h; ++y) std::memcpy(stage + i * fpx + (size_t)y * w, src + (size_t)y * stride, w);
+                    if (stride == (size_t)w * cn) std::memcpy(stage + i * fin, src, fin);
+                    else for (int y = 0; y < h; ++y) std::memcpy(stage + i * fin + (size_t)y * w * cn, src + (size_t)y * stride, (size_t)w * cn);
                 }
             });
             hin = stage;
@@ -257,7 +267,11 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
         if ((rc = drain(k & 1))) { gStage.wait(); break; }                 // the slot's previous chunk (k-2): its copy-out runs on the pool beside the staging above
         gStage.wait();
         hipStream_t stLn = twoStreams ? stL : stP;
-        if (hipMemcpyAsync(s.dIn.p, hin, fpx * c, hipMemcpyHostToDevice, cp) != hipSuccess || hipEventRecord(s.evIn, cp) != hipSuccess ||
+        if (hipMemcpyAsync(s.dIn.p, hin, fin * c, hipMemcpyHostToDevice, cp) != hipSuccess) { set_error("%s: H2D failed", fn); rc = SSLAM_ERR_HIP; break; }
+        // colour frames: the gray planes the two branches read, converted on the upload stream before evIn releases them
+        if (colour && (rc = gray_from_color_launch(ctx, format, s.dIn.as<uint8_t>(), w, h, (size_t)w * cn, fin, c, s.dGray.as<uint8_t>(), (size_t)w, fpx, cp))) break;
+        const uint8_t* dImg = colour ? s.dGray.as<uint8_t>() : s.dIn.as<uint8_t>();
+        if (hipEventRecord(s.evIn, cp) != hipSuccess ||
             hipStreamWaitEvent(stP, s.evIn, 0) != hipSuccess || (twoStreams && hipStreamWaitEvent(stL, s.evIn, 0) != hipSuccess)) { set_error("%s: H2D failed", fn); rc = SSLAM_ERR_HIP; break; }
         // the chunk's frames start one frame into the feature arrays
         sslam_keypoint* dKp = s.dKp.as<sslam_keypoint>() + cap; uint8_t* dDesc = s.dDesc.as<uint8_t>() + 32 * (size_t)cap; int32_t* dN = s.dN.as<int32_t>() + 1;
@@ -281,7 +295,7 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
             if (!ok) { set_error("%s: carrying the previous frame failed", fn); rc = SSLAM_ERR_HIP; break; }
         }
         // line branch first: its call records the core event; the point branch then waits for that event and runs under the latency-bound core
-        if (lines && (rc = sslam_lines_extract_batch_dev(lines, s.dIn.as<uint8_t>(), w, h, (size_t)w, fpx, c, s.dKl.as<sslam_keyline>(), dLd, s.dFn.as<double>(), dNl, lcap, stLn))) break;
+        if (lines && (rc = sslam_lines_extract_batch_dev(lines, dImg, w, h, (size_t)w, fpx, c, s.dKl.as<sslam_keyline>(), dLd, s.dFn.as<double>(), dNl, lcap, stLn))) break;
         if (lines && (rc = sslam_lines_batch_status_dev(lines, lcap, s.dStatus.as<int32_t>() + 4, stLn))) break;
         if (lmatch && (rc = sslam_line_match_batch_dev(ctx, s.dLd.as<uint8_t>(), s.dNl.as<int32_t>(), dLd, dNl, lcap, c, M->line_gate_scale, M->line_ratio_mode,
                                                        s.dLp.as<int32_t>(), s.dNlp.as<int32_t>(), stLn))) break;
@@ -289,7 +303,7 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
         const bool guestForm = twoStreams && sslam_lines_core_guest_form(lines, c) != 0;
         (void)sslam_orb_set_gate_event(orb, guestForm ? (void*)B.evCore : nullptr);
         if (twoStreams && (hipEventRecord(s.evLines, stL) != hipSuccess || (!guestForm && hipStreamWaitEvent(stP, B.evCore, 0) != hipSuccess))) { set_error("%s: event failed", fn); rc = SSLAM_ERR_HIP; break; }
-        if ((rc = sslam_orb_extract_batch_dev(orb, s.dIn.as<uint8_t>(), w, h, (size_t)w, fpx, c, dKp, dDesc, dN, cap, stP))) break;
+        if ((rc = sslam_orb_extract_batch_dev(orb, dImg, w, h, (size_t)w, fpx, c, dKp, dDesc, dN, cap, stP))) break;
         if ((rc = sslam_orb_batch_status_dev(orb, cap, s.dStatus.as<int32_t>(), stP))) break;
         if (U && (rc = undistort_launch(ctx, *cam, dKp, dN, 0, c, cap, dKpUn, stP))) break;       // Frame::UndistortKeyPoints (src/Frame.cc:95)
         if (M) {      // previous frame = F1 (query), current frame = F2 (train), as Tracking::MonocularInitialization calls it (src/Tracking.cc:330-345)
@@ -362,6 +376,15 @@ extern "C" int sslam_frontend_batch_match_camera(sslam_orb* orb, sslam_lines* li
     if (!cam) { set_error("sslam_frontend_batch_match_camera: invalid arguments"); return SSLAM_ERR_INVALID; }
     return batch_impl("sslam_frontend_batch_match_camera", orb, lines, images, n, w, h, stride, image_stride, chunk, kp_out, desc_out, nkp_out, cap,
                       kl_out, ldesc_out, linefn_out, nl_out, lcap, match, cam, kpun_out);
+}
+
+extern "C" int sslam_frontend_batch_color(sslam_orb* orb, sslam_lines* lines, const sslam_camera* cam, int format, const uint8_t* images, int n, int w, int h,
+                                          size_t stride, size_t image_stride, int chunk, sslam_keypoint* kp_out, sslam_keypoint* kpun_out, uint8_t* desc_out,
+                                          int32_t* nkp_out, int cap, sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out, int32_t* nl_out, int lcap,
+                                          const sslam_batch_match* match) {
+    if (pix_channels(format) == 0) { set_error("sslam_frontend_batch_color: unknown format %d (SSLAM_PIX_*)", format); return SSLAM_ERR_INVALID; }
+    return batch_impl("sslam_frontend_batch_color", orb, lines, images, n, w, h, stride, image_stride, chunk, kp_out, desc_out, nkp_out, cap,
+                      kl_out, ldesc_out, linefn_out, nl_out, lcap, match, cam, cam ? kpun_out : nullptr, format);
 }
 
 // Releases the staging buffers, streams and events sslam_frontend_batch keeps per context between calls (they are also released with the context).

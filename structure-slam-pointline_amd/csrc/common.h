@@ -66,6 +66,7 @@ struct sslam_ctx {
     std::recursive_mutex mu;       // every entry point serialises on the context (SURVEY §8b threading); recursive: the host forms call the *_batch_dev forms
     sslam::DevBuf scratch[8];      // matcher staging
     sslam::DevBuf camKp;           // sslam_undistort_keypoints: the host rows on the device (camera.hip)
+    sslam::DevBuf colorIn, colorGray;      // sslam_gray_from_color: the host frame and its gray plane on the device (color.hip)
     sslam::DevBuf knnExpand;       // sslam_hamming_knn2_batch_dev: the train rows as int8 matrix-core operands (match_knn.h)
     hipEvent_t knnDone = nullptr;  // recorded behind the kernel that reads knnExpand: a call on ANOTHER stream waits for it before it overwrites the buffer
     void* knnLastStream = nullptr;

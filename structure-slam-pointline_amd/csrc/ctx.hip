@@ -77,6 +77,7 @@ extern "C" int sslam_ctx_destroy(sslam_ctx* c) {
     for (auto& b : c->scratch) b.release();
     c->knnExpand.release();
     c->camKp.release();
+    c->colorIn.release(); c->colorGray.release();
     if (c->knnDone) (void)hipEventDestroy(c->knnDone);
     for (auto& b : c->recordOffsets) b.release();
     for (auto& b : c->pinned) b.release();

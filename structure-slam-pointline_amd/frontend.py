@@ -26,6 +26,23 @@ assert PQ_DTYPE.itemsize == 44
 
 _lib = None
 
+PIX_GRAY, PIX_RGB, PIX_BGR, PIX_RGBA, PIX_BGRA = 0, 1, 2, 3, 4      # SSLAM_PIX_* (include/sslam_frontend.h)
+PIX_CHANNELS = {PIX_GRAY: 1, PIX_RGB: 3, PIX_BGR: 3, PIX_RGBA: 4, PIX_BGRA: 4}
+
+
+def pix_format(channels, rgb=True):
+    """the SSLAM_PIX_* format Tracking::GrabImageMonocularWithPL converts with (src/Tracking.cc:146-161): channels 1, 3 or 4, rgb = mbRGB"""
+    return {1: PIX_GRAY, 3: PIX_RGB if rgb else PIX_BGR, 4: PIX_RGBA if rgb else PIX_BGRA}[int(channels)]
+
+
+def _image_layout(images, fmt, batch):
+    """(n, h, w, row pitch, image stride) of a uint8 numpy array [n,] h, w[, cn] in fmt whose pixels are packed (rows and frames may be padded views)"""
+    cn = PIX_CHANNELS[fmt]
+    a = images if batch else images[None]
+    assert a.dtype == np.uint8 and a.ndim == (3 if cn == 1 else 4) and (cn == 1 or a.shape[3] == cn), (a.dtype, a.shape, fmt)
+    assert a.strides[2] == cn and (cn == 1 or a.strides[3] == 1), "pixels must be packed (rows and frames may be padded)"
+    return a.shape[0], a.shape[1], a.shape[2], a.strides[1], a.strides[0]
+
 
 SSLAM_ERR_INVALID, SSLAM_ERR_NO_DEVICE, SSLAM_ERR_CAPACITY, SSLAM_ERR_HIP, SSLAM_ERR_UNSUPPORTED = -1, -2, -3, -4, -5      # include/sslam_frontend.h:31-35
 
@@ -207,6 +224,25 @@ class Context:
     def undistort_keypoints_batch_dev(self, cam, d_kp, d_counts, nframes, cap, d_kp_un, stream=None):
         """sslam_undistort_keypoints_batch_dev on device buffers laid out like sslam_orb_extract_batch_dev's (d_kp_un may be d_kp)"""
         _chk(lib().sslam_undistort_keypoints_batch_dev(self.h, C.byref(cam), _p(d_kp), _p(d_counts), int(nframes), int(cap), _p(d_kp_un), C.c_void_p(stream or 0)))
+
+    # ---- colour frames ----------------------------------------------------------
+    def gray_from_color(self, img, order="rgb", out=None):
+        """the cvtColor of Tracking::GrabImageMonocularWithPL (sslam_gray_from_color) on a numpy [h, w, 3|4] array (rows may be padded; [h, w]:
+        a copy) whose bytes are in `order` ("rgb": RGB / RGBA, "bgr": BGR / BGRA).  out: a uint8 [h, >= w] array (its rows may be padded) that
+        receives the gray rows in out[:, :w]; only those bytes are written.  Returns the [h, w] gray image."""
+        assert order in ("rgb", "bgr")
+        fmt = pix_format(img.shape[2] if img.ndim == 3 else 1, order == "rgb")
+        _, h, w, stride, _ = _image_layout(img, fmt, False)
+        if out is None:
+            out = np.empty((h, w), np.uint8)
+        assert out.dtype == np.uint8 and out.ndim == 2 and out.shape[0] == h and out.shape[1] >= w and out.strides[1] == 1
+        _chk(lib().sslam_gray_from_color(self.h, fmt, _p(img), w, h, C.c_size_t(stride), _p(out), C.c_size_t(out.strides[0])))
+        return out[:, :w]
+
+    def gray_from_color_batch_dev(self, fmt, d_src, w, h, pitch, image_stride, nframes, d_gray, gray_pitch, gray_image_stride, stream=None):
+        """sslam_gray_from_color_batch_dev on device pointers / tensors (byte pitches and strides)"""
+        _chk(lib().sslam_gray_from_color_batch_dev(self.h, int(fmt), _p(d_src), int(w), int(h), C.c_size_t(pitch), C.c_size_t(image_stride), int(nframes),
+                                                   _p(d_gray), C.c_size_t(gray_pitch), C.c_size_t(gray_image_stride), C.c_void_p(stream or 0)))
 
 
 class Vocabulary:
@@ -435,6 +471,31 @@ def frontend_batch_match_camera_raw(orb, lines, cam, images, out, mout=None, chu
     _chk(lib().sslam_frontend_batch_match_camera(orb.h, lines.h if lines is not None else None, C.byref(cam), _p(images), n, w, h, C.c_size_t(w),
                                                  C.c_size_t(w * h), int(chunk), _p(kp), _p(kpun), _p(desc), _p(nk), orb.cap, _p(kl), _p(ld), _p(fn), _p(nl),
                                                  int(kl.shape[1]), C.byref(M) if M is not None else None))
+    return out, mout
+
+
+def frontend_batch_color_raw(orb, lines, fmt, images, out, mout=None, cam=None, chunk=0, window=100, nnratio=0.9, check_orientation=True, bounds=None,
+                             line_gate_scale=0.5, line_ratio_mode=False):
+    """sslam_frontend_batch_color: images = uint8 [n, h, w, cn] in fmt (SSLAM_PIX_*; [n, h, w] for PIX_GRAY) in HOST memory, rows and frames
+    may be padded views.  out: frontend_batch_alloc's seven arrays, or frontend_batch_camera_alloc's eight with a Camera; mout:
+    frontend_batch_match_alloc's six or None (no match stage).  bounds default to the camera's (or the whole image)."""
+    n, h, w, stride, image_stride = _image_layout(images, fmt, True)
+    kp, desc, nk, kl, ld, fn, nl = out[:7]
+    kpun = out[7] if cam is not None else None
+    M = None
+    if mout is not None:
+        m12, nm, ki, kd, lp, nlp = mout
+        M = BatchMatch()
+        M.window_size = int(window); M.nnratio = float(nnratio); M.check_orientation = int(bool(check_orientation))
+        if bounds is None:
+            bounds = camera_image_bounds(cam, w, h) if cam is not None else (0.0, float(w), 0.0, float(h))
+        M.bounds = (C.c_float * 4)(*bounds)
+        M.line_gate_scale = float(line_gate_scale); M.line_ratio_mode = int(bool(line_ratio_mode))
+        vp = lambda a: a.ctypes.data if a is not None else None
+        M.init_matches12 = vp(m12); M.init_nmatches = vp(nm); M.knn_idx = vp(ki); M.knn_dist = vp(kd); M.line_pairs = vp(lp); M.line_npairs = vp(nlp)
+    _chk(lib().sslam_frontend_batch_color(orb.h, lines.h if lines is not None else None, C.byref(cam) if cam is not None else None, int(fmt), _p(images),
+                                          n, w, h, C.c_size_t(stride), C.c_size_t(image_stride), int(chunk), _p(kp), _p(kpun), _p(desc), _p(nk), orb.cap,
+                                          _p(kl), _p(ld), _p(fn), _p(nl), int(kl.shape[1]), C.byref(M) if M is not None else None))
     return out, mout
 
 

@@ -6,6 +6,9 @@ torch's current stream through the *_dev entry points.
 Workload = BASELINE config 3: per frame ORB extract (1000 kp) + LSD/LBD extract (<=200
 lines) + match against the previous frame's features: ORBmatcher::SearchForInitialization
 (window 100, level 0) + dense knn-2 over all ORB descriptors, and the LSD knn-2 + MAD gate.
+
+Colour frames ([B, h, w, 3|4] tensors; channel order from the constructor's `rgb`, Tracking's mbRGB) are converted on the device into a gray
+tensor the pipeline owns (sslam_gray_from_color_batch_dev), on the stream the extraction starts on; the gray path then runs unchanged.
 """
 import ctypes as C
 import numpy as np
@@ -13,8 +16,10 @@ import torch
 
 
 class FrontendBatch:
-    def __init__(self, fe, ctx, w, h, batch, nfeatures=1000, max_lines=200, device="cuda:0", with_lines=True, with_match=True):
+    def __init__(self, fe, ctx, w, h, batch, nfeatures=1000, max_lines=200, device="cuda:0", with_lines=True, with_match=True, rgb=True):
         self.fe, self.ctx = fe, ctx
+        self.rgb = rgb                  # byte order of colour inputs: RGB / RGBA (True) or BGR / BGRA, as mbRGB (src/Tracking.cc:146-161)
+        self.gray = None                # the converted frames of a colour input, allocated on first use
         self.w, self.h, self.B = w, h, batch
         self.dev = torch.device(device)
         self.with_lines, self.with_match = with_lines, with_match
@@ -49,9 +54,31 @@ class FrontendBatch:
             self._s1, self._s2 = torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev, priority=pr)
         return self._s1, self._s2
 
+    def _to_gray(self, images):
+        """[B, h, w] tensors pass through; a contiguous uint8 [B, h, w, 3|4] tensor is converted into self.gray on the point stream (the stream
+        the extraction starts on), which the caller's current stream then waits for"""
+        if images.dim() == 3:
+            return images
+        assert images.is_cuda and images.dtype == torch.uint8 and images.shape[:3] == (self.B, self.h, self.w) and images.shape[3] in (3, 4) \
+            and images.is_contiguous()
+        cn = images.shape[3]
+        if self.gray is None:
+            self.gray = torch.empty(self.B, self.h, self.w, dtype=torch.uint8, device=self.dev)
+        s1, s2 = self._streams()
+        cur = torch.cuda.current_stream(self.dev)
+        s1.wait_stream(cur)
+        s1.wait_stream(s2)          # the line branch of a previous step (join=False) may still read self.gray
+        with torch.cuda.stream(s1):
+            self.ctx.gray_from_color_batch_dev(self.fe.pix_format(cn, self.rgb), images, self.w, self.h, self.w * cn, self.w * self.h * cn, self.B,
+                                               self.gray, self.w, self.w * self.h, self._stream())
+            images.record_stream(s1)
+        cur.wait_stream(s1)
+        return self.gray
+
     def extract(self, images, tag="cur", lines_first=False):
-        """images: uint8 device tensor [B, h, w] (contiguous).  Runs on the pipeline's point stream; the
-        caller's current stream is ordered before and after."""
+        """images: uint8 device tensor [B, h, w] (contiguous), or [B, h, w, 3|4] colour frames (converted first).  Runs on the pipeline's
+        point stream; the caller's current stream is ordered before and after."""
+        images = self._to_gray(images)
         assert images.is_cuda and images.dtype == torch.uint8 and images.shape == (self.B, self.h, self.w) and images.is_contiguous()
         f = self.feat[tag]
         s1, _ = self._streams()
@@ -108,7 +135,9 @@ class FrontendBatch:
     def step(self, images, overlap=False, lines_first=False, join=True):
         """One pass of the hot path.  overlap=True runs the point branch (ORB extract + ORB matching)
         and the line branch (LSD/LBD extract + line matching) on two HIP streams: the line branch is
-        latency-bound (one persistent wave per frame), the point branch fills the idle issue slots."""
+        latency-bound (one persistent wave per frame), the point branch fills the idle issue slots.
+        images: as extract() takes them."""
+        images = self._to_gray(images)
         if not (overlap and self.with_lines):
             self.extract(images, "cur", lines_first=lines_first)
             if self.with_match:

@@ -24,13 +24,15 @@
 #include <vector>
 #define CV_8U 0
 #define CV_8UC1 0
+#define CV_8UC3 16           // CV_MAKETYPE(CV_8U, 3): interleaved 8-bit colour (camera frames: Tracking::GrabImageMonocularWithPL)
+#define CV_8UC4 24
 #define CV_32F 5
 namespace cv {
 struct Point2f { float x = 0, y = 0; Point2f() {} Point2f(float a, float b) : x(a), y(b) {} };
 struct KeyPoint {            // opencv2/core/types.hpp
     Point2f pt; float size = 0, angle = -1, response = 0; int octave = 0, class_id = -1;
 };
-class Mat {                  // the subset of cv::Mat the front-end boundary touches: single channel, 8-bit (images, descriptors) or 32-bit float (poses, points)
+class Mat {                  // the subset of cv::Mat the front-end boundary touches: 8-bit (images, descriptors; 1, 3 or 4 channels) or 32-bit float (poses, points)
 public:
     int rows = 0, cols = 0; size_t step = 0; uint8_t* data = nullptr;
     Mat() {}
@@ -43,6 +45,7 @@ public:
     void release() { own_.reset(); data = nullptr; rows = cols = 0; step = 0; }
     bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
     int type() const { return type_; }
+    int channels() const { return (type_ >> 3) + 1; }
     bool isContinuous() const { return step == (size_t)cols * esz(type_); }
     uint8_t* ptr(int r = 0) { return data + (size_t)r * step; }
     const uint8_t* ptr(int r = 0) const { return data + (size_t)r * step; }
@@ -52,7 +55,7 @@ public:
     template <class T> const T& at(int r, int c = 0) const { return ptr<T>(r)[c]; }
     Mat row(int r) const { Mat m(1, cols, type_, (void*)ptr(r), step); m.keep_ = own_; return m; }
 private:
-    static size_t esz(int type) { return type == CV_32F ? 4 : 1; }
+    static size_t esz(int type) { return (size_t)(type == CV_32F ? 4 : 1) * ((type >> 3) + 1); }      // bytes per element: depth x channels
     int type_ = CV_8U;
     std::shared_ptr<uint8_t[]> own_, keep_;
 };
