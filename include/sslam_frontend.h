@@ -109,6 +109,8 @@ int sslam_orb_extract(sslam_orb* orb, const uint8_t* gray, int w, int h, size_t 
  * Level 0 of the pyramid is READ IN PLACE from d_images when base, pitch and image_stride are multiples of 4 and the frames are whole blocks
  * (pitch == w, or image_stride >= pitch * h): the kernels load aligned dwords and may touch the padding bytes [w, pitch) of a row, so with
  * padded rows every frame -- the last one included -- must be readable for pitch * h bytes.  Any other layout is copied first (one more pass).
+ * A pitch below w, or frames that overlap (image_stride < pitch * (h - 1) + w, when nframes > 1), give SSLAM_ERR_INVALID; nothing is enqueued.
+ * The padding bytes, the gaps between frames and the bytes around the buffer never change a result, and the images are only read.
  * The images must stay valid until the call's work on `stream` has finished (as for any asynchronous launch). */
 int sslam_orb_extract_batch_dev(sslam_orb* orb, const uint8_t* d_images, int w, int h,
                                 size_t pitch, size_t image_stride, int nframes,
@@ -373,6 +375,10 @@ int sslam_lines_set_nfa_variant(sslam_lines* ln, int variant);
 int sslam_lines_set_lbd_bit_order(sslam_lines* ln, int variant);
 int sslam_lines_set_resize_variant(sslam_lines* ln, int variant);
 int sslam_lines_set_seed_order(sslam_lines* ln, int variant);
+/* Batch-of-frames mode over the image layout of sslam_orb_extract_batch_dev (d_images + i*image_stride is frame i, row pitch `pitch`; with padded
+ * rows the last frame must be readable for pitch * h bytes): d_kl[nframes*cap], d_ldesc[nframes*cap*32], d_linefn[nframes*cap*3], d_counts[nframes].
+ * The layout only chooses how the rows are loaded (aligned dwords for a dword-aligned base, pitch and image_stride; bytes otherwise), never a result.
+ * A pitch below w, or frames that overlap (image_stride < pitch * (h - 1) + w, when nframes > 1), give SSLAM_ERR_INVALID; nothing is enqueued. */
 int sslam_lines_extract_batch_dev(sslam_lines* ln, const uint8_t* d_images, int w, int h,
                                   size_t pitch, size_t image_stride, int nframes,
                                   sslam_keyline* d_kl, uint8_t* d_ldesc, double* d_linefn,

@@ -540,6 +540,7 @@ extern "C" int sslam_lines_extract_batch_dev(sslam_lines* L, const uint8_t* d_im
     if (!L || !d_images || !d_kl || !d_ldesc || !d_linefn || !d_counts || w <= 0 || h <= 0 || nframes <= 0 || cap <= 0 || pitch < (size_t)w) {
         set_error("sslam_lines_extract_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
+    if (nframes > 1 && image_stride < pitch * (size_t)(h - 1) + (size_t)w) { set_error("sslam_lines_extract_batch_dev: the frames overlap (image_stride < pitch * (h - 1) + w)"); return SSLAM_ERR_INVALID; }
     const LinesKnobs K = lines_knobs();
     std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);      // plan, workspace and profile records are shared state
     SSLAM_HIP(hipSetDevice(L->ctx->device));

@@ -1167,6 +1167,7 @@ extern "C" int sslam_orb_extract_batch_dev(sslam_orb* o, const uint8_t* d_images
     if (!o || !d_images || !d_kp || !d_desc || !d_counts || w <= 0 || h <= 0 || nframes <= 0 || cap <= 0 || pitch < (size_t)w) {
         set_error("sslam_orb_extract_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
+    if (nframes > 1 && image_stride < pitch * (size_t)(h - 1) + (size_t)w) { set_error("sslam_orb_extract_batch_dev: the frames overlap (image_stride < pitch * (h - 1) + w)"); return SSLAM_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lk(o->ctx->mu);      // plan, workspace and profile records are shared state
     SSLAM_HIP(hipSetDevice(o->ctx->device));
     hipStream_t st = stream_ ? (hipStream_t)stream_ : o->ctx->stream;
