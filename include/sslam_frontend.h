@@ -338,6 +338,10 @@ int sslam_orb_search_by_bow_keyframes(sslam_ctx* ctx, const sslam_keypoint* kf1_
 int sslam_line_match(sslam_ctx* ctx, const uint8_t* ldesc1, int n1, const uint8_t* ldesc2, int n2,
                      double gate_scale, int ratio_mode, int32_t* pairs_out, int cap, int* npairs_out,
                      double* nn_mad_out, double* nn12_mad_out);
+/* The same for npairs_frames frame pairs on the device: pair p owns rows [p*cap, (p+1)*cap) of d_ldesc1 / d_ldesc2 and of d_pairs
+ * ((qdx,tdx) per row), its counts are d_n1[p] / d_n2[p], d_npairs[p] receives its number of pairs; rows of d_pairs past that number
+ * are not written.  A pair with no query rows, fewer than two train rows, or MORE THAN 1024 QUERY ROWS yields 0 pairs (the single
+ * call returns SSLAM_ERR_UNSUPPORTED for n1 > 1024; the batch form has no per-pair status). */
 int sslam_line_match_batch_dev(sslam_ctx* ctx, const uint8_t* d_ldesc1, const int32_t* d_n1,
                                const uint8_t* d_ldesc2, const int32_t* d_n2, int cap, int npairs_frames,
                                double gate_scale, int ratio_mode, int32_t* d_pairs, int32_t* d_npairs,
