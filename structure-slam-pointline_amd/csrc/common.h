@@ -58,13 +58,31 @@ struct HostPinned {
 
 struct sslam_prof_rec { const char* name; hipEvent_t a, b; };
 
+// Slots of sslam_ctx::scratch and ::pinned (match.hip) with their users.  A slot with several users is safe to share because every one of
+// them holds ctx->mu for the whole call and synchronises the stream before it returns.
+enum {
+    SCR_KNN_Q = 0, SCR_KNN_T = 1, SCR_KNN_OUT = 2,      // sslam_hamming_knn2, sslam_hamming_matrix: query rows, train rows, result
+    SCR_SFI_STATE = 3,       // sslam_orb_search_for_initialization_batch_dev: per-pair state (SfiArgs::scratch)
+    SCR_SFI_STAGE = 4,       // sslam_orb_search_for_initialization: the pair and its results
+    SCR_LINE_MATCH = 5,      // sslam_line_match
+    SCR_CALL = 6,            // the arena of search_proj_core, sslam_hamming_knn2_frames, sslam_distinctive_descriptors, sslam_fuse_search, sslam_orb_search_for_triangulation, bow_core
+    SCR_UPLOAD = 7,          // host features that a core with an arena in SCR_CALL reads (sslam_search_by_projection, sslam_bow_transform); the arena of search_by_bow_core
+    SCR_COUNT = 8
+};
+enum {
+    PIN_BOW = 1,             // search_by_bow_core
+    PIN_SFI = 2,             // sslam_orb_search_for_initialization
+    PIN_PROJ = 3,            // search_proj_core
+    PIN_COUNT = 4            // (slot 0 has no user)
+};
+
 struct sslam_ctx {
     int device = 0;
     bool profEnabled = false;              // per-kernel HIP-event timing (sslam_profile_*)
     std::vector<sslam_prof_rec> prof;
     hipStream_t stream = nullptr;
     std::recursive_mutex mu;       // every entry point serialises on the context (SURVEY §8b threading); recursive: the host forms call the *_batch_dev forms
-    sslam::DevBuf scratch[8];      // matcher staging
+    sslam::DevBuf scratch[SCR_COUNT];      // matcher staging (SCR_*)
     sslam::DevBuf camKp;           // sslam_undistort_keypoints: the host rows on the device (camera.hip)
     sslam::DevBuf colorIn, colorGray;      // sslam_gray_from_color: the host frame and its gray plane on the device (color.hip)
     sslam::DevBuf knnExpand;       // sslam_hamming_knn2_batch_dev: the train rows as int8 matrix-core operands (match_knn.h)
@@ -73,7 +91,7 @@ struct sslam_ctx {
     sslam::DevBuf recordOffsets[4];   // sslam_pack_records_dev: per-frame offsets of the record stream, one buffer per stream that packs
     void* recordOffsetsStream[4] = {nullptr, nullptr, nullptr, nullptr};
     unsigned long recordOffsetsUse[4] = {0, 0, 0, 0}, recordOffsetsClock = 0;      // least-recently-used recycling of the four slots
-    sslam::HostPinned pinned[4];
+    sslam::HostPinned pinned[PIN_COUNT];   // staging mirrors of the matcher arenas (PIN_*)
     int num_cus = 0;
     void* batchCache = nullptr;                  // sslam_frontend_batch: staging buffers, streams, events kept between calls (batch.hip)
     void (*batchCacheFree)(void*) = nullptr;

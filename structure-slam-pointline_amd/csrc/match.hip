@@ -4,8 +4,11 @@
 // src/LSDmatcher.cpp:143-183,257-284,364-415, src/Frame.cc:133-148,190-215,368-472.
 //
 // The path is integer/bitwise: v_bcnt popcounts on 8x u32 XORs, wave-wide min
-// reductions with the tie-break order carried in the key; no MFMA.
+// reductions with the tie-break order carried in the key; the knn-2 of a batch alone runs on the matrix cores (match_knn.h).
+// Which kernel a call launches depends on its sizes alone: the rules are the pure host functions of match_plan.h, and an entry
+// point reads as validate, lock, lay out, stage, switch on the plan's form with one launch per case, copy back.
 #include "common.h"
+#include "match_plan.h"
 #include <algorithm>
 
 using namespace sslam;
@@ -20,6 +23,11 @@ namespace {
 
 // =============================================================== host side
 static hipStream_t pick(sslam_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
+// a launch with more than the default 48 KB of dynamic LDS has to be allowed per kernel
+static int allow_dynamic_lds(const void* kernel, size_t bytes) {
+    if (bytes > 48 * 1024) SSLAM_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return SSLAM_OK;
+}
 
 extern "C" int sslam_hamming_knn2_dev(sslam_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int32_t* d_idx, int32_t* d_dist, void* stream) {
     if (!ctx || nq < 0 || nt < 0 || (nq > 0 && (!d_q || !d_idx || !d_dist))) { set_error("sslam_hamming_knn2_dev: invalid arguments"); return SSLAM_ERR_INVALID; }
@@ -37,25 +45,27 @@ extern "C" int sslam_hamming_knn2_batch_dev(sslam_ctx* ctx, const uint8_t* d_q, 
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
-    const char* formEnv = getenv("SSLAM_KNN2_BATCH");      // experiment / test knob, read on every call: popc = the xor + popcount form (the only one beyond 4096 rows), mfma1 = 32 queries per wave
-    const int form = !formEnv ? 2 : !strcmp(formEnv, "popc") ? 0 : !strcmp(formEnv, "mfma1") ? 1 : 2;
-    const int tilesCap = (cap + 31) / 32;
-    if (tilesCap <= KNN_MFMA_MAX_TILES && form) {       // matrix-core form (match_knn.h): train rows expanded to +-64 bytes in operand order, then 32 / 64 queries per wave
+    const Knn2Plan P = knn2_batch_plan(cap, nframes);
+    switch (P.form) {
+    case Knn2Form::MatrixCore: {       // match_knn.h: train rows expanded to +-64 bytes in operand order, then 64 queries per wave
         int rc;
         // ONE expand buffer per context (256 B per train row: 3 GB at 12 288 frames of 1 000 rows, never shrunk; sslam_frontend_batch counts it in its chunk estimate).
         // k_knn2_expand writes it and k_knn2_mfma reads it on the caller's stream: a call on another stream first waits for the event behind the previous reader.
         if (ctx->knnDone && ctx->knnLastStream != (void*)st) SSLAM_HIP(hipStreamWaitEvent(st, ctx->knnDone, 0));
         if (!ctx->knnDone) SSLAM_HIP(hipEventCreateWithFlags(&ctx->knnDone, hipEventDisableTiming));
-        if ((rc = ctx->knnExpand.ensure((size_t)nframes * tilesCap * 8 * 1024))) return rc;
-        { sslam::ProfScope _ps(ctx, "k_knn2_expand", st); hipLaunchKernelGGL(k_knn2_expand, dim3(tilesCap, nframes), dim3(64), 0, st, d_t, d_nt, cap, tilesCap, ctx->knnExpand.as<uint8_t>()); }
-        const int qblocks = form == 2 ? (cap + 63) / 64 : tilesCap;
-        const dim3 grid(8u * (unsigned)((nframes + 7) / 8) * (unsigned)qblocks);
-        sslam::ProfScope _ps(ctx, "k_knn2_batch", st);
-        if (form == 2) hipLaunchKernelGGL(k_knn2_mfma<2>, grid, dim3(64), 0, st, d_q, d_nq, ctx->knnExpand.as<uint8_t>(), d_nt, cap, tilesCap, qblocks, nframes, d_idx, d_dist);
-        else hipLaunchKernelGGL(k_knn2_mfma<1>, grid, dim3(64), 0, st, d_q, d_nq, ctx->knnExpand.as<uint8_t>(), d_nt, cap, tilesCap, qblocks, nframes, d_idx, d_dist);
+        if ((rc = ctx->knnExpand.ensure(P.expandBytes))) return rc;
+        { sslam::ProfScope _ps(ctx, "k_knn2_expand", st); hipLaunchKernelGGL(k_knn2_expand, dim3(P.tilesCap, nframes), dim3(64), 0, st, d_t, d_nt, cap, P.tilesCap, ctx->knnExpand.as<uint8_t>()); }
+        { sslam::ProfScope _ps(ctx, "k_knn2_batch", st);
+          hipLaunchKernelGGL(k_knn2_mfma<2>, dim3(P.grid), dim3(64), 0, st, d_q, d_nq, ctx->knnExpand.as<uint8_t>(), d_nt, cap, P.tilesCap, P.qblocks, nframes, d_idx, d_dist); }
         SSLAM_HIP(hipEventRecord(ctx->knnDone, st)); ctx->knnLastStream = (void*)st;
-    } else
-    { sslam::ProfScope _ps(ctx, "k_knn2_batch", st); hipLaunchKernelGGL(k_knn2_batch, dim3((cap + 15) / 16, nframes), dim3(256), 0, st, d_q, d_nq, d_t, d_nt, cap, d_idx, d_dist); }
+        break;
+    }
+    case Knn2Form::Popcount: {         // more than 4096 rows per frame: xor + popcount
+        sslam::ProfScope _ps(ctx, "k_knn2_batch", st);
+        hipLaunchKernelGGL(k_knn2_batch, dim3(P.grid, nframes), dim3(256), 0, st, d_q, d_nq, d_t, d_nt, cap, d_idx, d_dist);
+        break;
+    }
+    }
     SSLAM_HIP(hipGetLastError());
     return SSLAM_OK;
 }
@@ -66,14 +76,14 @@ extern "C" int sslam_hamming_knn2(sslam_ctx* ctx, const uint8_t* q, int nq, cons
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = ctx->scratch[0].ensure((size_t)nq * 32))) return rc;
-    if ((rc = ctx->scratch[1].ensure((size_t)std::max(nt, 1) * 32))) return rc;
-    if ((rc = ctx->scratch[2].ensure((size_t)nq * 16))) return rc;
+    if ((rc = ctx->scratch[SCR_KNN_Q].ensure((size_t)nq * 32))) return rc;
+    if ((rc = ctx->scratch[SCR_KNN_T].ensure((size_t)std::max(nt, 1) * 32))) return rc;
+    if ((rc = ctx->scratch[SCR_KNN_OUT].ensure((size_t)nq * 16))) return rc;
     hipStream_t st = ctx->stream;
-    SSLAM_HIP(hipMemcpyAsync(ctx->scratch[0].p, q, (size_t)nq * 32, hipMemcpyHostToDevice, st));
-    if (nt) SSLAM_HIP(hipMemcpyAsync(ctx->scratch[1].p, t, (size_t)nt * 32, hipMemcpyHostToDevice, st));
-    int* di = ctx->scratch[2].as<int>();
-    if ((rc = sslam_hamming_knn2_dev(ctx, ctx->scratch[0].as<uint8_t>(), nq, ctx->scratch[1].as<uint8_t>(), nt, di, di + (size_t)nq * 2, st))) return rc;
+    SSLAM_HIP(hipMemcpyAsync(ctx->scratch[SCR_KNN_Q].p, q, (size_t)nq * 32, hipMemcpyHostToDevice, st));
+    if (nt) SSLAM_HIP(hipMemcpyAsync(ctx->scratch[SCR_KNN_T].p, t, (size_t)nt * 32, hipMemcpyHostToDevice, st));
+    int* di = ctx->scratch[SCR_KNN_OUT].as<int>();
+    if ((rc = sslam_hamming_knn2_dev(ctx, ctx->scratch[SCR_KNN_Q].as<uint8_t>(), nq, ctx->scratch[SCR_KNN_T].as<uint8_t>(), nt, di, di + (size_t)nq * 2, st))) return rc;
     SSLAM_HIP(hipMemcpyAsync(idx, di, (size_t)nq * 8, hipMemcpyDeviceToHost, st));
     SSLAM_HIP(hipMemcpyAsync(dist, di + (size_t)nq * 2, (size_t)nq * 8, hipMemcpyDeviceToHost, st));
     SSLAM_HIP(hipStreamSynchronize(st));
@@ -86,16 +96,16 @@ extern "C" int sslam_hamming_matrix(sslam_ctx* ctx, const uint8_t* q, int nq, co
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = ctx->scratch[0].ensure((size_t)nq * 32))) return rc;
-    if ((rc = ctx->scratch[1].ensure((size_t)nt * 32))) return rc;
-    if ((rc = ctx->scratch[2].ensure((size_t)nq * nt * 2))) return rc;
+    if ((rc = ctx->scratch[SCR_KNN_Q].ensure((size_t)nq * 32))) return rc;
+    if ((rc = ctx->scratch[SCR_KNN_T].ensure((size_t)nt * 32))) return rc;
+    if ((rc = ctx->scratch[SCR_KNN_OUT].ensure((size_t)nq * nt * 2))) return rc;
     hipStream_t st = ctx->stream;
-    SSLAM_HIP(hipMemcpyAsync(ctx->scratch[0].p, q, (size_t)nq * 32, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(ctx->scratch[1].p, t, (size_t)nt * 32, hipMemcpyHostToDevice, st));
-    { sslam::ProfScope _ps(ctx, "k_hamming_matrix", st); hipLaunchKernelGGL(k_hamming_matrix, dim3((nt + 255) / 256, nq), dim3(256), 0, st, ctx->scratch[0].as<uint8_t>(), nq,
-                       ctx->scratch[1].as<uint8_t>(), nt, ctx->scratch[2].as<unsigned short>()); }
+    SSLAM_HIP(hipMemcpyAsync(ctx->scratch[SCR_KNN_Q].p, q, (size_t)nq * 32, hipMemcpyHostToDevice, st));
+    SSLAM_HIP(hipMemcpyAsync(ctx->scratch[SCR_KNN_T].p, t, (size_t)nt * 32, hipMemcpyHostToDevice, st));
+    { sslam::ProfScope _ps(ctx, "k_hamming_matrix", st); hipLaunchKernelGGL(k_hamming_matrix, dim3((nt + 255) / 256, nq), dim3(256), 0, st, ctx->scratch[SCR_KNN_Q].as<uint8_t>(), nq,
+                       ctx->scratch[SCR_KNN_T].as<uint8_t>(), nt, ctx->scratch[SCR_KNN_OUT].as<unsigned short>()); }
     SSLAM_HIP(hipGetLastError());
-    SSLAM_HIP(hipMemcpyAsync(D, ctx->scratch[2].p, (size_t)nq * nt * 2, hipMemcpyDeviceToHost, st));
+    SSLAM_HIP(hipMemcpyAsync(D, ctx->scratch[SCR_KNN_OUT].p, (size_t)nq * nt * 2, hipMemcpyDeviceToHost, st));
     SSLAM_HIP(hipStreamSynchronize(st));
     return SSLAM_OK;
 }
@@ -111,33 +121,33 @@ extern "C" int sslam_orb_search_for_initialization_batch_dev(sslam_ctx* ctx,
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);      // scratch buffers and profile records are shared state
     SSLAM_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = ctx->scratch[3].ensure(sizeof(int) * 5 * (size_t)cap * npairs))) return rc;
+    if ((rc = ctx->scratch[SCR_SFI_STATE].ensure(sizeof(int) * 5 * (size_t)cap * npairs))) return rc;
     SfiArgs A;
     A.kp1 = d_kp1; A.d1 = d_desc1; A.n1 = d_n1; A.kp2 = d_kp2; A.d2 = d_desc2; A.n2 = d_n2;
     A.cap = cap; A.n1s = 0; A.n2s = 0; A.prevMatched = d_prev; A.m12 = d_m12; A.nmatches = d_nm;
-    A.scratch = ctx->scratch[3].as<int>(); A.window = window; A.nnratio = nnratio; A.checkOri = checkOri;
-    A.minX = bounds[0]; A.maxX = bounds[1]; A.minY = bounds[2]; A.maxY = bounds[3]; A.ccap = 0;
-    // a handful of pairs (the single call of Tracking::MonocularInitialization): the LDS-resident kernel, as long as a pair fits the CU's LDS
-    const size_t ldsNeed = 64 + (size_t)cap * 15 * 4 + (size_t)cap * 2 * 4;      // per candidate 15 words (14 + the stamp of the speculative form), per F1 keypoint 2
-    const char* sfiForm = getenv("SSLAM_SFI_FORM");      // test / experiment knob: "global", "lds" (one wave), default: sixteen speculative waves
-    if (npairs <= 8 && ldsNeed <= 150 * 1024 && !(sfiForm && sfiForm[0] == 'g')) {
-        const bool oneWave = sfiForm && sfiForm[0] == 'l';
-        if (ldsNeed > 48 * 1024) SSLAM_HIP(hipFuncSetAttribute(oneWave ? (const void*)k_search_init_lds : (const void*)k_search_init_spec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsNeed));
-        sslam::ProfScope _ps(ctx, "k_search_init", pick(ctx, stream));
-        if (oneWave) hipLaunchKernelGGL(k_search_init_lds, dim3(npairs), dim3(64), ldsNeed, pick(ctx, stream), A);
-        else hipLaunchKernelGGL(k_search_init_spec, dim3(npairs), dim3(SFI_WAVES * 64), ldsNeed, pick(ctx, stream), A);
-    } else {
-        // the batch: one wave per pair with the pair's level-0 features in LDS (capacity 3/8 of the rows, at least 256: the level-0 quota of an
-        // 8-level pyramid is 21.7 % of nfeatures; a pair beyond it takes the global-memory body inside the same launch).  SSLAM_SFI_BATCH=global: the round 1-3 kernel.
-        const int ccap = std::min(cap, std::max(256, cap * 3 / 8));
-        const size_t ldsB = 64 + (size_t)ccap * 16 * 4;
-        const char* bf = getenv("SSLAM_SFI_BATCH");
-        sslam::ProfScope _ps(ctx, "k_search_init", pick(ctx, stream));
-        if (ldsB <= 64 * 1024 && !(bf && bf[0] == 'g')) {
-            A.ccap = ccap;
-            if (ldsB > 48 * 1024) SSLAM_HIP(hipFuncSetAttribute((const void*)k_search_init_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsB));
-            hipLaunchKernelGGL(k_search_init_lds, dim3(npairs), dim3(64), ldsB, pick(ctx, stream), A);
-        } else hipLaunchKernelGGL(k_search_init, dim3(npairs), dim3(64), 0, pick(ctx, stream), A);
+    A.scratch = ctx->scratch[SCR_SFI_STATE].as<int>(); A.window = window; A.nnratio = nnratio; A.checkOri = checkOri;
+    A.minX = bounds[0]; A.maxX = bounds[1]; A.minY = bounds[2]; A.maxY = bounds[3];
+    const SfiPlan P = sfi_plan(cap, npairs);      // match_plan.h: the kernel by size
+    A.ccap = P.ccap;
+    hipStream_t st = pick(ctx, stream);
+    switch (P.form) {
+    case SfiForm::Speculative: {      // a handful of pairs (the single call of Tracking::MonocularInitialization): sixteen waves per pair
+        if ((rc = allow_dynamic_lds((const void*)k_search_init_spec, P.ldsBytes))) return rc;
+        sslam::ProfScope _ps(ctx, "k_search_init", st);
+        hipLaunchKernelGGL(k_search_init_spec, dim3(npairs), dim3(SFI_WAVES * 64), P.ldsBytes, st, A);
+        break;
+    }
+    case SfiForm::LdsBatch: {         // one wave per pair, the pair's level-0 features in LDS
+        if ((rc = allow_dynamic_lds((const void*)k_search_init_lds, P.ldsBytes))) return rc;
+        sslam::ProfScope _ps(ctx, "k_search_init", st);
+        hipLaunchKernelGGL(k_search_init_lds, dim3(npairs), dim3(64), P.ldsBytes, st, A);
+        break;
+    }
+    case SfiForm::Global: {           // one wave per pair on global memory
+        sslam::ProfScope _ps(ctx, "k_search_init", st);
+        hipLaunchKernelGGL(k_search_init, dim3(npairs), dim3(64), 0, st, A);
+        break;
+    }
     }
     SSLAM_HIP(hipGetLastError());
     return SSLAM_OK;
@@ -162,10 +172,10 @@ extern "C" int sslam_orb_search_for_initialization(sslam_ctx* ctx,
     // that comes back (prev .. m12): ONE staged H2D and ONE D2H through pinned memory instead of six + three pageable copies (a pageable
     // hipMemcpyAsync costs 10-20 us of host time each, more than the kernel of a single call)
     const size_t oPrev = 2 * kb + 2 * db, oN = oPrev + 8 * (size_t)cap, oM = oN + 16, total = oM + 4 * (size_t)cap + 64;
-    if ((rc = ctx->scratch[4].ensure(total))) return rc;
-    if ((rc = ctx->pinned[2].ensure(total))) return rc;
-    uint8_t* base = ctx->scratch[4].as<uint8_t>();
-    uint8_t* H = ctx->pinned[2].as<uint8_t>();
+    if ((rc = ctx->scratch[SCR_SFI_STAGE].ensure(total))) return rc;
+    if ((rc = ctx->pinned[PIN_SFI].ensure(total))) return rc;
+    uint8_t* base = ctx->scratch[SCR_SFI_STAGE].as<uint8_t>();
+    uint8_t* H = ctx->pinned[PIN_SFI].as<uint8_t>();
     sslam_keypoint* dk1 = (sslam_keypoint*)base; sslam_keypoint* dk2 = (sslam_keypoint*)(base + kb);
     uint8_t* dd1 = base + 2 * kb; uint8_t* dd2 = dd1 + db;
     float* dpm = (float*)(base + oPrev); int* dn = (int*)(base + oN); int* dm12 = (int*)(base + oM);
@@ -211,8 +221,8 @@ extern "C" int sslam_line_match(sslam_ctx* ctx, const uint8_t* l1, int n1, const
     const int c = std::max(n1, n2);
     int rc;
     size_t total = 64 * (size_t)c + 8 * (size_t)c + 64;
-    if ((rc = ctx->scratch[5].ensure(total))) return rc;
-    uint8_t* base = ctx->scratch[5].as<uint8_t>();
+    if ((rc = ctx->scratch[SCR_LINE_MATCH].ensure(total))) return rc;
+    uint8_t* base = ctx->scratch[SCR_LINE_MATCH].as<uint8_t>();
     uint8_t* d1 = base; uint8_t* d2 = base + 32 * (size_t)c;
     int* dp = (int*)(d2 + 32 * (size_t)c); int* dn = dp + 2 * (size_t)c; double* dm = (double*)(dn + 4);
     SSLAM_HIP(hipMemcpyAsync(d1, l1, 32 * (size_t)n1, hipMemcpyHostToDevice, st));
@@ -238,50 +248,48 @@ static int search_proj_core(sslam_ctx* ctx, int kind, int mode, const void* d_fe
                             const float* d_uright, const uint8_t* occupied, const sslam_proj_query* queries, const uint8_t* qdesc, int nq,
                             float nnratio, int th_dist, int check_orientation, int32_t* assigned_out, int* nmatches_out) {
     hipStream_t st = ctx->stream;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t oO = 0, oQ = oO + al((size_t)n), oQD = oQ + al(sizeof(sslam_proj_query) * (size_t)nq), oA = oQD + al(32 * (size_t)nq), oN = oA + al(4 * (size_t)n),
-           oS = oN + 256, oT = oS + al(4 * (2 * (size_t)n + 2 * (size_t)nq)), oC = oT + al(8 * (size_t)PROJ_K * (size_t)nq), total = oC + al(4 * (size_t)nq);
+    const ProjArena L = proj_arena(n, nq, PROJ_K);
     int rc;
-    if ((rc = ctx->scratch[6].ensure(total))) return rc;
-    uint8_t* B = ctx->scratch[6].as<uint8_t>();
+    if ((rc = ctx->scratch[SCR_CALL].ensure(L.total))) return rc;
+    uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
     // occupancy, queries and query descriptors sit back to back in B: one staged H2D through pinned memory (each pageable copy costs more
     // host time than it moves data); the results (assigned, count) come back the same way
-    if ((rc = ctx->pinned[3].ensure(oN + 256))) return rc;
-    uint8_t* H = ctx->pinned[3].as<uint8_t>();
-    if (occupied) memcpy(H + oO, occupied, (size_t)n);
-    memcpy(H + oQ, queries, sizeof(sslam_proj_query) * (size_t)nq);
-    memcpy(H + oQD, qdesc, 32 * (size_t)nq);
-    SSLAM_HIP(hipMemcpyAsync(B + oO, H + oO, oA, hipMemcpyHostToDevice, st));
+    if ((rc = ctx->pinned[PIN_PROJ].ensure(L.pinnedBytes()))) return rc;
+    uint8_t* H = ctx->pinned[PIN_PROJ].as<uint8_t>();
+    if (occupied) memcpy(H + L.occ, occupied, (size_t)n);
+    memcpy(H + L.q, queries, sizeof(sslam_proj_query) * (size_t)nq);
+    memcpy(H + L.qdesc, qdesc, 32 * (size_t)nq);
+    SSLAM_HIP(hipMemcpyAsync(B + L.occ, H + L.occ, L.assigned - L.occ, hipMemcpyHostToDevice, st));
     ProjArgs A;
     A.kind = kind; A.mode = mode; A.feats = (const uint8_t*)d_feats; A.desc = d_desc; A.n = n;
     A.minX = bounds[0]; A.maxX = bounds[1]; A.minY = bounds[2]; A.maxY = bounds[3];
-    A.uright = d_uright; A.occIn = occupied ? B + oO : nullptr;
-    A.q = (const sslam_proj_query*)(B + oQ); A.qdesc = B + oQD; A.nq = nq; A.nnratio = nnratio; A.thDist = th_dist; A.checkOri = check_orientation;
-    A.assigned = (int*)(B + oA); A.nmatches = (int*)(B + oN); A.scratch = (int*)(B + oS);
-    A.stats = getenv("SSLAM_PROJ_STATS") ? (long long*)(B + oN + 64) : nullptr;      // development aid: seven counters behind the match count
-    const char* form = getenv("SSLAM_PROJ_FORM");      // test / experiment knob: "lds" (sixteen speculative waves on one CU), "wave" (one wave), default: two kernels
-    if (nq > 0 && n <= 8192 && !form) {      // one wave per query over the whole chip, then an ordered commit with parallel prefixes (match_ordered.h)
-        ProjTopArgs T; T.A = A; T.top = (unsigned long long*)(B + oT); T.cnt = (int*)(B + oC);
-        { sslam::ProfScope _ps(ctx, "k_proj_topk", st); hipLaunchKernelGGL(k_proj_topk, dim3((nq + 3) / 4), dim3(256), 0, st, T); }
-        const int featsInLds = n <= PROJ_MAXN ? 1 : 0;      // 64 bytes per feature: the re-scans of the commit then never leave the CU
-        const size_t lds = (featsInLds ? 64 : 8) * (size_t)n + 64;
-        if (lds > 48 * 1024) SSLAM_HIP(hipFuncSetAttribute((const void*)k_proj_commit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        { sslam::ProfScope _ps(ctx, "k_proj_commit", st); hipLaunchKernelGGL(k_proj_commit, dim3(1), dim3(64), lds, st, T, featsInLds); }
-    } else if (n <= PROJ_MAXN && !(form && form[0] == 'w')) {       // the frame fits in LDS: sixteen speculative queries per round
-        int n2 = 64; while (n2 < n) n2 <<= 1;
-        const size_t lds = (size_t)n * (32 + 7 * 4) + (size_t)n2 * 4 + (GRID_COLS + 2) * 4 + 64;
-        if (lds > 48 * 1024) SSLAM_HIP(hipFuncSetAttribute((const void*)k_search_proj_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        sslam::ProfScope _ps(ctx, "k_search_proj_lds", st);
-        hipLaunchKernelGGL(k_search_proj_lds, dim3(1), dim3(PROJ_WAVES * 64), lds, st, A);
-    } else { sslam::ProfScope _ps(ctx, "k_search_proj", st); hipLaunchKernelGGL(k_search_proj, dim3(1), dim3(64), 0, st, A); }
+    A.uright = d_uright; A.occIn = occupied ? B + L.occ : nullptr;
+    A.q = (const sslam_proj_query*)(B + L.q); A.qdesc = B + L.qdesc; A.nq = nq; A.nnratio = nnratio; A.thDist = th_dist; A.checkOri = check_orientation;
+    A.assigned = (int*)(B + L.assigned); A.nmatches = (int*)(B + L.count); A.scratch = (int*)(B + L.scratch);
+    A.stats = getenv("SSLAM_PROJ_STATS") ? (long long*)(B + L.stats()) : nullptr;      // development aid: seven counters behind the match count
+    const ProjPlan P = proj_plan(n, nq);
+    switch (P.form) {
+    case ProjForm::TwoKernel: {      // one wave per query over the whole chip, then an ordered commit with parallel prefixes (match_ordered.h)
+        ProjTopArgs T; T.A = A; T.top = (unsigned long long*)(B + L.top); T.cnt = (int*)(B + L.cnt);
+        { sslam::ProfScope _ps(ctx, "k_proj_topk", st); hipLaunchKernelGGL(k_proj_topk, dim3(P.topkGrid), dim3(256), 0, st, T); }
+        if ((rc = allow_dynamic_lds((const void*)k_proj_commit, P.ldsBytes))) return rc;
+        { sslam::ProfScope _ps(ctx, "k_proj_commit", st); hipLaunchKernelGGL(k_proj_commit, dim3(1), dim3(64), P.ldsBytes, st, T, P.featsInLds); }
+        break;
+    }
+    case ProjForm::OneWave: {
+        sslam::ProfScope _ps(ctx, "k_search_proj", st);
+        hipLaunchKernelGGL(k_search_proj, dim3(1), dim3(64), 0, st, A);
+        break;
+    }
+    }
     SSLAM_HIP(hipGetLastError());
-    SSLAM_HIP(hipMemcpyAsync(H + oA, B + oA, oN + 4 - oA, hipMemcpyDeviceToHost, st));
+    SSLAM_HIP(hipMemcpyAsync(H + L.assigned, B + L.assigned, L.count + 4 - L.assigned, hipMemcpyDeviceToHost, st));
     SSLAM_HIP(hipStreamSynchronize(st));
-    memcpy(assigned_out, H + oA, 4 * (size_t)n);
-    memcpy(nmatches_out, H + oN, sizeof(int));
+    memcpy(assigned_out, H + L.assigned, 4 * (size_t)n);
+    memcpy(nmatches_out, H + L.count, sizeof(int));
     if (A.stats) {
         long long hs[4];
-        SSLAM_HIP(hipMemcpy(hs, B + oN + 64, sizeof(hs), hipMemcpyDeviceToHost));
+        SSLAM_HIP(hipMemcpy(hs, B + L.stats(), sizeof(hs), hipMemcpyDeviceToHost));
         fprintf(stderr, "proj stats: commit steps %lld, re-scans %lld (%lld cycles), commit kernel %lld cycles\n", hs[0], hs[1], hs[2], hs[3]);
     }
     return SSLAM_OK;
@@ -301,11 +309,11 @@ extern "C" int sslam_search_by_projection(sslam_ctx* ctx, int kind, int mode, co
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t fsz = kind == 0 ? sizeof(sslam_keypoint) : sizeof(sslam_keyline);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t oF = 0, oD = oF + al(fsz * n), oU = oD + al(32 * (size_t)n), total = oU + al(4 * (size_t)n);
+    ArenaLayout L;
+    const size_t oF = L.take(fsz * n), oD = L.take(32 * (size_t)n), oU = L.take(4 * (size_t)n);
     int rc;
-    if ((rc = ctx->scratch[7].ensure(total))) return rc;
-    uint8_t* B = ctx->scratch[7].as<uint8_t>();
+    if ((rc = ctx->scratch[SCR_UPLOAD].ensure(L.size()))) return rc;
+    uint8_t* B = ctx->scratch[SCR_UPLOAD].as<uint8_t>();
     SSLAM_HIP(hipMemcpyAsync(B + oF, feats, fsz * n, hipMemcpyHostToDevice, st));
     SSLAM_HIP(hipMemcpyAsync(B + oD, desc, 32 * (size_t)n, hipMemcpyHostToDevice, st));
     if (uright) SSLAM_HIP(hipMemcpyAsync(B + oU, uright, 4 * (size_t)n, hipMemcpyHostToDevice, st));
@@ -402,8 +410,8 @@ extern "C" int sslam_hamming_knn2_frames(sslam_ctx* ctx, const sslam_frame* q, c
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     int rc;
-    if ((rc = ctx->scratch[6].ensure(16 * (size_t)q->n))) return rc;
-    int32_t* dI = ctx->scratch[6].as<int32_t>();
+    if ((rc = ctx->scratch[SCR_CALL].ensure(16 * (size_t)q->n))) return rc;
+    int32_t* dI = ctx->scratch[SCR_CALL].as<int32_t>();
     int32_t* dD = dI + 2 * (size_t)q->n;
     if ((rc = sslam_hamming_knn2_dev(ctx, q->desc.as<uint8_t>(), q->n, t->desc.as<uint8_t>(), t->n, dI, dD, (void*)st))) return rc;
     SSLAM_HIP(hipMemcpyAsync(idx, dI, 8 * (size_t)q->n, hipMemcpyDeviceToHost, st));
@@ -430,31 +438,26 @@ static int search_by_bow_core(sslam_ctx* ctx, const sslam_keypoint* kf_kp, const
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t ks = sizeof(sslam_keypoint);
-    size_t o[16]; size_t off = 0; int k = 0;
-    auto take = [&](size_t b) { o[k++] = off; off += al(b); };
-    take(ks * nkf); take(32 * (size_t)nkf); take((size_t)nkf); take(ks * nf); take(32 * (size_t)nf);
-    take(4 * (size_t)(nnodes + 1)); take(4 * (size_t)(nnodes + 1)); take(4 * (size_t)std::max(nk, 1)); take(4 * (size_t)std::max(nfi, 1));
-    take(4 * (size_t)nf); take(256); take(4 * (size_t)nf); take((size_t)nf);
+    const BowArena L = bow_arena(nkf, nf, nnodes, nk, nfi);
     int rc;
-    if ((rc = ctx->scratch[7].ensure(off))) return rc;
-    uint8_t* B = ctx->scratch[7].as<uint8_t>();
+    if ((rc = ctx->scratch[SCR_UPLOAD].ensure(L.total))) return rc;
+    uint8_t* B = ctx->scratch[SCR_UPLOAD].as<uint8_t>();
     // every input (and the -1 fill of the two result arrays) goes through ONE pinned staging buffer and one H2D copy: ten small pageable
     // copies cost more host time than the kernels take (0.11 ms of the call's 0.18)
     const void* src[9] = {kf_kp, kf_desc, kf_valid, f_kp, f_desc, node_kf_ptr, node_f_ptr, kf_idx, f_idx};
     const size_t len[9] = {ks * nkf, 32 * (size_t)nkf, (size_t)nkf, ks * nf, 32 * (size_t)nf, 4 * (size_t)(nnodes + 1), 4 * (size_t)(nnodes + 1), 4 * (size_t)nk, 4 * (size_t)nfi};
-    if ((rc = ctx->pinned[1].ensure(off))) return rc;
-    uint8_t* H = ctx->pinned[1].as<uint8_t>();
-    for (int i = 0; i < 9; ++i) if (len[i]) memcpy(H + o[i], src[i], len[i]);
-    memset(H + o[9], 0xFF, 4 * (size_t)nf); memset(H + o[10], 0, 256); memset(H + o[11], 0xFF, 4 * (size_t)nf);
-    if (f_valid) memcpy(H + o[12], f_valid, (size_t)nf);
-    SSLAM_HIP(hipMemcpyAsync(B, H, off, hipMemcpyHostToDevice, st));
+    if ((rc = ctx->pinned[PIN_BOW].ensure(L.total))) return rc;
+    uint8_t* H = ctx->pinned[PIN_BOW].as<uint8_t>();
+    for (int i = 0; i < 9; ++i) if (len[i]) memcpy(H + L.in[i], src[i], len[i]);
+    memset(H + L.assigned, 0xFF, 4 * (size_t)nf); memset(H + L.count, 0, 256); memset(H + L.qbin, 0xFF, 4 * (size_t)nf);
+    if (f_valid) memcpy(H + L.validF, f_valid, (size_t)nf);
+    SSLAM_HIP(hipMemcpyAsync(B, H, L.total, hipMemcpyHostToDevice, st));
     BowArgs A;
-    A.validF = f_valid ? B + o[12] : nullptr; A.strictTh = strict_th;
-    A.kpKF = (const sslam_keypoint*)(B + o[0]); A.dKF = B + o[1]; A.validKF = B + o[2]; A.kpF = (const sslam_keypoint*)(B + o[3]); A.dF = B + o[4]; A.nF = nf;
-    A.ptrKF = (const int*)(B + o[5]); A.ptrF = (const int*)(B + o[6]); A.nnodes = nnodes; A.idxKF = (const int*)(B + o[7]); A.idxF = (const int*)(B + o[8]);
-    A.nnratio = nnratio; A.checkOri = check_orientation; A.assigned = (int*)(B + o[9]); A.nmatches = (int*)(B + o[10]); A.qbin = (int*)(B + o[11]);
+    A.validF = f_valid ? B + L.validF : nullptr; A.strictTh = strict_th;
+    A.kpKF = (const sslam_keypoint*)(B + L.in[0]); A.dKF = B + L.in[1]; A.validKF = B + L.in[2]; A.kpF = (const sslam_keypoint*)(B + L.in[3]); A.dF = B + L.in[4]; A.nF = nf;
+    A.ptrKF = (const int*)(B + L.in[5]); A.ptrF = (const int*)(B + L.in[6]); A.nnodes = nnodes; A.idxKF = (const int*)(B + L.in[7]); A.idxF = (const int*)(B + L.in[8]);
+    A.nnratio = nnratio; A.checkOri = check_orientation; A.assigned = (int*)(B + L.assigned); A.nmatches = (int*)(B + L.count); A.qbin = (int*)(B + L.qbin);
     bool disjoint = true;                     // DBoW2 puts a feature under exactly one node; if a caller's lists do not, replay in order
     {
         std::vector<uint8_t> seen((size_t)nf, 0);
@@ -466,10 +469,10 @@ static int search_by_bow_core(sslam_ctx* ctx, const sslam_keypoint* kf_kp, const
     // all: 0.235 ms -- two nodes per wave in series instead of one workgroup per node)
     { sslam::ProfScope _ps(ctx, "k_bow_finish", st); hipLaunchKernelGGL(k_bow_finish, dim3(1), dim3(256), 0, st, A.assigned, A.qbin, nf, check_orientation, A.nmatches); }
     SSLAM_HIP(hipGetLastError());
-    SSLAM_HIP(hipMemcpyAsync(H + o[9], B + o[9], o[10] + 4 - o[9], hipMemcpyDeviceToHost, st));      // assigned + the count, back through the same staging
+    SSLAM_HIP(hipMemcpyAsync(H + L.assigned, B + L.assigned, L.count + 4 - L.assigned, hipMemcpyDeviceToHost, st));      // assigned + the count, back through the same staging
     SSLAM_HIP(hipStreamSynchronize(st));
-    memcpy(assigned_out, H + o[9], 4 * (size_t)nf);
-    memcpy(nmatches_out, H + o[10], sizeof(int));
+    memcpy(assigned_out, H + L.assigned, 4 * (size_t)nf);
+    memcpy(nmatches_out, H + L.count, sizeof(int));
     return SSLAM_OK;
 }
 
@@ -515,11 +518,11 @@ extern "C" int sslam_distinctive_descriptors(sslam_ctx* ctx, const uint8_t* desc
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t oD = 0, oP = oD + al(32 * (size_t)std::max(total, 1)), oB = oP + al(4 * (size_t)(nsets + 1)), tot = oB + al(4 * (size_t)nsets);
+    ArenaLayout L;
+    const size_t oD = L.take(32 * (size_t)std::max(total, 1)), oP = L.take(4 * (size_t)(nsets + 1)), oB = L.take(4 * (size_t)nsets);
     int rc;
-    if ((rc = ctx->scratch[6].ensure(tot))) return rc;
-    uint8_t* B = ctx->scratch[6].as<uint8_t>();
+    if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
+    uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
     if (total > 0) SSLAM_HIP(hipMemcpyAsync(B + oD, desc, 32 * (size_t)total, hipMemcpyHostToDevice, st));
     SSLAM_HIP(hipMemcpyAsync(B + oP, ptr, 4 * (size_t)(nsets + 1), hipMemcpyHostToDevice, st));
     { sslam::ProfScope _ps(ctx, "k_distinctive", st); hipLaunchKernelGGL(k_distinctive, dim3(std::min(nsets, 4096)), dim3(64), 0, st, B + oD, (const int32_t*)(B + oP), nsets, (int32_t*)(B + oB)); }
@@ -544,12 +547,11 @@ extern "C" int sslam_fuse_search(sslam_ctx* ctx, const sslam_frame* kf, int chi2
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t oQ = 0, oQD = oQ + al(sizeof(sslam_proj_query) * (size_t)nq), oS = oQD + al(32 * (size_t)nq), oI = oS + 256, oD = oI + al(4 * (size_t)nq),
-                 total = oD + al(4 * (size_t)nq);
+    ArenaLayout L;
+    const size_t oQ = L.take(sizeof(sslam_proj_query) * (size_t)nq), oQD = L.take(32 * (size_t)nq), oS = L.take(256), oI = L.take(4 * (size_t)nq), oD = L.take(4 * (size_t)nq);
     int rc;
-    if ((rc = ctx->scratch[6].ensure(total))) return rc;
-    uint8_t* B = ctx->scratch[6].as<uint8_t>();
+    if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
+    uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
     SSLAM_HIP(hipMemcpyAsync(B + oQ, queries, sizeof(sslam_proj_query) * (size_t)nq, hipMemcpyHostToDevice, st));
     SSLAM_HIP(hipMemcpyAsync(B + oQD, qdesc, 32 * (size_t)nq, hipMemcpyHostToDevice, st));
     if (chi2_mode) SSLAM_HIP(hipMemcpyAsync(B + oS, inv_level_sigma2, sizeof(float) * (size_t)nlevels, hipMemcpyHostToDevice, st));
@@ -590,15 +592,13 @@ extern "C" int sslam_orb_search_for_triangulation(sslam_ctx* ctx, const sslam_fr
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-    const size_t oF1 = take(n1), oF2 = take(n2), oP1 = take(4 * (size_t)(nnodes + 1)), oP2 = take(4 * (size_t)(nnodes + 1)), oI1 = take(4 * (size_t)total1),
-                 oI2 = take(4 * (size_t)total2), oNO = take(4 * (size_t)total1), oSF = take(4 * (size_t)nlevels), oSG = take(4 * (size_t)nlevels),
-                 oM = take(4 * (size_t)n1), oQB = take(4 * (size_t)n1), oN = take(4);
+    ArenaLayout L;
+    const size_t oF1 = L.take(n1), oF2 = L.take(n2), oP1 = L.take(4 * (size_t)(nnodes + 1)), oP2 = L.take(4 * (size_t)(nnodes + 1)), oI1 = L.take(4 * (size_t)total1),
+                 oI2 = L.take(4 * (size_t)total2), oNO = L.take(4 * (size_t)total1), oSF = L.take(4 * (size_t)nlevels), oSG = L.take(4 * (size_t)nlevels),
+                 oM = L.take(4 * (size_t)n1), oQB = L.take(4 * (size_t)n1), oN = L.take(4);
     int rc;
-    if ((rc = ctx->scratch[6].ensure(off))) return rc;
-    uint8_t* B = ctx->scratch[6].as<uint8_t>();
+    if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
+    uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
     SSLAM_HIP(hipMemcpyAsync(B + oF1, free1, n1, hipMemcpyHostToDevice, st));
     SSLAM_HIP(hipMemcpyAsync(B + oF2, free2, n2, hipMemcpyHostToDevice, st));
     SSLAM_HIP(hipMemcpyAsync(B + oP1, node_kf1_ptr, 4 * (size_t)(nnodes + 1), hipMemcpyHostToDevice, st));
@@ -664,11 +664,11 @@ extern "C" void sslam_vocab_destroy(sslam_vocab* v) {
 
 static int bow_core(sslam_ctx* ctx, const sslam_vocab* v, const uint8_t* d_desc, int n, int levelsup, int32_t* word_out, double* weight_out, int32_t* node_out) {
     hipStream_t st = ctx->stream;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t oW = 0, oV = oW + al(4 * (size_t)n), oN = oV + al(8 * (size_t)n), total = oN + al(4 * (size_t)n);
+    ArenaLayout L;
+    const size_t oW = L.take(4 * (size_t)n), oV = L.take(8 * (size_t)n), oN = L.take(4 * (size_t)n);
     int rc;
-    if ((rc = ctx->scratch[6].ensure(total))) return rc;
-    uint8_t* B = ctx->scratch[6].as<uint8_t>();
+    if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
+    uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
     { sslam::ProfScope _ps(ctx, "k_bow_transform", st);
       hipLaunchKernelGGL(k_bow_transform, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, n, v->childPtr.as<int>(), v->children.as<int>(), v->desc.as<uint8_t>(),
                          v->wordId.as<int>(), v->weight.as<double>(), v->levels - levelsup, (int*)(B + oW), (double*)(B + oV), (int*)(B + oN)); }
@@ -700,7 +700,7 @@ extern "C" int sslam_bow_transform(sslam_ctx* ctx, const sslam_vocab* vocab, con
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = ctx->scratch[7].ensure(32 * (size_t)n))) return rc;
-    SSLAM_HIP(hipMemcpyAsync(ctx->scratch[7].p, desc, 32 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    return bow_core(ctx, vocab, ctx->scratch[7].as<uint8_t>(), n, levelsup, word_out, weight_out, node_out);
+    if ((rc = ctx->scratch[SCR_UPLOAD].ensure(32 * (size_t)n))) return rc;
+    SSLAM_HIP(hipMemcpyAsync(ctx->scratch[SCR_UPLOAD].p, desc, 32 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    return bow_core(ctx, vocab, ctx->scratch[SCR_UPLOAD].as<uint8_t>(), n, levelsup, word_out, weight_out, node_out);
 }

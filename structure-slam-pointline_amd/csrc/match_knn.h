@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void k_knn2_batch(const uint8_t* __restrict__ 
 // The dense best / second-best search of a frame pair is 10^6 descriptor pairs; as xor + popcount it is 20 vector instructions per pair
 // and lane (k_knn2_batch: 0.43 M wave-instructions per frame, 6 % of a step that is bound by vector issue, docs/history/DESIGN_rounds_1-4.md 5f).  The same
 // distances as a product of +-64 matrices (int8): sum_k a_k b_k = 4096 (256 - 2 h), h the Hamming distance -- exact in the i32
-// accumulator of v_mfma_i32_32x32x32_i8.  One wave holds 32 (or 64) queries as the B operand (column j = lane & 31; 8 k-steps x 16 bytes
+// accumulator of v_mfma_i32_32x32x32_i8.  One wave holds 64 queries (two sets of 32) as the B operand (column j = lane & 31; 8 k-steps x 16 bytes
 // per lane, expanded once from the 256 bits) and streams the train rows through the A operand in tiles of 32; each lane then owns ONE
 // query and 16 train rows per tile (C/D layout: row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)), so best and second-best are a per-lane
 // running max / min over keys -- a handful of vector instructions per pair instead of 20, and the multiply-adds run on an otherwise
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void k_knn2_batch(const uint8_t* __restrict__ 
 // k_knn2_expand writes the train side in operand order: frame f, tile T, k-step s = 64 lanes x 16 bytes, contiguous.
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-constexpr int KNN_MFMA_MAX_TILES = 128;
+// KNN_MFMA_MAX_TILES = 128 (match_plan.h, with the launch rule): the 7 tile bits of the key above
 __device__ __forceinline__ unsigned spread4(unsigned n) { return __umul24(n, 0x00204081u) & 0x01010101u; }      // bit i of a nibble -> byte i (0 / 1)
 __device__ __forceinline__ int pm64(unsigned nibble) { const unsigned m = spread4(nibble); return (int)((m << 7) ^ 0xC0C0C0C0u); }      // bit 1 -> +64 (0x40), bit 0 -> -64 (0xC0)
 
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(64) void k_knn2_expand(const uint8_t* __restrict__ 
     }
 }
 
-// QS = query sets of 32 per wave: 2 halves the passes over the frame's train rows (the kernel's L2 traffic)
+// QS = query sets of 32 per wave: 2 halves the passes over the frame's train rows (the kernel's L2 traffic) and is the only instantiation
 template <int QS>
 __global__ __launch_bounds__(64) void k_knn2_mfma(const uint8_t* __restrict__ q, const int* __restrict__ nq, const uint8_t* __restrict__ texp,
                                                   const int* __restrict__ nt, int cap, int tilesCap, int qblocks, int nframes,

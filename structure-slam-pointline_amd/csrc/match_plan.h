@@ -1,0 +1,128 @@
+// Host-side plans of the matcher entry points (match.hip): which kernel a call launches for its sizes, the sizes that follow from
+// that choice (LDS bytes, capacities, grid), and how a staged call lays out its scratch arena.  Pure functions of integers and no HIP
+// in here: tests/sim/match_plan_dump.cpp compiles this header with a plain host compiler and tests/test_match_plan_cpu.py checks both
+// sides of every boundary.  A size rule lives here and nowhere else; the kernels are chosen by arguments alone (no environment).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include "../../include/sslam_frontend.h"
+
+namespace sslam {
+
+// -------------------------------------------------------------- scratch arena of one call
+// take(bytes) hands out the next 256-aligned offset, size() is the total so far: the one layout rule of every staged entry point
+struct ArenaLayout {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+    size_t size() const { return off; }
+};
+
+// -------------------------------------------------------------- knn-2 of a batch (sslam_hamming_knn2_batch_dev)
+// k_knn2_mfma packs the train tile into 7 bits of its reduction key: 128 tiles of 32 rows, 4096 rows per frame; beyond that xor + popcount
+constexpr int KNN_MFMA_MAX_TILES = 128;
+enum class Knn2Form { MatrixCore, Popcount };
+struct Knn2Plan {
+    Knn2Form form;
+    int tilesCap;             // train tiles of 32 rows per frame
+    int qblocks;              // MatrixCore: blocks of 64 queries per frame (k_knn2_mfma<2>)
+    unsigned grid;            // MatrixCore: workgroups of k_knn2_mfma; Popcount: grid.x of k_knn2_batch (grid.y = nframes)
+    size_t expandBytes;       // MatrixCore: the train rows as int8 operands, 256 B per row
+};
+inline Knn2Plan knn2_batch_plan(int cap, int nframes) {
+    Knn2Plan P{};
+    P.tilesCap = (cap + 31) / 32;
+    if (P.tilesCap <= KNN_MFMA_MAX_TILES) {
+        P.form = Knn2Form::MatrixCore;
+        P.qblocks = (cap + 63) / 64;
+        P.grid = 8u * (unsigned)((nframes + 7) / 8) * (unsigned)P.qblocks;
+        P.expandBytes = (size_t)nframes * P.tilesCap * 8 * 1024;
+    } else {
+        P.form = Knn2Form::Popcount;
+        P.grid = (unsigned)((cap + 15) / 16);
+    }
+    return P;
+}
+
+// -------------------------------------------------------------- SearchForInitialization (sslam_orb_search_for_initialization_batch_dev)
+//   Speculative  a handful of pairs (the single call of Tracking::MonocularInitialization) whose rows fit one compute unit's LDS: sixteen waves
+//                per pair, per candidate 15 words (14 + the stamp) and per F1 keypoint 2 -- k_search_init_spec
+//   LdsBatch     one wave per pair with the pair's LEVEL-0 features in LDS: capacity 3/8 of the rows and at least 256 (the level-0 quota of an
+//                8-level pyramid is 21.7 % of nfeatures), 16 words each; a pair beyond it takes the global-memory body inside the same launch
+//                -- k_search_init_lds
+//   Global       rows so long that even that capacity passes 64 KB: one wave per pair on global memory -- k_search_init
+enum class SfiForm { Speculative, LdsBatch, Global };
+struct SfiPlan {
+    SfiForm form;
+    size_t ldsBytes;          // dynamic LDS of the launch (0: Global)
+    int ccap;                 // LdsBatch: LDS capacity in level-0 features (SfiArgs::ccap); 0 otherwise
+};
+inline SfiPlan sfi_plan(int cap, int npairs) {
+    const size_t ldsSpec = 64 + (size_t)cap * 17 * 4;
+    if (npairs <= 8 && ldsSpec <= 150 * 1024) return {SfiForm::Speculative, ldsSpec, 0};
+    const int ccap = std::min(cap, std::max(256, cap * 3 / 8));
+    const size_t ldsBatch = 64 + (size_t)ccap * 16 * 4;
+    if (ldsBatch <= 64 * 1024) return {SfiForm::LdsBatch, ldsBatch, ccap};
+    return {SfiForm::Global, 0, 0};
+}
+
+// -------------------------------------------------------------- projection-window matchers (search_proj_core)
+//   TwoKernel  k_proj_topk (one wave per query over the whole chip) + k_proj_commit (one wave, ordered commit); up to PROJ_MAXN features the
+//              commit keeps the frame in LDS (64 bytes per feature: its re-scans then never leave the compute unit), beyond that only
+//              occupancy and stamps (8 bytes per feature)
+//   OneWave    more than 8192 features: k_search_proj
+constexpr int PROJ_MAXN = 2048;
+constexpr int PROJ_TWO_KERNEL_MAXN = 8192;
+enum class ProjForm { TwoKernel, OneWave };
+struct ProjPlan {
+    ProjForm form;
+    int featsInLds;           // TwoKernel: k_proj_commit copies the frame's features into LDS
+    size_t ldsBytes;          // TwoKernel: dynamic LDS of k_proj_commit
+    unsigned topkGrid;        // TwoKernel: workgroups of k_proj_topk (four queries each)
+};
+inline ProjPlan proj_plan(int n, int nq) {
+    if (n > PROJ_TWO_KERNEL_MAXN) return {ProjForm::OneWave, 0, 0, 0};
+    const int featsInLds = n <= PROJ_MAXN ? 1 : 0;
+    return {ProjForm::TwoKernel, featsInLds, (size_t)(featsInLds ? 64 : 8) * (size_t)n + 64, (unsigned)((nq + 3) / 4)};
+}
+
+// arena of search_proj_core.  occ | q | qdesc go up in ONE copy (occ .. assigned), assigned | count come back in one (assigned .. count + 4);
+// only that head (.. count + 256) has a pinned mirror.  projK = list length of k_proj_topk (PROJ_K).
+struct ProjArena {
+    size_t occ, q, qdesc, assigned, count, scratch, top, cnt, total;
+    size_t stats() const { return count + 64; }          // SSLAM_PROJ_STATS: counters behind the match count, inside its 256 bytes
+    size_t pinnedBytes() const { return count + 256; }
+};
+inline ProjArena proj_arena(int n, int nq, int projK) {
+    ArenaLayout L; ProjArena a;
+    a.occ = L.take((size_t)n);
+    a.q = L.take(sizeof(sslam_proj_query) * (size_t)nq);
+    a.qdesc = L.take(32 * (size_t)nq);
+    a.assigned = L.take(4 * (size_t)n);
+    a.count = L.take(256);
+    a.scratch = L.take(4 * (2 * (size_t)n + 2 * (size_t)nq));      // ProjArgs::scratch: occ[n], key[n], qbin[nq], qidx[nq]
+    a.top = L.take(8 * (size_t)projK * (size_t)nq);
+    a.cnt = L.take(4 * (size_t)nq);
+    a.total = L.size();
+    return a;
+}
+
+// arena of search_by_bow_core: the nine inputs, then assigned | count | qbin | validF; everything goes up in one copy, assigned .. count + 4 comes back
+struct BowArena {
+    size_t in[9];             // kpKF, dKF, validKF, kpF, dF, ptrKF, ptrF, idxKF, idxF
+    size_t assigned, count, qbin, validF, total;
+};
+inline BowArena bow_arena(int nkf, int nf, int nnodes, int nk, int nfi) {
+    const size_t ks = sizeof(sslam_keypoint);
+    ArenaLayout L; BowArena a;
+    const size_t len[9] = {ks * nkf, 32 * (size_t)nkf, (size_t)nkf, ks * nf, 32 * (size_t)nf, 4 * (size_t)(nnodes + 1), 4 * (size_t)(nnodes + 1),
+                           4 * (size_t)std::max(nk, 1), 4 * (size_t)std::max(nfi, 1)};
+    for (int i = 0; i < 9; ++i) a.in[i] = L.take(len[i]);
+    a.assigned = L.take(4 * (size_t)nf);
+    a.count = L.take(256);
+    a.qbin = L.take(4 * (size_t)nf);
+    a.validF = L.take((size_t)nf);
+    a.total = L.size();
+    return a;
+}
+
+}  // namespace sslam

@@ -70,13 +70,12 @@ def test_knn2_batch_dev_matrix_core_form(fe, ctx, oracle, cap):
         assert (idx[f, a:] == -7).all()          # rows past the frame's queries are not written
 
 
-@pytest.mark.parametrize("cap,knob", [(4200, None), (1000, "popc"), (96, "mfma1")])
-def test_knn2_batch_dev_other_forms(fe, ctx, oracle, cap, knob, monkeypatch):
-    """the xor + popcount form (the only one beyond 4096 rows per frame; SSLAM_KNN2_BATCH=popc forces it below) and the 32-queries-per-wave matrix-core form
-    (mfma1) against the oracle -- the knob is read on every call since round 5, so one process can compare the forms"""
+@pytest.mark.parametrize("cap", [4200, 1000, 96])
+def test_knn2_batch_dev_other_forms(fe, ctx, oracle, cap):
+    """the xor + popcount form (beyond 4096 rows per frame: cap 4200) and the matrix-core form (k_knn2_mfma<2>: cap 1000, 96) against the oracle, each
+    with a second call on a second stream"""
     import ctypes as C
     import torch
-    if knob: monkeypatch.setenv("SSLAM_KNN2_BATCH", knob)
     rng = np.random.default_rng(cap + 1)
     counts = [(cap, cap), (37, cap), (cap, 2), (0, 9), (65, 64)]
     B = len(counts)
@@ -131,16 +130,8 @@ def test_search_for_initialization(fe, ctx, oracle, seed, nfeat, ori):
     np.testing.assert_array_equal(pmo, opm)
 
 
-@pytest.mark.parametrize("form", ["spec", "lds", "global"])
-@pytest.mark.parametrize("seed", [3, 4])
-def test_search_for_initialization_contention(fe, ctx, oracle, form, seed, monkeypatch):
-    """The single call has three kernels (csrc/match_ordered.h: sixteen speculative waves -- the default --, one wave in LDS, one wave on global
-    memory).  Contended input: every F2 keypoint is wanted by several F1 keypoints in a row (near-duplicate descriptors at nearly the same
-    place), so that matches are taken over by later, closer keypoints (the un-match path) and keypoints of one speculative round collide on
-    their best / second-best candidate (the serial replay with re-evaluation).  All three forms must equal the oracle's restatement of
-    src/ORBmatcher.cc:408-523."""
-    if form != "spec": monkeypatch.setenv("SSLAM_SFI_FORM", form)
-    rng = np.random.default_rng(seed)
+def _sfi_contended_pair(fe, rng):
+    """every F2 keypoint is wanted by several F1 keypoints in a row (near-duplicate descriptors at nearly the same place)"""
     n2 = 260
     kp2 = np.zeros(n2, fe.KP_DTYPE)
     kp2["x"] = rng.uniform(20, 620, n2).astype(np.float32); kp2["y"] = rng.uniform(20, 460, n2).astype(np.float32)
@@ -155,21 +146,102 @@ def test_search_for_initialization_contention(fe, ctx, oracle, form, seed, monke
     d1 = d2[src].copy()
     for i in range(n1):                                                            # 0..24 flipped bits: ties, takeovers and ratio-test failures
         for b in rng.integers(0, 256, int(rng.integers(0, 25))): d1[i, b >> 3] ^= np.uint8(1 << (b & 7))
-    pm = np.stack([kp1["x"], kp1["y"]], axis=1).astype(np.float32)
-    m12, pmo, n = ctx.search_for_initialization(kp1, d1, kp2, d2, pm, 100, 0.9, True)
-    om12, opm, on = oracle.search_for_initialization(kp1, d1, kp2, d2, pm, 100, 0.9, True)
-    assert on > 50 and n == on
-    np.testing.assert_array_equal(m12, om12)
-    np.testing.assert_array_equal(pmo, opm)
+    return kp1, d1, kp2, d2
 
 
-@pytest.mark.parametrize("form", ["lds", "global"])
-def test_search_for_initialization_batch_forms(fe, ctx, oracle, form, monkeypatch):
+_SFI_CONTENDED = {}
+
+
+def _sfi_contended_batch(fe, oracle, seed):
+    """nine pairs for the batch entry point -- the pair of the single call first, seven more from other seeds, one empty -- and the oracle's
+    answer for each (computed once per seed, shared by the paths)"""
+    if seed not in _SFI_CONTENDED:
+        pairs = [None if p == 4 else _sfi_contended_pair(fe, np.random.default_rng(seed if p == 0 else seed * 100 + p)) for p in range(9)]
+        want = []
+        for pr in pairs:
+            if pr is None: want.append(None); continue
+            kp1, d1, kp2, d2 = pr
+            want.append(oracle.search_for_initialization(kp1, d1, kp2, d2, np.stack([kp1["x"], kp1["y"]], axis=1).astype(np.float32), 100, 0.9, True))
+        _SFI_CONTENDED[seed] = (pairs, want)
+    return _SFI_CONTENDED[seed]
+
+
+SFI_BATCH_CAP = {"lds": 2700, "global": 2800}          # rows per frame of the nine-pair call that reaches k_search_init_lds / k_search_init
+
+
+@pytest.mark.parametrize("form", ["spec", "lds", "global"])
+@pytest.mark.parametrize("seed", [3, 4])
+def test_search_for_initialization_contention(fe, ctx, oracle, form, seed):
+    """SearchForInitialization has three kernels (csrc/match_ordered.h), chosen by size (csrc/match_plan.h): sixteen speculative waves per pair for
+    the single call (k_search_init_spec), one wave per pair with the level-0 features in LDS (k_search_init_lds) and one wave per pair on global
+    memory (k_search_init) for batches of more than eight pairs, by row capacity.  Contended input: every F2 keypoint is wanted by several F1
+    keypoints in a row (near-duplicate descriptors at nearly the same place), so that matches are taken over by later, closer keypoints (the
+    un-match path) and keypoints of one speculative round collide on their best / second-best candidate (the serial replay with
+    re-evaluation).  All three must equal the oracle's restatement of src/ORBmatcher.cc:408-523: the single call, and nine pairs through
+    sslam_orb_search_for_initialization_batch_dev at a capacity whose LDS form holds the contended pairs (2700 rows: 1012 level-0 features)
+    and at one beyond its 64 KB (2800 rows)."""
+    pairs, want = _sfi_contended_batch(fe, oracle, seed)
+    if form == "spec":
+        kp1, d1, kp2, d2 = pairs[0]
+        assert 64 + max(len(kp1), len(kp2)) * 17 * 4 <= 150 * 1024                   # the speculative kernel (one pair, rows fit 150 KB of LDS)
+        pm = np.stack([kp1["x"], kp1["y"]], axis=1).astype(np.float32)
+        m12, pmo, n = ctx.search_for_initialization(kp1, d1, kp2, d2, pm, 100, 0.9, True)
+        om12, opm, on = want[0]
+        assert on > 50 and n == on
+        np.testing.assert_array_equal(m12, om12)
+        np.testing.assert_array_equal(pmo, opm)
+        return
+    import ctypes as C, torch
+    P, cap = len(pairs), SFI_BATCH_CAP[form]
+    ccap = min(cap, max(256, cap * 3 // 8))                                         # the plan rule, restated: more than eight pairs, then by LDS bytes
+    assert P > 8
+    if form == "lds":
+        assert 64 + ccap * 64 <= 64 * 1024
+        for pr in pairs:
+            if pr is not None: assert (pr[0]["octave"] == 0).sum() <= ccap and (pr[2]["octave"] == 0).sum() <= ccap      # the LDS body, not its in-launch fallback
+    else:
+        assert 64 + ccap * 64 > 64 * 1024
+    rng = np.random.default_rng(seed + cap)
+    kp1 = rng.integers(0, 256, (P, cap, fe.KP_DTYPE.itemsize), dtype=np.uint8).view(fe.KP_DTYPE).reshape(P, cap)      # junk past the counts
+    kp2 = rng.integers(0, 256, (P, cap, fe.KP_DTYPE.itemsize), dtype=np.uint8).view(fe.KP_DTYPE).reshape(P, cap)
+    d1 = rng.integers(0, 256, (P, cap, 32), dtype=np.uint8); d2 = rng.integers(0, 256, (P, cap, 32), dtype=np.uint8)
+    pm = rng.uniform(-1000, 1000, (P, cap, 2)).astype(np.float32)
+    n1 = np.zeros(P, np.int32); n2 = np.zeros(P, np.int32)
+    for p, pr in enumerate(pairs):
+        if pr is None: continue
+        a, b = len(pr[0]), len(pr[2])
+        kp1[p, :a], d1[p, :a], kp2[p, :b], d2[p, :b] = pr
+        pm[p, :a, 0] = pr[0]["x"]; pm[p, :a, 1] = pr[0]["y"]
+        n1[p], n2[p] = a, b
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    g = dict(kp1=t(kp1.view(np.uint8)), d1=t(d1), n1=t(n1), kp2=t(kp2.view(np.uint8)), d2=t(d2), n2=t(n2), pm=t(pm))
+    m12 = torch.full((P, cap), -7, dtype=torch.int32, device="cuda"); nm = torch.full((P,), -7, dtype=torch.int32, device="cuda")
+    _p = lambda x: C.c_void_p(x.data_ptr())
+    bounds = (C.c_float * 4)(0.0, 640.0, 0.0, 480.0)
+    torch.cuda.synchronize()
+    rc = fe.lib().sslam_orb_search_for_initialization_batch_dev(ctx.h, _p(g["kp1"]), _p(g["d1"]), _p(g["n1"]), _p(g["kp2"]), _p(g["d2"]), _p(g["n2"]), cap, P, _p(g["pm"]), _p(m12), _p(nm),
+                                                                100, C.c_float(0.9), 1, bounds, C.c_void_p(0))
+    assert rc == 0, fe.lib().sslam_last_error()
+    ctx.synchronize()
+    m12 = m12.cpu().numpy(); nm = nm.cpu().numpy(); pmo = g["pm"].cpu().numpy()
+    for p, pr in enumerate(pairs):
+        if pr is None:
+            assert nm[p] == 0
+            continue
+        a = len(pr[0])
+        om12, opm, on = want[p]
+        assert on > 50 and nm[p] == on, (p, nm[p], on)
+        np.testing.assert_array_equal(m12[p, :a], om12, err_msg="pair %d" % p)
+        np.testing.assert_array_equal(pmo[p, :a], opm, err_msg="pair %d" % p)
+
+
+@pytest.mark.parametrize("form", ["lds"])
+def test_search_for_initialization_batch_forms(fe, ctx, oracle, form):
     """sslam_orb_search_for_initialization_batch_dev, more than eight pairs per call: one wave per pair with the pair's level-0 features staged
     in LDS (round 4; capacity 3/8 of the rows), pairs with more level-0 features than that falling back to the global-memory body inside the
-    same launch, and the global-memory kernel of rounds 1-3 (SSLAM_SFI_BATCH=global).  Every pair against the oracle."""
+    same launch (the one case, "lds", keeps the name it had beside a knob-forced "global" case).  Every pair against the oracle.  (The global-memory kernel of longer rows: test_match_sizes_gpu.py::test_sfi_batch_by_cap[2800],
+    and on contended pairs test_search_for_initialization_contention[*-global].)"""
     import ctypes as C, torch
-    if form == "global": monkeypatch.setenv("SSLAM_SFI_BATCH", "global")
     rng = np.random.default_rng(99)
     P, cap = 13, 700
     kp1 = np.zeros((P, cap), fe.KP_DTYPE); kp2 = np.zeros((P, cap), fe.KP_DTYPE)
@@ -264,15 +336,14 @@ def test_orb_search_by_projection(fe, ctx, oracle, mode, seed):
         np.testing.assert_array_equal(a, oa)
 
 
-@pytest.mark.parametrize("form", ["two-kernel", "lds", "wave"])
 @pytest.mark.parametrize("mode", [0, 1])
-def test_orb_search_by_projection_contention(fe, ctx, oracle, form, mode, monkeypatch):
-    """The window matcher has three device forms (csrc/match_ordered.h: per-query top-4 lists + ordered commit with parallel prefixes -- the
-    default --, sixteen speculative waves in LDS, one wave).  Contended input: every query is repeated several times in a row with small
-    jitter (so that consecutive queries want the same keypoint, lists run dry and the commit has to re-scan), a third of the map points has
-    no observations (takes a keypoint without blocking it), a fifth of the keypoints is occupied from the start.  All forms must equal the
-    oracle's restatement of src/ORBmatcher.cc:45-129 / :1331-1473."""
-    if form != "two-kernel": monkeypatch.setenv("SSLAM_PROJ_FORM", form)
+def test_orb_search_by_projection_contention(fe, ctx, oracle, mode):
+    """The window matcher of a frame of up to 8192 features (csrc/match_ordered.h: per-query top-8 lists + ordered commit with parallel
+    prefixes).  Contended input: every query is repeated several times in a row with small jitter (so that consecutive queries want the same
+    keypoint, lists run dry and the commit has to re-scan), a third of the map points has no observations (takes a keypoint without blocking
+    it), a fifth of the keypoints is occupied from the start.  Must equal the oracle's restatement of src/ORBmatcher.cc:45-129 / :1331-1473.
+    The one-wave kernel of larger frames (k_search_proj) meets contended input -- dry lists, initial occupancy, obs_positive = 0, valid = 0,
+    both modes -- in test_match_sizes_gpu.py::test_proj_clusters[8200-*]."""
     rng = np.random.default_rng(77 + mode)
     cur = synth_frame(1234); prev = warp_prev(cur)
     kp1, d1 = oracle.orb_extract(prev, 500); kp2, d2 = oracle.orb_extract(cur, 1000)
