@@ -232,6 +232,32 @@ int sslam_frame_count(const sslam_frame* frame);
 int sslam_search_by_projection_frame(sslam_ctx* ctx, const sslam_frame* frame, int mode, const uint8_t* occupied,
                                      const sslam_proj_query* queries, const uint8_t* qdesc, int nq,
                                      float nnratio, int th_dist, int check_orientation, int32_t* assigned_out, int* nmatches_out);
+/* sslam_search_by_projection for `nframes` independent frames whose features are already on the device, asynchronously: the batch form of the
+ * matcher a tracker runs on every frame after initialisation (TrackWithMotionModel, SearchLocalPoints and the LSDmatcher twins), for callers that
+ * extract many sessions' frames in one launch.  The layout is the batch extractors': frame f owns rows [f*cap, f*cap + d_n[f]) of d_feats
+ * (kind 0: sslam_keypoint, kind 1: sslam_keyline), d_desc (32 bytes per row) and, where given, d_uright and d_occupied (NULL: as in the single
+ * call), so the outputs of sslam_orb_extract_batch_dev / sslam_undistort_keypoints_batch_dev / sslam_lines_extract_batch_dev are inputs here
+ * without a copy; it owns rows [f*qcap, f*qcap + d_nq[f]) of d_queries and d_qdesc.  A count below 0 is read as 0, one above its capacity as
+ * the capacity.  kind, mode, bounds, nnratio, th_dist and check_orientation are shared by all frames and mean what they mean in the single call.
+ * d_assigned[f*cap + i], i < n[f], receives what sslam_search_by_projection writes to assigned_out[i] for that frame (query index, -1, or -2
+ * after the rotation check); rows at or past a frame's count are not touched.  d_nmatches[f] = the frame's match count (0 for a frame without
+ * features or without queries, whose valid rows are still set to -1).
+ * Every pointer is a device pointer except bounds; d_desc and d_qdesc are 16-byte aligned.  The call enqueues on `stream` (NULL: the context's
+ * stream) and returns without synchronising; it reads no host memory but bounds and writes none.  SSLAM_ERR_INVALID (nothing enqueued): the
+ * single call's rules (kind / mode 0 or 1, no kind 1 with mode 1 and check_orientation, cap < 2^19), a negative cap, qcap or nframes, a NULL or
+ * misaligned buffer.  nframes == 0 is SSLAM_OK and enqueues nothing.
+ * Scratch: the context owns one arena for this call, apart from the synchronous matchers' (a synchronous matcher may run on the context stream
+ * while a batch runs on another).  The batch runs in slices of frames, in stream order, so the arena does not grow with nframes: per frame of a
+ * slice 8*(cap + qcap) + 68*qcap bytes (the per-query top-8 lists and counts, the per-frame rotation bins), at most 256 MiB (+ 768 bytes of
+ * alignment) per context in all, or one frame's worth where a single frame needs more.  Calls on different streams of one context are ordered
+ * on the arena by an event (the later call's kernels wait for the earlier call's); a call that needs a larger arena than the context holds
+ * waits on the host for the previous call before it replaces it -- the only case in which the call blocks. */
+int sslam_search_by_projection_batch_dev(sslam_ctx* ctx, int kind, int mode,
+                                         const void* d_feats, const uint8_t* d_desc, const int32_t* d_n, int cap, int nframes, const float bounds[4],
+                                         const float* d_uright, const uint8_t* d_occupied,
+                                         const sslam_proj_query* d_queries, const uint8_t* d_qdesc, const int32_t* d_nq, int qcap,
+                                         float nnratio, int th_dist, int check_orientation,
+                                         int32_t* d_assigned, int32_t* d_nmatches, void* stream);
 /* sslam_hamming_knn2 between the descriptors of two frame handles (cv::BFMatcher::knnMatch(d1, d2, m, 2),
  * src/LSDmatcher.cpp:150,261,293,336,387). */
 int sslam_hamming_knn2_frames(sslam_ctx* ctx, const sslam_frame* query, const sslam_frame* train, int32_t* idx, int32_t* dist);

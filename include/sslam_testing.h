@@ -55,6 +55,10 @@ int sslam_selftest_fetch_probe(sslam_ctx* ctx, size_t bytes, int mode, long long
  * the last call; meaningful in builds with -DSSLAM_CL_CYCLES only (tools/cl_probe.py). */
 int sslam_lines_debug_cluster(sslam_lines* ln, int frame, long long* out8);
 
+/* sslam_search_by_projection_batch_dev of THIS library: at most max_slice frames per slice (0: the plan's own size), so that a test crosses a slice
+ * boundary with a handful of frames; feats_in_lds != 0: the commit keeps each frame's features in LDS as the single call does (64 bytes per feature,
+ * rows of at most 2048), the layout tools/proj_batch_probe.py times against the one the plan chooses.  Process-wide; results do not depend on either. */
+int sslam_testing_proj_batch_tuning(int max_slice, int feats_in_lds);
 
 #ifdef __cplusplus
 }

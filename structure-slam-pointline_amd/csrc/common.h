@@ -59,7 +59,7 @@ struct HostPinned {
 struct sslam_prof_rec { const char* name; hipEvent_t a, b; };
 
 // Slots of sslam_ctx::scratch and ::pinned (match.hip) with their users.  A slot with several users is safe to share because every one of
-// them holds ctx->mu for the whole call and synchronises the stream before it returns.
+// them holds ctx->mu for the whole call and synchronises the stream before it returns (SCR_PROJ_BATCH does neither and has one user).
 enum {
     SCR_KNN_Q = 0, SCR_KNN_T = 1, SCR_KNN_OUT = 2,      // sslam_hamming_knn2, sslam_hamming_matrix: query rows, train rows, result
     SCR_SFI_STATE = 3,       // sslam_orb_search_for_initialization_batch_dev: per-pair state (SfiArgs::scratch)
@@ -67,7 +67,8 @@ enum {
     SCR_LINE_MATCH = 5,      // sslam_line_match
     SCR_CALL = 6,            // the arena of search_proj_core, sslam_hamming_knn2_frames, sslam_distinctive_descriptors, sslam_fuse_search, sslam_orb_search_for_triangulation, bow_core
     SCR_UPLOAD = 7,          // host features that a core with an arena in SCR_CALL reads (sslam_search_by_projection, sslam_bow_transform); the arena of search_by_bow_core
-    SCR_COUNT = 8
+    SCR_PROJ_BATCH = 8,      // sslam_search_by_projection_batch_dev: the arena of one slice of frames.  Its user runs on the CALLER's stream and returns without synchronising, so it shares the slot with nobody; calls are ordered on it by projBatchDone
+    SCR_COUNT = 9
 };
 enum {
     PIN_BOW = 1,             // search_by_bow_core
@@ -88,6 +89,8 @@ struct sslam_ctx {
     sslam::DevBuf knnExpand;       // sslam_hamming_knn2_batch_dev: the train rows as int8 matrix-core operands (match_knn.h)
     hipEvent_t knnDone = nullptr;  // recorded behind the kernel that reads knnExpand: a call on ANOTHER stream waits for it before it overwrites the buffer
     void* knnLastStream = nullptr;
+    hipEvent_t projBatchDone = nullptr;      // recorded behind the last kernel that uses scratch[SCR_PROJ_BATCH]: a call on another stream waits for it on the device, a call that has to grow the slot on the host
+    void* projBatchLastStream = nullptr;
     sslam::DevBuf recordOffsets[4];   // sslam_pack_records_dev: per-frame offsets of the record stream, one buffer per stream that packs
     void* recordOffsetsStream[4] = {nullptr, nullptr, nullptr, nullptr};
     unsigned long recordOffsetsUse[4] = {0, 0, 0, 0}, recordOffsetsClock = 0;      // least-recently-used recycling of the four slots

@@ -321,6 +321,79 @@ extern "C" int sslam_search_by_projection(sslam_ctx* ctx, int kind, int mode, co
                             nnratio, th_dist, check_orientation, assigned_out, nmatches_out);
 }
 
+// ---- the projection-window matcher for B frames that are already on the device (the batch extractors' output buffers), asynchronous
+#ifdef SSLAM_TESTING      // libsslam_frontend_testing.so only (include/sslam_testing.h)
+static ProjBatchTuning g_projBatchTuning;
+extern "C" int sslam_testing_proj_batch_tuning(int max_slice, int feats_in_lds) {
+    if (max_slice < 0) { set_error("sslam_testing_proj_batch_tuning: invalid arguments"); return SSLAM_ERR_INVALID; }
+    g_projBatchTuning.maxSlice = max_slice; g_projBatchTuning.featsInLds = feats_in_lds != 0;
+    return SSLAM_OK;
+}
+#endif
+
+extern "C" int sslam_search_by_projection_batch_dev(sslam_ctx* ctx, int kind, int mode,
+        const void* d_feats, const uint8_t* d_desc, const int32_t* d_n, int cap, int nframes, const float bounds[4],
+        const float* d_uright, const uint8_t* d_occupied,
+        const sslam_proj_query* d_queries, const uint8_t* d_qdesc, const int32_t* d_nq, int qcap,
+        float nnratio, int th_dist, int check_orientation, int32_t* d_assigned, int32_t* d_nmatches, void* stream) {
+    const uintptr_t align4 = (uintptr_t)d_feats | (uintptr_t)d_n | (uintptr_t)d_uright | (uintptr_t)d_queries | (uintptr_t)d_nq | (uintptr_t)d_assigned | (uintptr_t)d_nmatches;
+    const uintptr_t align16 = (uintptr_t)d_desc | (uintptr_t)d_qdesc;      // descriptor rows are read as two 16-byte words
+    if (!ctx || (kind != 0 && kind != 1) || (mode != 0 && mode != 1) || (kind == 1 && mode == 1 && check_orientation) || cap < 0 || cap >= (1 << 19) || qcap < 0 ||
+        nframes < 0 || !bounds || !d_feats || !d_desc || !d_n || !d_queries || !d_qdesc || !d_nq || !d_assigned || !d_nmatches || (align4 & 3) || (align16 & 15)) {
+        set_error("sslam_search_by_projection_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (nframes == 0) return SSLAM_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    SSLAM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+#ifdef SSLAM_TESTING
+    const ProjBatchTuning tune = g_projBatchTuning;
+#else
+    const ProjBatchTuning tune;
+#endif
+    const ProjBatchPlan P = proj_batch_plan(cap, qcap, nframes, tune);      // match_plan.h: the kernels by row capacity, the slice by scratch
+    const ProjBatchArena L = proj_batch_arena(cap, qcap, P.slice, PROJ_K);
+    // ONE arena per context, used by the kernels of this call on the caller's stream after the call has returned.  A call on another stream waits (on the
+    // device) for the event behind the previous call's last kernel; a call that has to grow the arena waits for it on the host first, since growing frees it.
+    sslam::DevBuf& S = ctx->scratch[SCR_PROJ_BATCH];
+    if (!ctx->projBatchDone) SSLAM_HIP(hipEventCreateWithFlags(&ctx->projBatchDone, hipEventDisableTiming));
+    else if (L.total > S.cap) SSLAM_HIP(hipEventSynchronize(ctx->projBatchDone));
+    else if (ctx->projBatchLastStream != (void*)st) SSLAM_HIP(hipStreamWaitEvent(st, ctx->projBatchDone, 0));
+    int rc;
+    if ((rc = S.ensure(L.total))) return rc;
+    uint8_t* B = S.as<uint8_t>();
+    ProjBatchArgs T;
+    ProjArgs& A = T.A;
+    A.kind = kind; A.mode = mode; A.feats = d_feats; A.desc = d_desc; A.n = 0;
+    A.minX = bounds[0]; A.maxX = bounds[1]; A.minY = bounds[2]; A.maxY = bounds[3];
+    A.uright = d_uright; A.occIn = d_occupied; A.q = d_queries; A.qdesc = d_qdesc; A.nq = 0;
+    A.nnratio = nnratio; A.thDist = th_dist; A.checkOri = check_orientation;
+    A.assigned = d_assigned; A.nmatches = d_nmatches; A.scratch = nullptr; A.stats = nullptr;
+    T.n = d_n; T.nq = d_nq; T.cap = cap; T.qcap = qcap; T.frame0 = 0;
+    T.scratch = (int*)(B + L.scratch); T.top = (unsigned long long*)(B + L.top); T.cnt = (int*)(B + L.cnt);
+    if (P.form == ProjForm::TwoKernel && (rc = allow_dynamic_lds((const void*)k_proj_commit_batch, P.ldsBytes))) return rc;
+    for (int s = 0; s < proj_batch_slices(P, nframes); ++s) {      // slices of frames, in stream order on the one arena
+        const ProjBatchSlice sl = proj_batch_slice(P, nframes, s);
+        const int ns = sl.count;
+        T.frame0 = sl.first;
+        switch (P.form) {
+        case ProjForm::TwoKernel: {      // one wave per (frame, query), then one committing wave per frame
+            { sslam::ProfScope _ps(ctx, "k_proj_topk_batch", st); hipLaunchKernelGGL(k_proj_topk_batch, dim3(P.topkGrid, ns), dim3(256), 0, st, T); }
+            { sslam::ProfScope _ps(ctx, "k_proj_commit_batch", st); hipLaunchKernelGGL(k_proj_commit_batch, dim3(ns), dim3(64), P.ldsBytes, st, T, P.featsInLds); }
+            break;
+        }
+        case ProjForm::OneWave: {
+            sslam::ProfScope _ps(ctx, "k_search_proj_batch", st);
+            hipLaunchKernelGGL(k_search_proj_batch, dim3(ns), dim3(64), 0, st, T);
+            break;
+        }
+        }
+    }
+    SSLAM_HIP(hipGetLastError());
+    SSLAM_HIP(hipEventRecord(ctx->projBatchDone, st)); ctx->projBatchLastStream = (void*)st;
+    return SSLAM_OK;
+}
+
 // ---- device-resident frames
 extern "C" void sslam_frame_destroy(sslam_frame* f);
 extern "C" void sslam_vocab_destroy(sslam_vocab* v);

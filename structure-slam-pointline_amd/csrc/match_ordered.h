@@ -493,13 +493,12 @@ struct ProjArgs {
     long long* stats;      // SSLAM_PROJ_STATS (development aid, two-kernel form): commit steps, re-scans, cycles in re-scans, total cycles
 };
 
-__global__ __launch_bounds__(64) void k_search_proj(ProjArgs A) {
-    const int lane = threadIdx.x;
+// one frame by one wave; hist: HISTO_LENGTH ints of the workgroup's LDS
+__device__ __forceinline__ void search_proj_body(const ProjArgs& A, int lane, int* __restrict__ hist) {
     const int n = A.n, nq = A.nq;
     int* occ = A.scratch; int* key = occ + n; int* qbin = key + n; int* qidx = qbin + nq;
     const sslam_keypoint* kps = (const sslam_keypoint*)A.feats;
     const sslam_keyline* kls = (const sslam_keyline*)A.feats;
-    __shared__ int hist[HISTO_LENGTH];
     if (lane < HISTO_LENGTH) hist[lane] = 0;
     const float invW = __fdiv_rn((float)GRID_COLS, __fsub_rn(A.maxX, A.minX));
     const float invH = __fdiv_rn((float)GRID_ROWS, __fsub_rn(A.maxY, A.minY));
@@ -608,6 +607,10 @@ __global__ __launch_bounds__(64) void k_search_proj(ProjArgs A) {
     }
     if (lane == 0) *A.nmatches = nmatches;
 }
+__global__ __launch_bounds__(64) void k_search_proj(ProjArgs A) {
+    __shared__ int hist[HISTO_LENGTH];
+    search_proj_body(A, threadIdx.x, hist);
+}
 
 
 // ------------------------------------------------------------------ projection matchers, two-kernel form (round 3: the single call)
@@ -627,10 +630,7 @@ __global__ __launch_bounds__(64) void k_search_proj(ProjArgs A) {
 // The result equals the sequential loop: a query's pick is "smallest key among its candidates that are free when its turn comes", and a
 // prefix commits only when that set of free candidates is already final for every query in it.
 // Measured (1000 queries against 1000 keypoints): 0.14-0.22 ms per call, CPU oracle 0.26-0.46 ms (profiles/r03_matchers.txt).
-#ifndef SSLAM_PROJ_K
-#define SSLAM_PROJ_K 8
-#endif
-constexpr int PROJ_K = SSLAM_PROJ_K;      // list length: with 4, 3 % of the queries of a dense frame ran out of free entries and paid a re-scan (11-13 k cycles each, two thirds of the commit)
+// PROJ_K, the list length, lives in match_plan.h: the scratch of a batch is sized by it
 struct ProjTopArgs { ProjArgs A; unsigned long long* top; int* cnt; };
 
 // the candidate test of one (query, feature) pair, features in global memory; returns false when the feature is no candidate.
@@ -678,10 +678,9 @@ __device__ __forceinline__ bool proj_candidate(const ProjArgs& A, const sslam_pr
 }
 __device__ __forceinline__ int proj_key_feature(unsigned long long key) { return (int)((key >> 4) & 0x7FFFFu); }
 
-__global__ __launch_bounds__(256) void k_proj_topk(ProjTopArgs T) {
+// query iq (< A.nq) of one frame by one wave
+__device__ __forceinline__ void proj_topk_body(const ProjTopArgs& T, int iq, int lane) {
     const ProjArgs& A = T.A;
-    const int lane = threadIdx.x & 63, iq = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (iq >= A.nq) return;
     const sslam_proj_query Q = A.q[iq];
     unsigned long long t[PROJ_K];
 #pragma unroll
@@ -715,6 +714,11 @@ __global__ __launch_bounds__(256) void k_proj_topk(ProjTopArgs T) {
         }
     }
     if (lane == 0) T.cnt[iq] = cnt;
+}
+__global__ __launch_bounds__(256) void k_proj_topk(ProjTopArgs T) {
+    const int lane = threadIdx.x & 63, iq = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (iq >= T.A.nq) return;
+    proj_topk_body(T, iq, lane);
 }
 
 // accept / reject on (best, second) keys of the layout above: thresholds, same-level ratio test (mode 0), rotation bin (mode 1)
@@ -765,10 +769,10 @@ __device__ __forceinline__ bool proj_candidate_lds(const ProjArgs& A, const Proj
 // PROJ_MAXN (match_plan.h, where the host decides featsInLds) bounds the frames that take that copy: 64 bytes per feature must fit the 160 KB
 // of one compute unit next to the static arrays below.
 static_assert(64 * (size_t)PROJ_MAXN + 64 + 1024 <= 160 * 1024, "k_proj_commit: PROJ_MAXN features do not fit one compute unit's LDS");
-__global__ __launch_bounds__(64) void k_proj_commit(ProjTopArgs T, int featsInLds) {
-    extern __shared__ __align__(16) int pc[];
+// one frame by one wave; pc: the dynamic LDS described above, hist: HISTO_LENGTH ints of the workgroup's LDS
+__device__ __forceinline__ void proj_commit_body(const ProjTopArgs& T, int featsInLds, int* __restrict__ pc, int* __restrict__ hist, int lane) {
     const ProjArgs& A = T.A;
-    const int lane = threadIdx.x, n = A.n, nq = A.nq;
+    const int n = A.n, nq = A.nq;
     ProjFeatLds F;
     uint4* fdesc = (uint4*)pc;                                  // [2n] when featsInLds
     int* rest = featsInLds ? (int*)(fdesc + 2 * (size_t)n) : pc;
@@ -776,7 +780,6 @@ __global__ __launch_bounds__(64) void k_proj_commit(ProjTopArgs T, int featsInLd
     float* fx = (float*)(stamp + n); float* fy = fx + n; float* fang = fy + n; float* fur = fang + n; int* foct = (int*)(fur + n); int* ford = foct + n;
     F.desc = fdesc; F.x = fx; F.y = fy; F.ang = fang; F.ur = fur; F.oct = foct; F.order = ford;
     int* qbin = A.scratch + 2 * n; int* qidx = qbin + nq;          // the scratch layout of k_search_proj
-    __shared__ int hist[HISTO_LENGTH];
     if (lane < HISTO_LENGTH) hist[lane] = 0;
     const float invW = __fdiv_rn((float)GRID_COLS, __fsub_rn(A.maxX, A.minX));
     const float invH = __fdiv_rn((float)GRID_ROWS, __fsub_rn(A.maxY, A.minY));
@@ -903,6 +906,62 @@ __global__ __launch_bounds__(64) void k_proj_commit(ProjTopArgs T, int featsInLd
     }
     if (lane == 0) *A.nmatches = nmatches;
     if (lane == 0 && A.stats) { A.stats[0] = it; A.stats[1] = stRescan; A.stats[2] = cyRescan; A.stats[3] = __builtin_readcyclecounter() - tK0; }
+}
+__global__ __launch_bounds__(64) void k_proj_commit(ProjTopArgs T, int featsInLds) {
+    extern __shared__ __align__(16) int pc[];
+    __shared__ int hist[HISTO_LENGTH];
+    proj_commit_body(T, featsInLds, pc, hist, threadIdx.x);
+}
+
+// ------------------------------------------------------------------ projection matchers of a batch (sslam_search_by_projection_batch_dev)
+// B independent frames in cap / qcap strided buffers, a slice of them per launch (match_plan.h: proj_batch_plan).  Every kernel builds the ProjArgs of
+// its frame from the batch arguments and runs the single-frame body above on it: the matching rules exist once.  All per-frame state -- occupancy,
+// stamps and rotation histogram in the LDS of the frame's own workgroup, rotation bins, lists and counts in the frame's rows of the slice's scratch --
+// belongs to one workgroup (commit, one-wave form) or to the waves of one blockIdx.y (candidates): no two frames of a launch share any of it.
+struct ProjBatchArgs {
+    ProjArgs A;                    // the shared arguments; its pointers are the batch buffers (row 0 of frame 0); n, nq, scratch and stats are per frame
+    const int* n; const int* nq;   // per-frame counts, clamped to [0, cap] / [0, qcap] here
+    int cap, qcap;
+    int frame0;                    // first frame of the slice
+    int* scratch; unsigned long long* top; int* cnt;      // per frame of the SLICE: scratch[2 cap + 2 qcap], top[PROJ_K qcap], cnt[qcap]
+};
+__device__ __forceinline__ ProjTopArgs proj_batch_frame(const ProjBatchArgs& B, int s) {
+    const int f = B.frame0 + s;
+    const size_t r = (size_t)f * (size_t)B.cap, rq = (size_t)f * (size_t)B.qcap;
+    ProjTopArgs T;
+    T.A = B.A;
+    ProjArgs& A = T.A;
+    A.n = min(max(B.n[f], 0), B.cap); A.nq = min(max(B.nq[f], 0), B.qcap);
+    A.feats = (const uint8_t*)B.A.feats + r * (B.A.kind == 0 ? sizeof(sslam_keypoint) : sizeof(sslam_keyline));
+    A.desc = B.A.desc + r * 32;
+    A.uright = B.A.uright ? B.A.uright + r : nullptr;
+    A.occIn = B.A.occIn ? B.A.occIn + r : nullptr;
+    A.q = B.A.q + rq; A.qdesc = B.A.qdesc + rq * 32;
+    A.assigned = B.A.assigned + r; A.nmatches = B.A.nmatches + f;
+    A.scratch = B.scratch + (size_t)s * 2 * ((size_t)B.cap + (size_t)B.qcap);
+    A.stats = nullptr;
+    T.top = B.top + (size_t)s * PROJ_K * (size_t)B.qcap; T.cnt = B.cnt + (size_t)s * (size_t)B.qcap;
+    return T;
+}
+// grid (topkGrid, frames of the slice): one wave per (frame, query)
+__global__ __launch_bounds__(256) void k_proj_topk_batch(ProjBatchArgs B) {
+    const ProjTopArgs T = proj_batch_frame(B, blockIdx.y);
+    const int lane = threadIdx.x & 63, iq = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (iq >= T.A.nq) return;
+    proj_topk_body(T, iq, lane);
+}
+// grid (frames of the slice): one wave per frame, one frame per workgroup -- the frames of a slice commit concurrently
+__global__ __launch_bounds__(64) void k_proj_commit_batch(ProjBatchArgs B, int featsInLds) {
+    extern __shared__ __align__(16) int pc[];
+    __shared__ int hist[HISTO_LENGTH];
+    const ProjTopArgs T = proj_batch_frame(B, blockIdx.x);
+    proj_commit_body(T, featsInLds, pc, hist, threadIdx.x);
+}
+// rows beyond PROJ_TWO_KERNEL_MAXN: the one-wave kernel, one workgroup per frame
+__global__ __launch_bounds__(64) void k_search_proj_batch(ProjBatchArgs B) {
+    __shared__ int hist[HISTO_LENGTH];
+    const ProjTopArgs T = proj_batch_frame(B, blockIdx.x);
+    search_proj_body(T.A, threadIdx.x, hist);
 }
 
 // ---------------------------------------------------------------- SearchByBoW(KeyFrame*, Frame&)

@@ -85,6 +85,73 @@ inline ProjPlan proj_plan(int n, int nq) {
     return {ProjForm::TwoKernel, featsInLds, (size_t)(featsInLds ? 64 : 8) * (size_t)n + 64, (unsigned)((nq + 3) / 4)};
 }
 
+// -------------------------------------------------------------- projection-window matcher of a batch (sslam_search_by_projection_batch_dev)
+// B independent frames in cap / qcap strided device buffers.  The form follows the row capacity alone (every frame of a launch runs the same kernel):
+//   TwoKernel  cap <= PROJ_TWO_KERNEL_MAXN: k_proj_topk_batch (one wave per (frame, query), grid = topkGrid x frames of the slice) +
+//              k_proj_commit_batch (one wave per frame, one frame per workgroup).  The commit keeps occupancy and stamps in LDS, 8 bytes per feature:
+//              it is a latency-bound sequential walk, and at 8 KB per 1000-keypoint frame a compute unit holds as many frames as it has wave slots
+//              (32), where the single call's 64 bytes per feature would hold two.  Its rare re-scans read the features from global memory.
+//   OneWave    beyond that: k_search_proj_batch, one workgroup per frame on global memory.
+// The batch runs in slices of frames on the caller's stream so that the per-frame scratch (top-PROJ_K lists 8 * PROJ_K * qcap, eligible counts 4 * qcap,
+// and 8 * (cap + qcap) of per-frame state) does not grow with nframes: a slice holds as many frames as fit PROJ_BATCH_SCRATCH_MAX and at most
+// PROJ_BATCH_MAX_SLICE (grid.y of the candidate kernel), and at least one.
+#ifndef SSLAM_PROJ_K
+#define SSLAM_PROJ_K 8
+#endif
+constexpr int PROJ_K = SSLAM_PROJ_K;      // list length of k_proj_topk: with 4, 3 % of the queries of a dense frame ran out of free entries and paid a re-scan (11-13 k cycles each, two thirds of the commit)
+constexpr size_t PROJ_BATCH_SCRATCH_MAX = (size_t)256 << 20;
+constexpr int PROJ_BATCH_MAX_SLICE = 32768;
+constexpr size_t DYNAMIC_LDS_DEFAULT_MAX = 48 * 1024;      // more dynamic LDS than this has to be allowed per kernel (hipFuncSetAttribute)
+// what only libsslam_frontend_testing.so can set (sslam_testing_proj_batch_tuning): a smaller slice, so that a test crosses a slice boundary with a handful
+// of frames, and the single call's features-in-LDS commit layout, so that tools/proj_batch_probe.py can time it against the one chosen here
+struct ProjBatchTuning { int maxSlice = 0; int featsInLds = 0; };
+struct ProjBatchPlan {
+    ProjForm form;
+    int featsInLds;           // TwoKernel: the commit copies the frame's features into LDS (0 unless the testing library asks for it and cap <= PROJ_MAXN)
+    size_t ldsBytes;          // TwoKernel: dynamic LDS of k_proj_commit_batch per workgroup (= per frame)
+    int ldsOptIn;             // ldsBytes is more than a launch may ask for without hipFuncSetAttribute
+    unsigned topkGrid;        // TwoKernel: grid.x of k_proj_topk_batch (four queries per workgroup), at least 1; grid.y = frames of the slice
+    size_t frameBytes;        // scratch of one frame of a slice
+    int slice;                // frames per slice: 1 <= slice <= max(nframes, 1)
+};
+inline size_t proj_batch_frame_bytes(int cap, int qcap, int projK) {
+    return 8 * ((size_t)cap + (size_t)qcap) + 8 * (size_t)projK * (size_t)qcap + 4 * (size_t)qcap;
+}
+inline ProjBatchPlan proj_batch_plan(int cap, int qcap, int nframes, ProjBatchTuning tune = ProjBatchTuning()) {
+    ProjBatchPlan P{};
+    P.form = cap > PROJ_TWO_KERNEL_MAXN ? ProjForm::OneWave : ProjForm::TwoKernel;
+    if (P.form == ProjForm::TwoKernel) {
+        P.featsInLds = tune.featsInLds && cap <= PROJ_MAXN ? 1 : 0;
+        P.ldsBytes = (size_t)(P.featsInLds ? 64 : 8) * (size_t)cap + 64;
+        P.ldsOptIn = P.ldsBytes > DYNAMIC_LDS_DEFAULT_MAX ? 1 : 0;
+        P.topkGrid = (unsigned)std::max(1, (qcap + 3) / 4);
+    }
+    P.frameBytes = proj_batch_frame_bytes(cap, qcap, PROJ_K);
+    const size_t fit = PROJ_BATCH_SCRATCH_MAX / std::max<size_t>(P.frameBytes, 1);
+    int slice = (int)std::min<size_t>(fit, (size_t)PROJ_BATCH_MAX_SLICE);
+    if (tune.maxSlice > 0) slice = std::min(slice, tune.maxSlice);
+    P.slice = std::max(1, std::min(slice, nframes));
+    return P;
+}
+// the slices of a batch, in launch order: slice s holds frames [first, first + count)
+struct ProjBatchSlice { int first, count; };
+inline int proj_batch_slices(const ProjBatchPlan& P, int nframes) { return (nframes + P.slice - 1) / P.slice; }
+inline ProjBatchSlice proj_batch_slice(const ProjBatchPlan& P, int nframes, int s) {
+    const int first = s * P.slice;
+    return {first, std::min(P.slice, nframes - first)};
+}
+// arena of one slice: per frame of the slice scratch[2 cap + 2 qcap] ints (ProjArgs::scratch), top[projK qcap] keys, cnt[qcap] ints.
+// total <= max(PROJ_BATCH_SCRATCH_MAX, one frame's bytes) + 3 * 256, whatever nframes is.
+struct ProjBatchArena { size_t scratch, top, cnt, total; };
+inline ProjBatchArena proj_batch_arena(int cap, int qcap, int slice, int projK) {
+    ArenaLayout L; ProjBatchArena a;
+    a.scratch = L.take((size_t)slice * 8 * ((size_t)cap + (size_t)qcap));
+    a.top = L.take((size_t)slice * 8 * (size_t)projK * (size_t)qcap);
+    a.cnt = L.take((size_t)slice * 4 * (size_t)qcap);
+    a.total = L.size();
+    return a;
+}
+
 // arena of search_proj_core.  occ | q | qdesc go up in ONE copy (occ .. assigned), assigned | count come back in one (assigned .. count + 4);
 // only that head (.. count + 256) has a pinned mirror.  projK = list length of k_proj_topk (PROJ_K).
 struct ProjArena {

@@ -170,6 +170,16 @@ class Context:
                                               len(queries), C.c_float(nnratio), int(th_dist), int(bool(check_orientation)), _p(assigned), C.byref(nm)))
         return assigned, nm.value
 
+    def search_by_projection_batch_dev(self, kind, mode, d_feats, d_desc, d_n, cap, nframes, d_queries, d_qdesc, d_nq, qcap, d_assigned, d_nmatches,
+                                       d_occupied=None, d_uright=None, nnratio=0.8, th_dist=100, check_orientation=True, bounds=(0.0, 640.0, 0.0, 480.0),
+                                       stream=None):
+        """sslam_search_by_projection_batch_dev on device tensors / pointers laid out like the batch extractors' outputs (rows f*cap .. of the
+        features, f*qcap .. of the queries); enqueues on `stream` (None: the context's) and returns without synchronising"""
+        b = (C.c_float * 4)(*bounds)
+        _chk(lib().sslam_search_by_projection_batch_dev(self.h, int(kind), int(mode), _p(d_feats), _p(d_desc), _p(d_n), int(cap), int(nframes), b,
+                                                        _p(d_uright), _p(d_occupied), _p(d_queries), _p(d_qdesc), _p(d_nq), int(qcap), C.c_float(nnratio),
+                                                        int(th_dist), int(bool(check_orientation)), _p(d_assigned), _p(d_nmatches), C.c_void_p(stream or 0)))
+
     def search_by_bow(self, kf_kp, kf_desc, kf_valid, f_kp, f_desc, ptr_kf, ptr_f, idx_kf, idx_f, nnratio=0.9, check_orientation=True):
         kf_kp = np.ascontiguousarray(kf_kp); f_kp = np.ascontiguousarray(f_kp)
         kf_desc = np.ascontiguousarray(kf_desc, np.uint8); f_desc = np.ascontiguousarray(f_desc, np.uint8)

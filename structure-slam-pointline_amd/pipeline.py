@@ -132,6 +132,37 @@ class FrontendBatch:
                                           C.c_double(0.5), 0, _p(self.lpairs), _p(self.nlpairs), st)
         assert rc == 0, L.sslam_last_error()
 
+    def search_by_projection(self, kind, mode, queries, qdesc, nq, occupied=None, nnratio=0.8, th_dist=100, check_orientation=True):
+        """The projection-window matcher (sslam_search_by_projection_batch_dev) of every frame of the batch against the resident features of
+        the `cur` extraction: kind 0 keypoints (kp, desc, n), kind 1 keylines (kl, ldesc, nl).  queries: device tensor of [B, qcap]
+        sslam_proj_query records (44 bytes each, any dtype), qdesc: uint8 [B, qcap, 32], nq: int32 [B]; occupied: uint8 [B, cap] or None.
+        Runs on the pipeline's point stream; the caller's current stream is ordered before and after.  Returns the [B, cap] assigned tensor
+        and the [B] match counts (owned by the pipeline: the next call of the same kind overwrites them; rows at or past a frame's count are
+        not written and keep what they held)."""
+        c = self.feat["cur"]
+        feats, desc, n, cap = (c["kp"], c["desc"], c["n"], self.cap) if kind == 0 else (c["kl"], c["ldesc"], c["nl"], self.lcap)
+        qcap = qdesc.shape[1]
+        assert qdesc.is_cuda and qdesc.dtype == torch.uint8 and qdesc.shape == (self.B, qcap, 32) and qdesc.is_contiguous()
+        assert queries.is_cuda and queries.is_contiguous() and queries.numel() * queries.element_size() == self.B * qcap * 44
+        assert nq.is_cuda and nq.dtype == torch.int32 and nq.shape == (self.B,)
+        assert occupied is None or (occupied.is_cuda and occupied.dtype == torch.uint8 and occupied.shape == (self.B, cap) and occupied.is_contiguous())
+        if not hasattr(self, "_proj_out"):
+            self._proj_out = {}
+        if kind not in self._proj_out:          # on first use: a pipeline that never calls this holds no memory for it
+            self._proj_out[kind] = (torch.full((self.B, cap), -1, dtype=torch.int32, device=self.dev), torch.zeros(self.B, dtype=torch.int32, device=self.dev))
+        assigned, nm = self._proj_out[kind]
+        s1, _ = self._streams()
+        cur = torch.cuda.current_stream(self.dev)
+        s1.wait_stream(cur)
+        with torch.cuda.stream(s1):
+            self.ctx.search_by_projection_batch_dev(kind, mode, feats, desc, n, cap, self.B, queries, qdesc, nq, qcap, assigned, nm, d_occupied=occupied,
+                                                    nnratio=nnratio, th_dist=th_dist, check_orientation=check_orientation,
+                                                    bounds=(0.0, float(self.w), 0.0, float(self.h)), stream=self._stream())
+            for t in (queries, qdesc, nq) + ((occupied,) if occupied is not None else ()):
+                t.record_stream(s1)
+        cur.wait_stream(s1)
+        return assigned, nm
+
     def step(self, images, overlap=False, lines_first=False, join=True):
         """One pass of the hot path.  overlap=True runs the point branch (ORB extract + ORB matching)
         and the line branch (LSD/LBD extract + line matching) on two HIP streams: the line branch is
