@@ -55,6 +55,19 @@ int sslam_selftest_fetch_probe(sslam_ctx* ctx, size_t bytes, int mode, long long
  * the last call; meaningful in builds with -DSSLAM_CL_CYCLES only (tools/cl_probe.py). */
 int sslam_lines_debug_cluster(sslam_lines* ln, int frame, long long* out8);
 
+/* The line tail -- k_keylines (checkLineExtremes, KeyLine fill, top-N by response, line equations), k_blur_sobel and k_lbd: LSDDetector::detectImpl's KeyLine fill,
+ * the cap and BinaryDescriptor::compute of src/ExtractLineSegment.cpp:42-68 -- on segments the CALLER supplies in place of the LSD detector's, so that a test can drive those
+ * kernels at their own edges.  `nframes` gray images of one size on the host (row pitch `stride`, `image_stride` bytes from frame to frame); segs[nframes][nmax][4] = x1, y1,
+ * x2, y2 in source pixels in emission order; accept[nframes][nmax] (NULL: all accepted) = what the NFA stage's flag would be; nsegs[nframes] <= min(nmax, 8192) candidates per
+ * frame (more: SSLAM_ERR_INVALID).  The call builds plan, workspace and constants as sslam_lines_extract_batch_dev does (one shared function), zeroes the frames' scalars,
+ * writes segments, flags and candidate counts where the NFA stage leaves them and runs the launches the product path runs behind that stage (one shared function).
+ * Outputs on the host, `cap` (<= 8192) rows per frame: kl_out[nframes][cap], ldesc_out[nframes][cap][32], linefn_out[nframes][cap][3], counts_out[nframes] and, unless
+ * NULL, lbd_dir_out[nframes][cap][2] = the (cos, sin) pairs k_keylines leaves for k_lbd.  Every device output buffer is filled with the byte 0xA5 before the launches and
+ * copied back whole: rows at or past a frame's count still hold it.  The handle must have been created by THIS library (the kernels' __constant__ tables are per library and
+ * uploaded once per handle); sslam_lines_debug_segments afterwards returns the accepted segments in order. */
+int sslam_testing_lines_tail(sslam_lines* ln, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, const float* segs, const uint8_t* accept,
+                             const int32_t* nsegs, int nmax, int cap, sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out, int32_t* counts_out, float* lbd_dir_out);
+
 /* sslam_search_by_projection_batch_dev of THIS library: at most max_slice frames per slice (0: the plan's own size), so that a test crosses a slice
  * boundary with a handful of frames; feats_in_lds != 0: the commit keeps each frame's features in LDS as the single call does (64 bytes per feature,
  * rows of at most 2048), the layout tools/proj_batch_probe.py times against the one the plan chooses.  Process-wide; results do not depend on either. */

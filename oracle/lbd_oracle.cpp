@@ -143,17 +143,9 @@ using namespace orc;
 
 extern "C" {
 
-// LineSegment::ExtractLineSegment (src/ExtractLineSegment.cpp:18-69) with the cap as a parameter
-// (the reference hard-codes 40, :42).  Returns the number of lines; keylines are 68-byte KeyLine
-// records, ldesc n x 32, linefn n x 3 doubles.  raw_segments (optional) receives every LSD segment.
-int orc_lines_extract(const uint8_t* gray, int w, int h, int stride, int max_lines, void* kl_out, uint8_t* ldesc_out,
-                      double* linefn_out, int cap, float* raw_segments, int raw_cap, int* raw_n, float* float_desc_out) {
-    Img8 im(w, h);
-    for (int y = 0; y < h; ++y) std::memcpy(im.row(y), gray + (size_t)y * stride, w);
-    std::vector<KeyLine> kls; std::vector<Seg4f> raw;
-    lsd_detect_keylines(im, kls, &raw);
-    if (raw_n) *raw_n = (int)raw.size();
-    if (raw_segments && !raw.empty()) std::memcpy(raw_segments, raw.data(), sizeof(Seg4f) * std::min<size_t>(raw.size(), raw_cap));
+// LineSegment::ExtractLineSegment (src/ExtractLineSegment.cpp:42-68) from the KeyLine list onward: the cap (a parameter; the reference hard-codes 40, :42), LBD and the
+// line equations.  Returns the number of lines; at most `cap` of them are written.
+static int lines_tail(const Img8& im, std::vector<KeyLine>& kls, int max_lines, void* kl_out, uint8_t* ldesc_out, double* linefn_out, int cap, float* float_desc_out) {
     if ((int)kls.size() > max_lines) {
         std::stable_sort(kls.begin(), kls.end(), [](const KeyLine& a, const KeyLine& b) { return a.response > b.response; });   // D3
         kls.resize(max_lines);
@@ -174,6 +166,50 @@ int orc_lines_extract(const uint8_t* gray, int w, int h, int stride, int max_lin
         linefn_out[i * 3] = l0 / nrm; linefn_out[i * 3 + 1] = l1 / nrm; linefn_out[i * 3 + 2] = l2 / nrm;
     }
     return (int)kls.size();
+}
+
+static Img8 image_of(const uint8_t* gray, int w, int h, int stride) {
+    Img8 im(w, h);
+    for (int y = 0; y < h; ++y) std::memcpy(im.row(y), gray + (size_t)y * stride, w);
+    return im;
+}
+
+// LineSegment::ExtractLineSegment (src/ExtractLineSegment.cpp:18-69) with the cap as a parameter
+// (the reference hard-codes 40, :42).  Returns the number of lines; keylines are 68-byte KeyLine
+// records, ldesc n x 32, linefn n x 3 doubles.  raw_segments (optional) receives every LSD segment.
+int orc_lines_extract(const uint8_t* gray, int w, int h, int stride, int max_lines, void* kl_out, uint8_t* ldesc_out,
+                      double* linefn_out, int cap, float* raw_segments, int raw_cap, int* raw_n, float* float_desc_out) {
+    const Img8 im = image_of(gray, w, h, stride);
+    std::vector<KeyLine> kls; std::vector<Seg4f> raw;
+    lsd_detect_keylines(im, kls, &raw);
+    if (raw_n) *raw_n = (int)raw.size();
+    if (raw_segments && !raw.empty()) std::memcpy(raw_segments, raw.data(), sizeof(Seg4f) * std::min<size_t>(raw.size(), raw_cap));
+    return lines_tail(im, kls, max_lines, kl_out, ldesc_out, linefn_out, cap, float_desc_out);
+}
+
+// The same from the KeyLine fill onward, on `n` segments (x1, y1, x2, y2 in emission order) the caller supplies in place of the detector's
+int orc_lines_tail(const uint8_t* gray, int w, int h, int stride, const float* segs, int n, int max_lines, void* kl_out, uint8_t* ldesc_out,
+                   double* linefn_out, int cap, float* float_desc_out) {
+    const Img8 im = image_of(gray, w, h, stride);
+    std::vector<Seg4f> sv((size_t)std::max(n, 0));
+    if (n > 0) std::memcpy(sv.data(), segs, sizeof(Seg4f) * (size_t)n);
+    std::vector<KeyLine> kls;
+    keylines_from_segments(w, h, sv, kls);
+    return lines_tail(im, kls, max_lines, kl_out, ldesc_out, linefn_out, cap, float_desc_out);
+}
+
+// lbd_compute on `n` keylines the caller supplies (under orc_set_gauss_variant / orc_set_lbd_bit_order as every other entry): ldesc n x 32, float_desc (optional) n x 72
+int orc_lbd_from_keylines(const uint8_t* gray, int w, int h, int stride, const void* keylines, int n, uint8_t* ldesc_out, float* float_desc_out) {
+    const Img8 im = image_of(gray, w, h, stride);
+    std::vector<KeyLine> kls((size_t)std::max(n, 0));
+    if (n > 0) std::memcpy(kls.data(), keylines, sizeof(KeyLine) * (size_t)n);
+    std::vector<uint8_t> desc; std::vector<float> fdesc;
+    lbd_compute(im, kls, desc, float_desc_out ? &fdesc : nullptr);
+    if (n > 0) {
+        std::memcpy(ldesc_out, desc.data(), (size_t)n * 32);
+        if (float_desc_out) std::memcpy(float_desc_out, fdesc.data(), sizeof(float) * 72 * (size_t)n);
+    }
+    return n;
 }
 
 int orc_set_lbd_bit_order(int v) { const int old = g_lbdBitOrder; g_lbdBitOrder = v == 1 ? 1 : 0; return old; }

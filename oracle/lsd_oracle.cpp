@@ -409,26 +409,31 @@ struct Lsd {
     }
 };
 
-// LSDDetector::detectImpl (opencv_contrib line_descriptor/src/LSDDetector.cpp), numOctaves = 1
+// LSDDetector::detectImpl (opencv_contrib line_descriptor/src/LSDDetector.cpp), numOctaves = 1: the detector ...
 void lsd_detect_keylines(const Img8& image, std::vector<KeyLine>& keylines, std::vector<Seg4f>* raw) {
-    keylines.clear();
     Lsd lsd;
     std::vector<Seg4f> segs;
     lsd.detect(image, segs);
     if (raw) *raw = segs;
+    keylines_from_segments(image.w, image.h, segs, keylines);
+}
+
+// ... and its KeyLine fill, for the segments of an image of w x h pixels in emission order
+void keylines_from_segments(int w, int h, const std::vector<Seg4f>& segs, std::vector<KeyLine>& keylines) {
+    keylines.clear();
     int class_counter = -1;
     const float octaveScale = 1.0f;      // pow((float)scale, 0)
     for (size_t k = 0; k < segs.size(); ++k) {
         float e[4] = {segs[k].x1, segs[k].y1, segs[k].x2, segs[k].y2};
         // checkLineExtremes
         if (e[0] < 0) e[0] = 0;
-        if (e[0] >= image.w) e[0] = (float)image.w - 1.0f;
+        if (e[0] >= w) e[0] = (float)w - 1.0f;
         if (e[2] < 0) e[2] = 0;
-        if (e[2] >= image.w) e[2] = (float)image.w - 1.0f;
+        if (e[2] >= w) e[2] = (float)w - 1.0f;
         if (e[1] < 0) e[1] = 0;
-        if (e[1] >= image.h) e[1] = (float)image.h - 1.0f;
+        if (e[1] >= h) e[1] = (float)h - 1.0f;
         if (e[3] < 0) e[3] = 0;
-        if (e[3] >= image.h) e[3] = (float)image.h - 1.0f;
+        if (e[3] >= h) e[3] = (float)h - 1.0f;
         KeyLine kl;
         kl.startPointX = e[0] * octaveScale; kl.startPointY = e[1] * octaveScale;
         kl.endPointX = e[2] * octaveScale; kl.endPointY = e[3] * octaveScale;
@@ -442,7 +447,7 @@ void lsd_detect_keylines(const Img8& image, std::vector<KeyLine>& keylines, std:
         kl.class_id = ++class_counter;
         kl.octave = 0;
         kl.size = (kl.endPointX - kl.startPointX) * (kl.endPointY - kl.startPointY);
-        kl.response = kl.lineLength / (float)std::max(image.w, image.h);
+        kl.response = kl.lineLength / (float)std::max(w, h);
         kl.pt_x = (kl.endPointX + kl.startPointX) / 2; kl.pt_y = (kl.endPointY + kl.startPointY) / 2;
         keylines.push_back(kl);
     }

@@ -501,6 +501,20 @@ static int lines_core(const LinesCall& c, const LinesKnobs& K, CoreForm form, in
     return SSLAM_OK;
 }
 
+// Behind the NFA stage: the output lines (KeyLine fill, top-N, line equations), LBD's gradient image unless the side stream has it, and the descriptors.  What lines_tail
+// and the testing library's sslam_testing_lines_tail (segments injected in place of the NFA stage's) share.
+static void lines_describe(const LinesCall& c, SideJoin& side, sslam_keyline* d_kl, uint8_t* d_ldesc, double* d_linefn, int32_t* d_counts, int cap) {
+    sslam_lines* L = c.L; const LsdPlan& P = c.P; const int nframes = c.nframes; hipStream_t st = c.st;
+    { sslam::ProfScope _ps(L->ctx, "k_keylines", st); hipLaunchKernelGGL(k_keylines, dim3(nframes), dim3(256), 0, st, c.ws, P, L->maxLines, d_kl, d_linefn, d_counts, cap); }
+    if (!side.forked) lines_blur_sobel(c, st);
+    side.join();
+    {   // the walk's conversion form (lbd.h): images of up to 16 384 pixels a side; the previous form beyond
+        const bool rpi = P.w <= 16384 && P.h <= 16384;
+        sslam::ProfScope _ps(L->ctx, "k_lbd", st);
+        hipLaunchKernelGGL(rpi ? k_lbd<true> : k_lbd<false>, dim3(std::min(L->maxLines, cap), nframes), dim3(64), 0, st, c.ws, P, d_kl, d_counts, d_ldesc, cap);
+    }
+}
+
 // The tail: the NFA stage, the output lines, LBD's gradient image and the descriptors
 static int lines_tail(const LinesCall& c, CoreForm form, size_t nfaStageOff, SideJoin& side, sslam_keyline* d_kl, uint8_t* d_ldesc, double* d_linefn, int32_t* d_counts, int cap) {
     sslam_lines* L = c.L; const LsdPlan& P = c.P; const int nframes = c.nframes; hipStream_t st = c.st;
@@ -523,28 +537,13 @@ static int lines_tail(const LinesCall& c, CoreForm form, size_t nfaStageOff, Sid
         side.join();
         if ((rc = sslam::launch_nfa_stream(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), L->clFrame, nfaStageOff, nframes, 16, 0, false))) return rc;
     } else if ((rc = sslam::launch_nfa_stage(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), nframes))) return rc;
-    { sslam::ProfScope _ps(L->ctx, "k_keylines", st); hipLaunchKernelGGL(k_keylines, dim3(nframes), dim3(256), 0, st, c.ws, P, L->maxLines, d_kl, d_linefn, d_counts, cap); }
-    if (!side.forked) lines_blur_sobel(c, st);
-    side.join();
-    {   // the walk's conversion form (lbd.h): images of up to 16 384 pixels a side; the previous form beyond
-        const bool rpi = P.w <= 16384 && P.h <= 16384;
-        sslam::ProfScope _ps(L->ctx, "k_lbd", st);
-        hipLaunchKernelGGL(rpi ? k_lbd<true> : k_lbd<false>, dim3(std::min(L->maxLines, cap), nframes), dim3(64), 0, st, c.ws, P, d_kl, d_counts, d_ldesc, cap);
-    }
+    lines_describe(c, side, d_kl, d_ldesc, d_linefn, d_counts, cap);
     return SSLAM_OK;
 }
 
-extern "C" int sslam_lines_extract_batch_dev(sslam_lines* L, const uint8_t* d_images, int w, int h, size_t pitch, size_t image_stride,
-                                             int nframes, sslam_keyline* d_kl, uint8_t* d_ldesc, double* d_linefn, int32_t* d_counts,
-                                             int cap, void* stream_) {
-    if (!L || !d_images || !d_kl || !d_ldesc || !d_linefn || !d_counts || w <= 0 || h <= 0 || nframes <= 0 || cap <= 0 || pitch < (size_t)w) {
-        set_error("sslam_lines_extract_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
-    }
-    if (nframes > 1 && image_stride < pitch * (size_t)(h - 1) + (size_t)w) { set_error("sslam_lines_extract_batch_dev: the frames overlap (image_stride < pitch * (h - 1) + w)"); return SSLAM_ERR_INVALID; }
-    const LinesKnobs K = lines_knobs();
-    std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);      // plan, workspace and profile records are shared state
-    SSLAM_HIP(hipSetDevice(L->ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : L->ctx->stream;
+// What a batch call needs before its first launch: the plan of the image size, LBD's constants on the device, a workspace of `nframes` frames.  The caller holds the
+// context's lock.  (sslam_lines_extract_batch_dev and, in the testing library, sslam_testing_lines_tail)
+static int lines_prepare(sslam_lines* L, int w, int h, int nframes, hipStream_t st) {
     int rc;
     if (w != L->planW || h != L->planH) { SSLAM_HIP(hipStreamSynchronize(st)); if ((rc = lines_build_plan(L, w, h))) return rc; }
     if (!L->constsUploaded) {
@@ -571,6 +570,23 @@ extern "C" int sslam_lines_extract_batch_dev(sslam_lines* L, const uint8_t* d_im
         if ((rc = L->dWs.ensure(P.frameBytes * (size_t)nframes))) return rc;
         L->wsFrames = nframes;
     }
+    return SSLAM_OK;
+}
+
+extern "C" int sslam_lines_extract_batch_dev(sslam_lines* L, const uint8_t* d_images, int w, int h, size_t pitch, size_t image_stride,
+                                             int nframes, sslam_keyline* d_kl, uint8_t* d_ldesc, double* d_linefn, int32_t* d_counts,
+                                             int cap, void* stream_) {
+    if (!L || !d_images || !d_kl || !d_ldesc || !d_linefn || !d_counts || w <= 0 || h <= 0 || nframes <= 0 || cap <= 0 || pitch < (size_t)w) {
+        set_error("sslam_lines_extract_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (nframes > 1 && image_stride < pitch * (size_t)(h - 1) + (size_t)w) { set_error("sslam_lines_extract_batch_dev: the frames overlap (image_stride < pitch * (h - 1) + w)"); return SSLAM_ERR_INVALID; }
+    const LinesKnobs K = lines_knobs();
+    std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);      // plan, workspace and profile records are shared state
+    SSLAM_HIP(hipSetDevice(L->ctx->device));
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : L->ctx->stream;
+    int rc;
+    if ((rc = lines_prepare(L, w, h, nframes, st))) return rc;
+    const LsdPlan& P = L->plan;
     const LinesCall c{L, P, d_images, pitch, image_stride, nframes, st, L->dWs.as<uint8_t>()};
     { sslam::ProfScope _ps(L->ctx, "k_zero_misc", st); hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c.ws, P); }
     SideJoin side{L, st};
@@ -700,6 +716,66 @@ extern "C" int sslam_lines_debug_cluster(sslam_lines* L, int frame, long long* o
     ClCtl c;
     SSLAM_HIP(hipMemcpy(&c, L->dCl.as<uint8_t>() + (size_t)frame * L->clFrame, sizeof(c), hipMemcpyDeviceToHost));
     for (int i = 0; i < 8; ++i) out8[i] = c.stat[i];
+    return SSLAM_OK;
+}
+
+// The line tail on segments the caller supplies (include/sslam_testing.h): the preparation of sslam_lines_extract_batch_dev (lines_prepare), k_zero_misc, then the
+// segments, accept flags and candidate count written where the NFA stage leaves them, and the launches the product path runs behind that stage (lines_describe).
+extern "C" int sslam_testing_lines_tail(sslam_lines* L, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, const float* segs,
+                                        const uint8_t* accept, const int32_t* nsegs, int nmax, int cap, sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out,
+                                        int32_t* counts_out, float* lbd_dir_out) {
+    if (!L || !gray || !nsegs || !kl_out || !ldesc_out || !linefn_out || !counts_out || w <= 0 || h <= 0 || nframes <= 0 || nmax < 0 || cap <= 0 || cap > MAX_SEG ||
+        stride < (size_t)w || (nmax > 0 && !segs)) {
+        set_error("sslam_testing_lines_tail: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (nframes > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w) { set_error("sslam_testing_lines_tail: the frames overlap"); return SSLAM_ERR_INVALID; }
+    for (int b = 0; b < nframes; ++b)
+        if (nsegs[b] < 0 || nsegs[b] > MAX_SEG || nsegs[b] > nmax) { set_error("sslam_testing_lines_tail: frame %d holds %d segments (at most %d)", b, nsegs[b], std::min(nmax, MAX_SEG)); return SSLAM_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
+    SSLAM_HIP(hipSetDevice(L->ctx->device));
+    hipStream_t st = L->ctx->stream;
+    int rc;
+    const size_t dpitch = ((size_t)w + 63) & ~(size_t)63, dframe = dpitch * h, rows = (size_t)nframes * cap;
+    if ((rc = L->dImg.ensure(dframe * nframes))) return rc;
+    if ((rc = L->dKl.ensure(sizeof(sslam_keyline) * rows))) return rc;
+    if ((rc = L->dDesc.ensure(32 * rows))) return rc;
+    if ((rc = L->dFn.ensure(24 * rows))) return rc;
+    if ((rc = L->dCounts.ensure(std::max<size_t>(16, sizeof(int32_t) * nframes)))) return rc;
+    L->lastN = -1;      // (the buffers of the last sslam_lines_extract are overwritten)
+    for (int b = 0; b < nframes; ++b)
+        SSLAM_HIP(hipMemcpy2DAsync(L->dImg.as<uint8_t>() + (size_t)b * dframe, dpitch, gray + (size_t)b * image_stride, stride, w, h, hipMemcpyHostToDevice, st));
+    if ((rc = lines_prepare(L, w, h, nframes, st))) return rc;
+    const LsdPlan& P = L->plan;
+    const LinesCall c{L, P, L->dImg.as<uint8_t>(), dpitch, dframe, nframes, st, L->dWs.as<uint8_t>()};
+    hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c.ws, P);
+    std::vector<int> flags((size_t)nframes * std::max(nmax, 1), 1);      // (alive until the stream is idle)
+    if (accept) for (size_t i = 0; i < (size_t)nframes * nmax; ++i) flags[i] = accept[i] ? 1 : 0;
+    for (int b = 0; b < nframes; ++b) {
+        uint8_t* base = c.ws + (size_t)b * P.frameBytes;
+        const int n = nsegs[b];
+        if (n > 0) {
+            SSLAM_HIP(hipMemcpyAsync(base + P.offSeg, segs + (size_t)b * nmax * 4, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, st));
+            SSLAM_HIP(hipMemcpyAsync(base + P.offFlag, flags.data() + (size_t)b * nmax, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+        }
+        SSLAM_HIP(hipMemcpyAsync(base + P.offMisc + offsetof(Misc, nCand), &nsegs[b], sizeof(int), hipMemcpyHostToDevice, st));
+        SSLAM_HIP(hipMemsetAsync(base + P.offLbdDir, 0xA5, sizeof(float2) * (size_t)cap, st));
+    }
+    SSLAM_HIP(hipMemsetAsync(L->dKl.p, 0xA5, sizeof(sslam_keyline) * rows, st));
+    SSLAM_HIP(hipMemsetAsync(L->dDesc.p, 0xA5, 32 * rows, st));
+    SSLAM_HIP(hipMemsetAsync(L->dFn.p, 0xA5, 24 * rows, st));
+    SSLAM_HIP(hipMemsetAsync(L->dCounts.p, 0xA5, sizeof(int32_t) * (size_t)nframes, st));
+    SideJoin side{L, st};
+    lines_describe(c, side, L->dKl.as<sslam_keyline>(), L->dDesc.as<uint8_t>(), L->dFn.as<double>(), L->dCounts.as<int32_t>(), cap);
+    SSLAM_HIP(hipGetLastError());
+    L->lastFrames = nframes;
+    SSLAM_HIP(hipMemcpyAsync(kl_out, L->dKl.p, sizeof(sslam_keyline) * rows, hipMemcpyDeviceToHost, st));
+    SSLAM_HIP(hipMemcpyAsync(ldesc_out, L->dDesc.p, 32 * rows, hipMemcpyDeviceToHost, st));
+    SSLAM_HIP(hipMemcpyAsync(linefn_out, L->dFn.p, 24 * rows, hipMemcpyDeviceToHost, st));
+    SSLAM_HIP(hipMemcpyAsync(counts_out, L->dCounts.p, sizeof(int32_t) * (size_t)nframes, hipMemcpyDeviceToHost, st));
+    if (lbd_dir_out)
+        for (int b = 0; b < nframes; ++b)
+            SSLAM_HIP(hipMemcpyAsync(lbd_dir_out + (size_t)b * cap * 2, c.ws + (size_t)b * P.frameBytes + P.offLbdDir, sizeof(float2) * (size_t)cap, hipMemcpyDeviceToHost, st));
+    SSLAM_HIP(hipStreamSynchronize(st));
     return SSLAM_OK;
 }
 

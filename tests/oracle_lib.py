@@ -301,7 +301,30 @@ def _orc_line_methods():
         self.L.orc_lsd_scaled(_p(gray), w, h, gray.strides[0], _p(out), C.byref(ow), C.byref(oh))
         return out
 
-    for f in (lines_extract, lsd_scaled):
+    def lines_tail(self, gray, segs, max_lines=40, cap=None, want_float=False):
+        """orc_lines_extract from the KeyLine fill onward, on the caller's segments (n x 4: x1, y1, x2, y2 in emission order) -> (keylines, ldesc, linefn[, float desc]),
+        min(lines, cap) rows each"""
+        gray = np.ascontiguousarray(gray, np.uint8); segs = np.ascontiguousarray(segs, np.float32).reshape(-1, 4)
+        h, w = gray.shape
+        cap = max(int(cap or min(len(segs), max_lines)), 1)
+        kl = np.zeros(cap, KL_DTYPE); ld = np.zeros((cap, 32), np.uint8); fn = np.zeros((cap, 3), np.float64)
+        fd = np.zeros((cap, 72), np.float32) if want_float else None
+        n = self.L.orc_lines_tail(_p(gray), w, h, gray.strides[0], _p(segs), len(segs), int(max_lines), _p(kl), _p(ld), _p(fn), cap, _p(fd))
+        n = min(n, cap)
+        out = (kl[:n].copy(), ld[:n].copy(), fn[:n].copy())
+        return out + (fd[:n].copy(),) if want_float else out
+
+    def lbd_from_keylines(self, gray, keylines, want_float=False):
+        """lbd_compute on the caller's keylines (KL_DTYPE) under the variants in force -> ldesc n x 32 [, float desc n x 72]"""
+        gray = np.ascontiguousarray(gray, np.uint8); kl = np.ascontiguousarray(keylines)
+        assert kl.dtype.itemsize == KL_DTYPE.itemsize
+        h, w = gray.shape
+        n = len(kl)
+        ld = np.zeros((n, 32), np.uint8); fd = np.zeros((n, 72), np.float32) if want_float else None
+        self.L.orc_lbd_from_keylines(_p(gray), w, h, gray.strides[0], _p(kl), n, _p(ld), _p(fd))
+        return (ld, fd) if want_float else ld
+
+    for f in (lines_extract, lsd_scaled, lines_tail, lbd_from_keylines):
         setattr(Oracle, f.__name__, f)
 
 

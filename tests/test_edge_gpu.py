@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 from synth import synth_frame, noise_frame
+from test_lines_gpu import _ulp_diff
 
 pytestmark = pytest.mark.gpu
 
@@ -63,7 +64,8 @@ def test_lines_ragged_and_caps(fe, ctx, oracle, w, h, cap):
     assert len(kl) == len(okl) == min(cap, len(oraw))
     a = kl.copy(); b = okl.copy(); a["angle"] = 0; b["angle"] = 0
     np.testing.assert_array_equal(a.view(np.uint8), b.view(np.uint8))
-    assert np.unpackbits(ld ^ old, axis=1).sum(axis=1).max(initial=0) <= 8
+    assert _ulp_diff(kl["angle"], okl["angle"]).max(initial=0) <= 1
+    np.testing.assert_array_equal(ld, oracle.lbd_from_keylines(img, kl))          # every row, against the oracle's LBD of the device's own keylines
     np.testing.assert_array_equal(fn, ofn)
     ex.close()
 
@@ -135,8 +137,11 @@ def test_randomised_parity_sweep(fe, ctx, oracle):
         for f in kl.dtype.names:
             if f != "angle":
                 np.testing.assert_array_equal(kl[f], okl[f], err_msg=f)
-        same = kl["angle"].view(np.uint32) == okl["angle"].view(np.uint32)
-        np.testing.assert_array_equal(ld[same], old[same]); np.testing.assert_array_equal(fn, ofn)
+        assert _ulp_diff(kl["angle"], okl["angle"]).max(initial=0) <= 1
+        prev = oracle.L.orc_set_lbd_bit_order(dec[1])          # (the one decision of the case that LBD depends on)
+        try: want = oracle.lbd_from_keylines(img, kl)
+        finally: oracle.L.orc_set_lbd_bit_order(prev)
+        np.testing.assert_array_equal(ld, want, err_msg="LBD, case %d" % it); np.testing.assert_array_equal(fn, ofn)
         n += 1
     assert n >= 40
 

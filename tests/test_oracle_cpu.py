@@ -169,6 +169,19 @@ def test_line_equations_and_keylines(oracle):
         assert kl["numOfPixels"][i] == max(abs(round(ex) - round(sx)), abs(round(ey) - round(sy))) + 1
 
 
+@pytest.mark.parametrize("frame,cap", [("synth2000", 40), ("synth2000", 200), ("icl", 40)])
+def test_lines_tail_reproduces_the_extraction(oracle, frame, cap):
+    """orc_lines_tail (the KeyLine fill, the cap, LBD and the line equations on segments the caller supplies) on the raw segments of orc_lines_extract gives that call's
+    output byte for byte, and orc_lbd_from_keylines on its keylines its descriptors"""
+    img = synth_frame(2000) if frame == "synth2000" else np.load(os.path.join(GOLD, "icl_input_gray.npz"))["gray"]
+    kl, ld, fn, raw, fd = oracle.lines_extract(img, cap, want_float=True)
+    assert len(raw) > cap == len(kl)
+    kl2, ld2, fn2, fd2 = oracle.lines_tail(img, raw, cap, cap=20000, want_float=True)
+    assert kl2.tobytes() == kl.tobytes() and ld2.tobytes() == ld.tobytes() and fn2.tobytes() == fn.tobytes() and fd2.tobytes() == fd.tobytes()
+    ld3, fd3 = oracle.lbd_from_keylines(img, kl, want_float=True)
+    assert ld3.tobytes() == ld.tobytes() and fd3.tobytes() == fd.tobytes()
+
+
 def test_vocabulary_text_loader_and_bow_vector(oracle, tmp_path):
     """oracle side of ORBVocabulary::loadFromTextFile + transform(features, BowVector, FeatureVector, levelsup) against a
     brute-force numpy restatement on a small ragged tree"""
