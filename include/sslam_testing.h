@@ -68,6 +68,22 @@ int sslam_lines_debug_cluster(sslam_lines* ln, int frame, long long* out8);
 int sslam_testing_lines_tail(sslam_lines* ln, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, const float* segs, const uint8_t* accept,
                              const int32_t* nsegs, int nmax, int cap, sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out, int32_t* counts_out, float* lbd_dir_out);
 
+/* The ORB tail -- k_octree (DistributeOctTree, src/ORBextractor.cc:539-763) and k_describe (IC_Angle, the 7x7 blur, computeOrbDescriptor and the KeyPoint fill, :77-147,
+ * :835-847, :1085-1101) -- on FAST candidates the CALLER supplies in place of k_fast_cells', so that a test can drive the two kernels at their own edges.  `nframes` gray
+ * images of one size on the host (row pitch `stride`, `image_stride` bytes from frame to frame), uploaded the way sslam_orb_extract uploads its frame;
+ * cand[nframes][nlevels][nmax][3] = x, y, score per candidate, x and y relative to the level's minBorder (16) as k_fast_cells packs them, in arrival order;
+ * ncand[nframes][nlevels] <= nmax.  Before any launch: 0 <= x < W, 0 <= y < H (the level's maxBorder - minBorder extents: its width and height less 32), 1 <= score <= 255,
+ * ncand <= the level's candidate capacity (the sum of its cells' ((cw + 1) / 2) * ((ch + 1) / 2); 0 for a level without cells), no two candidates of a level at one pixel
+ * -- SSLAM_ERR_INVALID otherwise.  The call prepares plan, constants and workspace and runs level-0 copy, resizes and k_fast_cells as sslam_orb_extract_batch_dev does (shared
+ * functions), then overwrites what k_fast_cells left: each level's list is dealt into that level's cells in order, every cell up to its capacity, and the cells' counts set to
+ * match, so that k_octree's gather returns the list in the caller's order; then it runs the product path's tail (one shared function).  Outputs on the host, `cap` rows per
+ * frame: kp_out[nframes][cap], desc_out[nframes][cap][32], counts_out[nframes], level_counts_out[nframes][nlevels] = what k_octree kept per level, and, unless NULL,
+ * *octree_lds_bytes_out = the dynamic LDS the k_octree launch asked for.  Every device output buffer is filled with the byte 0xA5 before the launches and copied back whole:
+ * rows at or past a frame's count still hold it.  The handle must have been created by THIS library (the kernels' __constant__ tables are per library and uploaded once per
+ * handle); sslam_orb_debug_candidates afterwards returns the injected lists. */
+int sslam_testing_orb_tail(sslam_orb* o, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, const int32_t* cand, const int32_t* ncand,
+                           int nmax, int cap, sslam_keypoint* kp_out, uint8_t* desc_out, int32_t* counts_out, int32_t* level_counts_out, size_t* octree_lds_bytes_out);
+
 /* sslam_search_by_projection_batch_dev of THIS library: at most max_slice frames per slice (0: the plan's own size), so that a test crosses a slice
  * boundary with a handful of frames; feats_in_lds != 0: the commit keeps each frame's features in LDS as the single call does (64 bytes per feature,
  * rows of at most 2048), the layout tools/proj_batch_probe.py times against the one the plan chooses.  Process-wide; results do not depend on either. */

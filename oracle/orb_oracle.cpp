@@ -124,9 +124,28 @@ static void divide_node(const Node& p, Node& n1, Node& n2, Node& n3, Node& n4) {
     if (n4.keys.size() == 1) n4.noMore = true;
 }
 
+// What a run of distribute_octtree went through (orc_orb_tail, orc_distribute_octtree): tests/test_orb_tail_cases_cpu.py proves from it that a candidate list reaches the
+// branch of the device's k_octree it is named after.  64 ints per level, the layout of tests/oracle_lib.py OCT_TRACE.
+struct OctTrace {
+    enum { END_FIRST_N = 0, END_FIRST_NO_GROWTH = 1, END_SECOND_BREAK = 2, END_SECOND_ROUND = 3, MAX_SORTED = 46 };
+    int end = END_FIRST_NO_GROWTH;      // how the loop ended
+    int finalNodes = 0, rounds1 = 0, rounds2 = 0;
+    int rounds2NoBreak = 0;             // second-phase rounds that divided every entry of their list
+    int maxDivided = 0, divSmall = 0, divLarge = 0;      // the largest node divided; divisions of n <= 64 and of n > 64 keypoints
+    int divEmptyClass = 0, divLargeEmptyClass = 0;       // divisions that left one of the four children empty (all / those of n > 64)
+    int div64 = 0, div65 = 0, div128 = 0, div129 = 0;
+    int tieNodes = 0;                   // final nodes that hold the maximal response twice or more
+    int equalPairs = 0;                 // adjacent entries of equal size, over all sorted lists
+    int maxAllEqual = 0;                // the longest sorted list (>= 2 entries) whose entries all have one size
+    int nSorted = 0;                    // sorted lists; the first MAX_SORTED lengths follow
+    int sorted[MAX_SORTED] = {};
+};
+static_assert(sizeof(OctTrace) == 64 * sizeof(int), "OctTrace is 64 ints");
+
 // DistributeOctTree, src/ORBextractor.cc:539-763
-static std::vector<KP> distribute_octtree(const std::vector<KP>& in, int minX, int maxX, int minY, int maxY, int N) {
+static std::vector<KP> distribute_octtree(const std::vector<KP>& in, int minX, int maxX, int minY, int maxY, int N, OctTrace* tr = nullptr) {
     std::vector<KP> result;
+    if (tr) *tr = OctTrace();
     const int nIni = (int)std::round((float)(maxX - minX) / (maxY - minY));
     if (nIni <= 0) return result;           // reference: division by zero (portrait aspect < 0.5); defined here as "no keypoints"
     const float hX = (float)(maxX - minX) / nIni;
@@ -170,43 +189,68 @@ static std::vector<KP> distribute_octtree(const std::vector<KP>& in, int minX, i
         if (a.first != b.first) return a.first < b.first;
         return a.second->seq < b.second->seq;            // D1
     };
+    auto note_division = [&](const Node& p, const Node& n1, const Node& n2, const Node& n3, const Node& n4) {
+        if (!tr) return;
+        const int n = (int)p.keys.size();
+        const bool empty = n1.keys.empty() || n2.keys.empty() || n3.keys.empty() || n4.keys.empty();
+        tr->maxDivided = std::max(tr->maxDivided, n);
+        ++(n <= 64 ? tr->divSmall : tr->divLarge);
+        if (empty) { ++tr->divEmptyClass; if (n > 64) ++tr->divLargeEmptyClass; }
+        tr->div64 += n == 64; tr->div65 += n == 65; tr->div128 += n == 128; tr->div129 += n == 129;
+    };
     while (!finish) {
         int prevSize = (int)nodes.size();
         auto it = nodes.begin();
         int nToExpand = 0;
         sizeAndNode.clear();
+        if (tr) ++tr->rounds1;
         while (it != nodes.end()) {
             if (it->noMore) { ++it; continue; }
             Node n1, n2, n3, n4;
             divide_node(*it, n1, n2, n3, n4);
+            note_division(*it, n1, n2, n3, n4);
             push_child(n1, &nToExpand); push_child(n2, &nToExpand);
             push_child(n3, &nToExpand); push_child(n4, &nToExpand);
             it = nodes.erase(it);
         }
-        if ((int)nodes.size() >= N || (int)nodes.size() == prevSize) finish = true;
+        if ((int)nodes.size() >= N || (int)nodes.size() == prevSize) { finish = true; if (tr) tr->end = (int)nodes.size() >= N ? OctTrace::END_FIRST_N : OctTrace::END_FIRST_NO_GROWTH; }
         else if ((int)nodes.size() + nToExpand * 3 > N) {
             while (!finish) {
                 prevSize = (int)nodes.size();
                 std::vector<SP> prev = sizeAndNode;
                 sizeAndNode.clear();
                 std::sort(prev.begin(), prev.end(), by_size_then_seq);
+                if (tr) {
+                    ++tr->rounds2;
+                    if (tr->nSorted < OctTrace::MAX_SORTED) tr->sorted[tr->nSorted] = (int)prev.size();
+                    ++tr->nSorted;
+                    int eq = 0;
+                    for (size_t k = 1; k < prev.size(); ++k) eq += prev[k].first == prev[k - 1].first;
+                    tr->equalPairs += eq;
+                    if (prev.size() >= 2 && eq == (int)prev.size() - 1) tr->maxAllEqual = std::max(tr->maxAllEqual, (int)prev.size());
+                }
+                bool broke = false;
                 for (int j = (int)prev.size() - 1; j >= 0; --j) {
                     Node n1, n2, n3, n4;
                     divide_node(*prev[j].second, n1, n2, n3, n4);
+                    note_division(*prev[j].second, n1, n2, n3, n4);
                     push_child(n1, nullptr); push_child(n2, nullptr);
                     push_child(n3, nullptr); push_child(n4, nullptr);
                     nodes.erase(prev[j].second->lit);
-                    if ((int)nodes.size() >= N) break;
+                    if ((int)nodes.size() >= N) { broke = true; break; }
                 }
+                if (tr) { if (!broke) ++tr->rounds2NoBreak; tr->end = broke ? OctTrace::END_SECOND_BREAK : OctTrace::END_SECOND_ROUND; }
                 if ((int)nodes.size() >= N || (int)nodes.size() == prevSize) finish = true;
             }
         }
     }
+    if (tr) tr->finalNodes = (int)nodes.size();
     for (Node& n : nodes) {                               // :742-760 best response, first wins ties
         const KP* best = &n.keys[0];
         float mx = best->response;
         for (size_t k = 1; k < n.keys.size(); ++k)
             if (n.keys[k].response > mx) { best = &n.keys[k]; mx = n.keys[k].response; }
+        if (tr) { int same = 0; for (const KP& k : n.keys) same += k.response == mx; tr->tieNodes += same >= 2; }
         result.push_back(*best);
     }
     return result;
@@ -236,11 +280,17 @@ static void orb_descriptor(const KP& kp, const Img8& img, uint8_t* desc) {
     float angle = kp.angle * factorPI;
     float a = cr_cosf(angle), b = cr_sinf(angle);      // D5
     const int step = img.w;
-    const uint8_t* center = img.d.data() + (size_t)cv_roundf(kp.y) * step + cv_roundf(kp.x);
+    const int cx = cv_roundf(kp.x), cy = cv_roundf(kp.y);
+    const uint8_t* center = img.d.data() + (size_t)cy * step + cx;
     const int* pat = kPattern;
+    // A keypoint of the reference lies 19 pixels inside its level (FAST's 3 on top of minBorder) and the pattern reaches 18: every tap is inside.  An INJECTED candidate
+    // (orc_orb_tail) may lie up to 3 pixels closer to the border; a tap that leaves the level then reads the blur of the level's reflect-101 extension, which by the
+    // symmetry of extension and kernel is the blurred level at the reflected position.
+    const bool inside = cx >= 18 && cy >= 18 && cx + 18 < img.w && cy + 18 < img.h;
     auto tap = [&](int idx) -> int {
         float px = (float)pat[idx * 2], py = (float)pat[idx * 2 + 1];
         int yy = cv_roundf(px * b + py * a), xx = cv_roundf(px * a - py * b);   // D4: no FMA
+        if (!inside) return img.d[(size_t)reflect101(cy + yy, img.h) * step + reflect101(cx + xx, img.w)];
         return center[yy * step + xx];
     };
     for (int i = 0; i < 32; ++i, pat += 32) {
@@ -256,6 +306,10 @@ static void orb_descriptor(const KP& kp, const Img8& img, uint8_t* desc) {
 struct OrbDebug {      // optional per-stage taps for stage-by-stage parity tests
     std::vector<Img8> levels;                      // unpadded pyramid levels
     std::vector<std::vector<FastKp>> candidates;   // per level, coords relative to minBorder (16)
+    // orc_orb_tail: per level, candidates that REPLACE what FAST finds (x, y relative to minBorder, in arrival order); what the quadtree went through and kept
+    const std::vector<std::vector<FastKp>>* inject = nullptr;
+    std::vector<OctTrace> traces;
+    std::vector<int> levelCounts;
 };
 
 // ORBextractor::operator() :1043-1105 with ComputeKeyPointsOctTree :765-853
@@ -265,7 +319,8 @@ static void orb_extract(const OrbParams& P, const Img8& image, std::vector<KP>& 
     if (image.w == 0 || image.h == 0) return;
     std::vector<Level> pyr = compute_pyramid(P, image);
     std::vector<std::vector<KP>> all(P.nlevels);
-    if (dbg) { dbg->levels.clear(); dbg->candidates.assign(P.nlevels, {}); for (auto& l : pyr) dbg->levels.push_back(l.roi); }
+    if (dbg) { dbg->levels.clear(); dbg->candidates.assign(P.nlevels, {}); for (auto& l : pyr) dbg->levels.push_back(l.roi); dbg->traces.assign(P.nlevels, OctTrace()); dbg->levelCounts.assign(P.nlevels, 0); }
+    const bool inject = dbg && dbg->inject;
     const float W = 30;
     for (int level = 0; level < P.nlevels; ++level) {
         const Img8& im = pyr[level].roi;     // mvImagePyramid[level] is the ROI; FAST views index it directly
@@ -274,7 +329,13 @@ static void orb_extract(const OrbParams& P, const Img8& image, std::vector<KP>& 
         std::vector<KP> toDistribute;
         const float width = (float)(maxBX - minBX), height = (float)(maxBY - minBY);
         const int nCols = (int)(width / W), nRows = (int)(height / W);
-        if (nCols > 0 && nRows > 0) {
+        if (inject) {
+            for (const FastKp& c : (*dbg->inject)[level]) {
+                KP k; k.x = (float)c.x; k.y = (float)c.y;
+                k.size = 7.f; k.angle = -1.f; k.response = (float)c.score; k.octave = 0; k.class_id = -1;
+                toDistribute.push_back(k);
+            }
+        } else if (nCols > 0 && nRows > 0) {
             const int wCell = (int)std::ceil(width / nCols), hCell = (int)std::ceil(height / nRows);
             std::vector<FastKp> cell;
             for (int i = 0; i < nRows; ++i) {
@@ -299,7 +360,8 @@ static void orb_extract(const OrbParams& P, const Img8& image, std::vector<KP>& 
             }
         }
         std::vector<KP>& keypoints = all[level];
-        keypoints = distribute_octtree(toDistribute, minBX, maxBX, minBY, maxBY, P.perLevel[level]);
+        keypoints = distribute_octtree(toDistribute, minBX, maxBX, minBY, maxBY, P.perLevel[level], dbg ? &dbg->traces[level] : nullptr);
+        if (dbg) dbg->levelCounts[level] = (int)keypoints.size();
         const int scaledPatchSize = (int)(PATCH_SIZE * P.scale[level]);
         for (KP& k : keypoints) { k.x += minBX; k.y += minBY; k.octave = level; k.size = (float)scaledPatchSize; }
     }
@@ -376,6 +438,49 @@ int orc_orb_candidates(const uint8_t* gray, int w, int h, int stride, int nfeatu
     int n = std::min((int)c.size(), cap);
     for (int i = 0; i < n; ++i) { xys_out[i * 3] = c[i].x; xys_out[i * 3 + 1] = c[i].y; xys_out[i * 3 + 2] = c[i].score; }
     return (int)c.size();
+}
+
+// orc_orb_extract with the FAST candidates of every level replaced by the caller's: cand[nlevels][nmax][3] = x, y, score relative to minBorder (16) in arrival order,
+// ncand[nlevels].  The checks of sslam_testing_orb_tail (inside the level's maxBorder - minBorder extents, scores 1..255) hold here too: -1 otherwise.  Returns the number
+// of keypoints; level_counts_out[nlevels]; trace_out[nlevels][64] (OctTrace) unless null.
+int orc_orb_tail(const uint8_t* gray, int w, int h, int stride, int nfeatures, float scaleFactor, int nlevels, const int32_t* cand, const int32_t* ncand, int nmax,
+                 void* kp_out, uint8_t* desc_out, int cap, int32_t* level_counts_out, int32_t* trace_out) {
+    OrbParams P = make_params(nfeatures, scaleFactor, nlevels, 20, 7);
+    Img8 im(w, h);
+    for (int y = 0; y < h; ++y) std::memcpy(im.row(y), gray + (size_t)y * stride, w);
+    std::vector<std::vector<FastKp>> inj(nlevels);
+    for (int l = 0; l < nlevels; ++l) {
+        const float scale = P.invScale[l];
+        const int W = cv_roundf((float)w * scale) - 2 * (EDGE_THRESHOLD - 3), H = cv_roundf((float)h * scale) - 2 * (EDGE_THRESHOLD - 3);
+        for (int i = 0; i < ncand[l]; ++i) {
+            const int32_t* c = cand + ((size_t)l * nmax + i) * 3;
+            if (ncand[l] > nmax || c[0] < 0 || c[0] >= W || c[1] < 0 || c[1] >= H || c[2] < 1 || c[2] > 255) return -1;
+            inj[l].push_back({c[0], c[1], c[2]});
+        }
+    }
+    std::vector<KP> kps; std::vector<uint8_t> desc; OrbDebug dbg;
+    dbg.inject = &inj;
+    orb_extract(P, im, kps, desc, &dbg);
+    const int n = std::min((int)kps.size(), cap);
+    if (n > 0) {
+        std::memcpy(kp_out, kps.data(), (size_t)n * sizeof(KP));
+        std::memcpy(desc_out, desc.data(), (size_t)n * 32);
+    }
+    for (int l = 0; l < nlevels; ++l) level_counts_out[l] = dbg.levelCounts[l];
+    if (trace_out) std::memcpy(trace_out, dbg.traces.data(), sizeof(OctTrace) * (size_t)nlevels);
+    return (int)kps.size();
+}
+
+// distribute_octtree alone on n candidates (x, y, score relative to minBorder) of a level whose maxBorder - minBorder extents are W x H, N features wanted:
+// sel_out[cap][3] = what it keeps, in order; trace_out[64] unless null.  Returns the number kept.
+int orc_distribute_octtree(const int32_t* cand, int n, int W, int H, int N, int32_t* sel_out, int cap, int32_t* trace_out) {
+    std::vector<KP> in(n);
+    for (int i = 0; i < n; ++i) { KP& k = in[i]; k.x = (float)cand[3 * i]; k.y = (float)cand[3 * i + 1]; k.size = 7.f; k.angle = -1.f; k.response = (float)cand[3 * i + 2]; k.octave = 0; k.class_id = -1; }
+    OctTrace tr;
+    const std::vector<KP> out = distribute_octtree(in, EDGE_THRESHOLD - 3, EDGE_THRESHOLD - 3 + W, EDGE_THRESHOLD - 3, EDGE_THRESHOLD - 3 + H, N, &tr);
+    for (int i = 0; i < (int)out.size() && i < cap; ++i) { sel_out[3 * i] = (int)out[i].x; sel_out[3 * i + 1] = (int)out[i].y; sel_out[3 * i + 2] = (int)out[i].response; }
+    if (trace_out) std::memcpy(trace_out, &tr, sizeof(tr));
+    return (int)out.size();
 }
 
 int orc_set_gauss_variant(int v) { const int old = g_gaussVariant; g_gaussVariant = v == 1 ? 1 : 0; return old; }

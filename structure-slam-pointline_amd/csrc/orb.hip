@@ -959,9 +959,17 @@ static std::vector<int> blur_taps_q8(int n, double sigma) {
     return t;
 }
 
+// k_octree's node capacity and dynamic LDS for a plan: what the launch asks for and what build_plan holds against the device's limit
+static void octree_lds(const Plan& P, int& NC, int& NCp2, size_t& lds) {
+    NC = P.maxNodeCap + 2; NCp2 = 1;
+    while (NCp2 < NC) NCp2 <<= 1;
+    lds = sizeof(unsigned long long) * 2 * (size_t)NCp2 + sizeof(int) * ((size_t)P.maxCellsLevel + 1) + sizeof(unsigned) * 5 * (size_t)NC;
+}
+
 static int build_plan(sslam_orb* o, int w, int h) {
     Plan& P = o->plan;
     memset(&P, 0, sizeof(P));
+    o->planW = o->planH = 0;      // (a size that is refused below leaves no plan behind: the next call builds one, whatever its size)
     P.nlevels = o->nlevels;
     o->cells.clear(); o->tabs.clear();
     size_t off = 0;
@@ -1058,6 +1066,20 @@ static int build_plan(sslam_orb* o, int w, int h) {
                 o->tabs.push_back(0);
             }
             while ((o->tabs.size() / 4) % 4) o->tabs.insert(o->tabs.end(), 4, (short)0);      // keep every tabX 32-byte aligned
+        }
+    }
+    {   // k_octree keeps its node list in LDS and a node's slot in 16 bits of the sort key (0xFFFF = nil): sizes it cannot take are refused here, before any launch
+        int lvl = 0;
+        for (int l = 1; l < o->nlevels; ++l) if (P.L[l].selCap > P.L[lvl].selCap) lvl = l;
+        int NC, NCp2; size_t lds;
+        octree_lds(P, NC, NCp2, lds);
+        if (NC > 0xFFFF) {
+            set_error("nfeatures %d: level %d would give the quadtree %d node slots (limit %d: 16-bit slot numbers)", o->nfeatures, lvl, NC, 0xFFFF); return SSLAM_ERR_UNSUPPORTED;
+        }
+        int ldsMax = 0;
+        SSLAM_HIP(hipDeviceGetAttribute(&ldsMax, hipDeviceAttributeMaxSharedMemoryPerBlock, o->ctx->device));
+        if (lds > (size_t)ldsMax) {
+            set_error("nfeatures %d: level %d (%d keypoints) needs %zu bytes of LDS for the quadtree, the device allows %d", o->nfeatures, lvl, P.L[lvl].nfeat, lds, ldsMax); return SSLAM_ERR_UNSUPPORTED;
         }
     }
     P.pyrFrame = (off + 16 + 255) & ~(size_t)255;      // 16 spare bytes: k_resize reads whole dwords past a row's last pixel
@@ -1162,15 +1184,9 @@ extern "C" int sslam_orb_max_keypoints(const sslam_orb* o) {
     return n;
 }
 
-extern "C" int sslam_orb_extract_batch_dev(sslam_orb* o, const uint8_t* d_images, int w, int h, size_t pitch, size_t image_stride,
-                                           int nframes, sslam_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int cap, void* stream_) {
-    if (!o || !d_images || !d_kp || !d_desc || !d_counts || w <= 0 || h <= 0 || nframes <= 0 || cap <= 0 || pitch < (size_t)w) {
-        set_error("sslam_orb_extract_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
-    }
-    if (nframes > 1 && image_stride < pitch * (size_t)(h - 1) + (size_t)w) { set_error("sslam_orb_extract_batch_dev: the frames overlap (image_stride < pitch * (h - 1) + w)"); return SSLAM_ERR_INVALID; }
-    std::lock_guard<std::recursive_mutex> lk(o->ctx->mu);      // plan, workspace and profile records are shared state
-    SSLAM_HIP(hipSetDevice(o->ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : o->ctx->stream;
+// What a batch call needs before its first launch: the plan of the image size, the blur taps and their matrix-core operands, the kernels' constants, a workspace of `nframes`
+// frames.  The caller holds the context's lock.  (sslam_orb_extract_batch_dev and, in the testing library, sslam_testing_orb_tail)
+static int orb_prepare(sslam_orb* o, int w, int h, int nframes, hipStream_t st) {
     int rc;
     if (w != o->planW || h != o->planH) {
         SSLAM_HIP(hipStreamSynchronize(st));
@@ -1213,8 +1229,11 @@ extern "C" int sslam_orb_extract_batch_dev(sslam_orb* o, const uint8_t* d_images
         o->constsUploaded = true;
     }
     if (nframes > o->wsFrames) { SSLAM_HIP(hipStreamSynchronize(st)); }
-    if ((rc = ensure_workspace(o, nframes))) return rc;
-    Plan P = o->plan;
+    return ensure_workspace(o, nframes);
+}
+
+// The front: level 0 (in place or copied), the resizes and FAST per cell.  P is the call's copy of the plan: the front binds the caller's image to it (Plan::img0).
+static int orb_front(sslam_orb* o, Plan& P, const uint8_t* d_images, int w, int h, size_t pitch, size_t image_stride, int nframes, hipStream_t st) {
     uint8_t* pyr = o->dPyr.as<uint8_t>();
     // level 0 in place when the caller's layout allows aligned dword loads (see Plan::img0)
     // The aligned dword reads of the kernels may touch the padding bytes [w, pitch) of a row: with padded rows the frames must therefore be whole pitch x h blocks
@@ -1248,10 +1267,18 @@ extern "C" int sslam_orb_extract_batch_dev(sslam_orb* o, const uint8_t* d_images
         { sslam::ProfScope _ps(o->ctx, "k_fast_cells", st); hipLaunchKernelGGL(k_fast_cells, grd, dim3(64), lds, st, pyr, P.pyrFrame, P, o->dCells.as<CellInfo>(), o->dCand.as<unsigned>(),
                            o->dCellCount.as<int>(), o->iniTh, o->minTh, tileP, scP); }
     }
+    return SSLAM_OK;
+}
+
+// The tail: the quadtree over the cells' candidates and the descriptors of what it keeps
+static int orb_tail(sslam_orb* o, const Plan& P, int nframes, hipStream_t st, sslam_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int cap, size_t* octreeLdsOut) {
+    uint8_t* pyr = o->dPyr.as<uint8_t>();
     {
-        int NC = P.maxNodeCap + 2, NCp2 = 1;
-        while (NCp2 < NC) NCp2 <<= 1;
-        size_t lds = sizeof(unsigned long long) * 2 * NCp2 + sizeof(int) * (P.maxCellsLevel + 1) + sizeof(unsigned) * 5 * (size_t)NC;
+        int NC, NCp2; size_t lds;
+        octree_lds(P, NC, NCp2, lds);
+        if (octreeLdsOut) *octreeLdsOut = lds;
+        // more dynamic LDS than the default 48 KB has to be allowed per kernel (build_plan has held the size against the device's limit)
+        if (lds > 48 * 1024) SSLAM_HIP(hipFuncSetAttribute((const void*)k_octree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         dim3 grd(P.nlevels, nframes);
         { sslam::ProfScope _ps(o->ctx, "k_octree", st); hipLaunchKernelGGL(k_octree, grd, dim3(64), lds, st, o->dCand.as<unsigned>(), o->dCellCount.as<int>(), o->dCells.as<CellInfo>(),
                            o->dBufA.as<unsigned>(), o->dBufB.as<unsigned>(), o->dSel.as<unsigned>(), o->dSelCount.as<int>(), P, NC, NCp2); }
@@ -1264,6 +1291,22 @@ extern "C" int sslam_orb_extract_batch_dev(sslam_orb* o, const uint8_t* d_images
     SSLAM_HIP(hipGetLastError());
     o->lastFrames = nframes;
     return SSLAM_OK;
+}
+
+extern "C" int sslam_orb_extract_batch_dev(sslam_orb* o, const uint8_t* d_images, int w, int h, size_t pitch, size_t image_stride,
+                                           int nframes, sslam_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int cap, void* stream_) {
+    if (!o || !d_images || !d_kp || !d_desc || !d_counts || w <= 0 || h <= 0 || nframes <= 0 || cap <= 0 || pitch < (size_t)w) {
+        set_error("sslam_orb_extract_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (nframes > 1 && image_stride < pitch * (size_t)(h - 1) + (size_t)w) { set_error("sslam_orb_extract_batch_dev: the frames overlap (image_stride < pitch * (h - 1) + w)"); return SSLAM_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lk(o->ctx->mu);      // plan, workspace and profile records are shared state
+    SSLAM_HIP(hipSetDevice(o->ctx->device));
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : o->ctx->stream;
+    int rc;
+    if ((rc = orb_prepare(o, w, h, nframes, st))) return rc;
+    Plan P = o->plan;
+    if ((rc = orb_front(o, P, d_images, w, h, pitch, image_stride, nframes, st))) return rc;
+    return orb_tail(o, P, nframes, st, d_kp, d_desc, d_counts, cap, nullptr);
 }
 
 extern "C" int sslam_orb_extract(sslam_orb* o, const uint8_t* gray, int w, int h, size_t stride,
@@ -1392,6 +1435,79 @@ extern "C" int sslam_orb_debug_blur_patches(sslam_orb* o, int frame, sslam_keypo
     if (n > cap) { set_error("sslam_orb_debug_blur_patches: %d keypoints exceed capacity %d", n, cap); return SSLAM_ERR_CAPACITY; }
     return SSLAM_OK;
 }
+
+#ifdef SSLAM_TESTING      // exists in libsslam_frontend_testing.so only (include/sslam_testing.h)
+// The ORB tail on candidates the caller supplies in place of k_fast_cells': preparation, front and tail are the product path's own functions; between front and tail the
+// cells' candidate lists and counts are overwritten (each level's list dealt into that level's cells in order, so that k_octree's gather returns it as given).
+extern "C" int sslam_testing_orb_tail(sslam_orb* o, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, const int32_t* cand,
+                                      const int32_t* ncand, int nmax, int cap, sslam_keypoint* kp_out, uint8_t* desc_out, int32_t* counts_out, int32_t* level_counts_out,
+                                      size_t* octree_lds_bytes_out) {
+    if (!o || !gray || !ncand || !kp_out || !desc_out || !counts_out || !level_counts_out || w <= 0 || h <= 0 || nframes <= 0 || nmax < 0 || cap <= 0 || stride < (size_t)w ||
+        (nmax > 0 && !cand)) {
+        set_error("sslam_testing_orb_tail: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (nframes > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w) { set_error("sslam_testing_orb_tail: the frames overlap"); return SSLAM_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lk(o->ctx->mu);
+    SSLAM_HIP(hipSetDevice(o->ctx->device));
+    hipStream_t st = o->ctx->stream;
+    int rc;
+    if ((rc = orb_prepare(o, w, h, nframes, st))) return rc;
+    Plan P = o->plan;
+    const int nl = P.nlevels;
+    // every check before any launch; the injected cell lists are built on the way
+    std::vector<unsigned> hCand((size_t)P.candFrame * nframes, 0u);
+    std::vector<int> hCount((size_t)std::max(P.nCellsFrame, 1) * nframes, 0);
+    std::vector<unsigned> seen;
+    for (int b = 0; b < nframes; ++b)
+        for (int l = 0; l < nl; ++l) {
+            const LevelInfo& L = P.L[l];
+            const int n = ncand[(size_t)b * nl + l];
+            if (n < 0 || n > nmax || n > L.candCap) { set_error("sslam_testing_orb_tail: frame %d level %d holds %d candidates (at most %d)", b, l, n, std::min(nmax, L.candCap)); return SSLAM_ERR_INVALID; }
+            const int32_t* c = cand + ((size_t)b * nl + l) * (size_t)nmax * 3;
+            seen.resize(n);
+            for (int i = 0; i < n; ++i) {
+                const int x = c[3 * i], y = c[3 * i + 1], s = c[3 * i + 2];
+                if (x < 0 || x >= L.W || y < 0 || y >= L.H || s < 1 || s > 255) { set_error("sslam_testing_orb_tail: frame %d level %d candidate %d = (%d, %d, %d) is outside the level (%d x %d) or the scores (1..255)", b, l, i, x, y, s, L.W, L.H); return SSLAM_ERR_INVALID; }
+                seen[i] = ((unsigned)y << 12) | (unsigned)x;
+            }
+            std::sort(seen.begin(), seen.end());
+            if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { set_error("sslam_testing_orb_tail: frame %d level %d holds two candidates at one pixel", b, l); return SSLAM_ERR_INVALID; }
+            int i = 0;
+            for (int k = 0; k < L.nCells && i < n; ++k) {
+                const CellInfo& ci = o->cells[L.cellBeg + k];
+                const int room = ((ci.x1 - ci.x0 + 1) / 2) * ((ci.y1 - ci.y0 + 1) / 2);
+                int m = 0;
+                for (; m < room && i < n; ++m, ++i) hCand[(size_t)b * P.candFrame + ci.candOff + m] = ((unsigned)c[3 * i + 2] << 24) | ((unsigned)c[3 * i + 1] << 12) | (unsigned)c[3 * i];
+                hCount[(size_t)b * P.nCellsFrame + L.cellBeg + k] = m;
+            }
+        }
+    const int icap = sslam_orb_max_keypoints(o);
+    const size_t dpitch = ((size_t)w + 63) & ~(size_t)63, dframe = dpitch * h, rows = (size_t)nframes * cap;
+    if ((rc = o->dImg.ensure(dframe * nframes))) return rc;
+    if ((rc = o->dKp.ensure(sizeof(sslam_keypoint) * std::max(rows, (size_t)icap)))) return rc;
+    if ((rc = o->dDesc.ensure(32 * std::max(rows, (size_t)icap)))) return rc;
+    if ((rc = o->dCounts.ensure(std::max<size_t>(16, sizeof(int32_t) * nframes)))) return rc;
+    o->lastN = -1;      // (the buffers of the last sslam_orb_extract are overwritten)
+    for (int b = 0; b < nframes; ++b)
+        SSLAM_HIP(hipMemcpy2DAsync(o->dImg.as<uint8_t>() + (size_t)b * dframe, dpitch, gray + (size_t)b * image_stride, stride, w, h, hipMemcpyHostToDevice, st));
+    if ((rc = orb_front(o, P, o->dImg.as<uint8_t>(), w, h, dpitch, dframe, nframes, st))) return rc;
+    SSLAM_HIP(hipMemcpyAsync(o->dCand.p, hCand.data(), sizeof(unsigned) * hCand.size(), hipMemcpyHostToDevice, st));
+    SSLAM_HIP(hipMemcpyAsync(o->dCellCount.p, hCount.data(), sizeof(int) * hCount.size(), hipMemcpyHostToDevice, st));
+    SSLAM_HIP(hipMemsetAsync(o->dKp.p, 0xA5, sizeof(sslam_keypoint) * rows, st));
+    SSLAM_HIP(hipMemsetAsync(o->dDesc.p, 0xA5, 32 * rows, st));
+    SSLAM_HIP(hipMemsetAsync(o->dCounts.p, 0xA5, sizeof(int32_t) * (size_t)nframes, st));
+    SSLAM_HIP(hipMemsetAsync(o->dSelCount.p, 0xA5, sizeof(int) * (size_t)nl * nframes, st));
+    size_t lds = 0;
+    if ((rc = orb_tail(o, P, nframes, st, o->dKp.as<sslam_keypoint>(), o->dDesc.as<uint8_t>(), o->dCounts.as<int32_t>(), cap, &lds))) return rc;
+    if (octree_lds_bytes_out) *octree_lds_bytes_out = lds;
+    SSLAM_HIP(hipMemcpyAsync(kp_out, o->dKp.p, sizeof(sslam_keypoint) * rows, hipMemcpyDeviceToHost, st));
+    SSLAM_HIP(hipMemcpyAsync(desc_out, o->dDesc.p, 32 * rows, hipMemcpyDeviceToHost, st));
+    SSLAM_HIP(hipMemcpyAsync(counts_out, o->dCounts.p, sizeof(int32_t) * (size_t)nframes, hipMemcpyDeviceToHost, st));
+    SSLAM_HIP(hipMemcpyAsync(level_counts_out, o->dSelCount.p, sizeof(int32_t) * (size_t)nl * nframes, hipMemcpyDeviceToHost, st));
+    SSLAM_HIP(hipStreamSynchronize(st));      // (hCand and hCount live until here)
+    return SSLAM_OK;
+}
+#endif      // SSLAM_TESTING
 
 // Keep the features of the last sslam_orb_extract call on the device as a frame handle (device-to-device snapshot of the
 // keypoints + descriptors the extractor still holds): the Frame that ExtractORB just filled never has to be uploaded

@@ -98,6 +98,49 @@ class Oracle:
         return int(self.L.orc_fast_score(_p(patch7)))
 
 
+# oracle/orb_oracle.cpp OctTrace: what a run of the quadtree went through, 64 ints per level
+OCT_TRACE = ("end", "final_nodes", "rounds1", "rounds2", "rounds2_no_break", "max_divided", "div_small", "div_large", "div_empty_class", "div_large_empty_class",
+             "div64", "div65", "div128", "div129", "tie_nodes", "equal_pairs", "max_all_equal", "n_sorted")
+END_FIRST_N, END_FIRST_NO_GROWTH, END_SECOND_BREAK, END_SECOND_ROUND = range(4)
+
+
+def _trace(t):
+    """one level's 64 ints -> dict of the named fields plus `sorted` = the lengths of the lists the second phase sorted (the first 46)"""
+    d = {k: int(v) for k, v in zip(OCT_TRACE, t)}
+    d["sorted"] = [int(v) for v in t[len(OCT_TRACE):len(OCT_TRACE) + min(d["n_sorted"], 64 - len(OCT_TRACE))]]
+    return d
+
+
+def _orc_orb_tail_methods():
+    def orb_tail(self, gray, cands, nfeatures, scale=1.2, nlevels=1, cap=None):
+        """orc_orb_extract with the FAST candidates of every level replaced by cands[level] (n x 3: x, y, score relative to minBorder, arrival order)
+        -> (keypoints, descriptors: min(total, cap) rows each; level counts; total; one trace dict per level)"""
+        gray = np.ascontiguousarray(gray, np.uint8); h, w = gray.shape
+        assert len(cands) == nlevels
+        nmax = max(max(len(c) for c in cands), 1)
+        cand = np.zeros((nlevels, nmax, 3), np.int32); nc = np.zeros(nlevels, np.int32)
+        for l, c in enumerate(cands):
+            c = np.asarray(c, np.int32).reshape(-1, 3); cand[l, :len(c)] = c; nc[l] = len(c)
+        rows = int(nc.sum()) + 8 if cap is None else max(int(cap), 1)
+        kp = np.zeros(rows, KP_DTYPE); desc = np.zeros((rows, 32), np.uint8); lc = np.zeros(nlevels, np.int32); tr = np.zeros((nlevels, 64), np.int32)
+        n = self.L.orc_orb_tail(_p(gray), w, h, gray.strides[0], int(nfeatures), C.c_float(scale), int(nlevels), _p(cand), _p(nc), nmax, _p(kp), _p(desc), rows, _p(lc), _p(tr))
+        assert n >= 0, "orc_orb_tail: a candidate outside its level or the scores 1..255"
+        m = min(n, rows)
+        return kp[:m].copy(), desc[:m].copy(), lc, n, [_trace(t) for t in tr]
+
+    def distribute_octtree(self, cand, W, H, N):
+        """the quadtree alone on one level's candidates (n x 3) -> (what it keeps: m x 3 in order, trace dict)"""
+        cand = np.ascontiguousarray(np.asarray(cand, np.int32).reshape(-1, 3))
+        sel = np.zeros((len(cand) + 1, 3), np.int32); tr = np.zeros(64, np.int32)
+        m = self.L.orc_distribute_octtree(_p(cand), len(cand), int(W), int(H), int(N), _p(sel), len(sel), _p(tr))
+        return sel[:m].copy(), _trace(tr)
+
+    Oracle.orb_tail = orb_tail; Oracle.distribute_octtree = distribute_octtree
+
+
+_orc_orb_tail_methods()
+
+
 def _orc_match_methods():
     def descriptor_distance(self, a, b):
         a = np.ascontiguousarray(a, np.uint8); b = np.ascontiguousarray(b, np.uint8)
