@@ -306,6 +306,20 @@ int sslam_bow_transform(sslam_ctx* ctx, const sslam_vocab* vocab, const uint8_t*
                         int32_t* word_out, double* weight_out, int32_t* node_out);
 int sslam_bow_transform_frame(sslam_ctx* ctx, const sslam_vocab* vocab, const sslam_frame* frame, int levelsup,
                               int32_t* word_out, double* weight_out, int32_t* node_out);
+/* The same descent (TemplatedVocabulary.h:1216-1259) for `nframes` frames whose descriptors are already on the device, asynchronously: what
+ * Frame::ComputeBoW (src/Tracking.cc:1012, :1967) needs of every frame before SearchByBoW, for callers that extract many sessions' frames in
+ * one launch.  The layout is the batch extractors': frame f owns rows [f*cap, f*cap + d_n[f]) of d_desc (32 bytes per row), so the descriptor
+ * buffer of sslam_orb_extract_batch_dev is the input without a copy.  A count below 0 is read as 0, one above cap as cap.  Per valid row
+ * d_word / d_weight / d_node receive what sslam_bow_transform writes for that descriptor (the first child with the smallest distance wins; the
+ * node is 0 when the word lies above level m_L - levelsup); rows at or past a frame's count are not touched.  d_word and d_weight may each be
+ * NULL, d_node may not: sslam_orb_search_by_bow_batch_dev below takes d_node as it is.  BowVector, its normalisation and score() are not part
+ * of this call (sslam_compute_bow).
+ * Every pointer but vocab is a device pointer; d_desc is 16-byte aligned.  One launch on `stream` (NULL: the context's stream), no scratch, no
+ * synchronise, no host memory read or written.  SSLAM_ERR_INVALID (nothing enqueued): a NULL vocab, d_desc, d_n or d_node, a vocabulary of
+ * another context, a negative cap, nframes or levelsup, nframes * cap >= 2^31, a misaligned buffer.  nframes == 0 is SSLAM_OK and enqueues
+ * nothing. */
+int sslam_bow_transform_batch_dev(sslam_ctx* ctx, const sslam_vocab* vocab, const uint8_t* d_desc, const int32_t* d_n, int cap, int nframes,
+                                  int levelsup, int32_t* d_word, double* d_weight, int32_t* d_node, void* stream);
 
 /* ORBVocabulary::loadFromTextFile (src/System.cc:64-73 -> TemplatedVocabulary.h:1338-1423): first line "k L scoring weighting"
  * (rejected outside 0<=k<=20, 1<=L<=10, 0<=scoring<=5, 0<=weighting<=3, as the reference does), then one line per node in id order
@@ -344,6 +358,29 @@ int sslam_orb_search_by_bow(sslam_ctx* ctx, const sslam_keypoint* kf_kp, const u
                             const int32_t* node_kf_ptr, const int32_t* node_f_ptr, int nnodes,
                             const int32_t* kf_idx, const int32_t* f_idx, float nnratio, int check_orientation,
                             int32_t* assigned_out, int* nmatches_out);
+/* The same matcher (src/ORBmatcher.cc:159-291, the KeyFrame -> Frame overload only) for `npairs` pairs of device-resident frames,
+ * asynchronously, from per-feature node ids instead of CSR lists: the batch form of Tracking::TrackReferenceKeyFrame (src/Tracking.cc:1009-1020,
+ * one reference keyframe per session) and of Tracking::Relocalization (src/Tracking.cc:1964-1996, one frame against K candidate keyframes).
+ * Keyframe slot k owns rows [k*kfcap, k*kfcap + d_nkf[k]) of d_kf_kp, d_kf_desc (32 bytes per row), d_kf_node and d_kf_valid
+ * (= vpMapPointsKF[i] && !isBad()); frame slot f owns rows [f*cap, f*cap + d_nf[f]) of d_f_kp, d_f_desc and d_f_node.  A count below 0 is read
+ * as 0, one above its capacity as the capacity.  The node arrays are what sslam_bow_transform_batch_dev writes to d_node.
+ * Pair p matches keyframe slot d_pair_kf[p] against frame slot d_pair_f[p]; either array may be NULL, which means slot p and requires that side's
+ * slot count to equal npairs.  A slot may appear in any number of pairs (Relocalization: every pair names the one frame slot).  A pair with a
+ * slot index outside its range is skipped: d_nmatches[p] = 0 and nothing else of the pair is written.
+ * Pair p yields what sslam_orb_search_by_bow returns for the two FeatureVectors that FeatureVector::addFeature(node[i], i) builds in feature
+ * order: the nodes are the ids >= 0 present on both sides; inside a node both sides are taken in ascending index; a row with a node id below 0
+ * is in no node.  d_assigned[p*cap + j], j < nf, = the keyframe feature matched to frame feature j, or -1 (also after the rotation check);
+ * rows at or past the frame's count are not touched.  d_nmatches[p] = the count after the rotation pruning.
+ * Every pointer is a device pointer; the descriptor buffers are 16-byte aligned.  One launch on `stream` (NULL: the context's stream), no
+ * scratch, no synchronise, no host memory read or written.  SSLAM_ERR_INVALID (nothing enqueued): a NULL (other than the pair arrays) or
+ * misaligned buffer, a negative size, kfcap or cap >= 2^19, a NULL pair array whose side has another slot count than npairs.  npairs == 0 is
+ * SSLAM_OK and enqueues nothing. */
+int sslam_orb_search_by_bow_batch_dev(sslam_ctx* ctx,
+                                      const sslam_keypoint* d_kf_kp, const uint8_t* d_kf_desc, const int32_t* d_kf_node, const uint8_t* d_kf_valid,
+                                      const int32_t* d_nkf, int kfcap, int nkeyframes,
+                                      const sslam_keypoint* d_f_kp, const uint8_t* d_f_desc, const int32_t* d_f_node, const int32_t* d_nf, int cap, int nframes,
+                                      const int32_t* d_pair_kf, const int32_t* d_pair_f, int npairs,
+                                      float nnratio, int check_orientation, int32_t* d_assigned, int32_t* d_nmatches, void* stream);
 
 /* ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12), src/ORBmatcher.cc:525-658 (loop closing,
  * src/LoopClosing.cc:271): same node walk; kfX_valid[i] = vpMapPointsX[i] && !isBad(); a candidate of the second keyframe is skipped

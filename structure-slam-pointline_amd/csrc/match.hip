@@ -743,7 +743,7 @@ static int bow_core(sslam_ctx* ctx, const sslam_vocab* v, const uint8_t* d_desc,
     if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
     uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
     { sslam::ProfScope _ps(ctx, "k_bow_transform", st);
-      hipLaunchKernelGGL(k_bow_transform, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, n, v->childPtr.as<int>(), v->children.as<int>(), v->desc.as<uint8_t>(),
+      hipLaunchKernelGGL(k_bow_transform, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, n, (const int*)nullptr, n, v->childPtr.as<int>(), v->children.as<int>(), v->desc.as<uint8_t>(),
                          v->wordId.as<int>(), v->weight.as<double>(), v->levels - levelsup, (int*)(B + oW), (double*)(B + oV), (int*)(B + oN)); }
     SSLAM_HIP(hipGetLastError());
     SSLAM_HIP(hipMemcpyAsync(word_out, B + oW, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -776,4 +776,65 @@ extern "C" int sslam_bow_transform(sslam_ctx* ctx, const sslam_vocab* vocab, con
     if ((rc = ctx->scratch[SCR_UPLOAD].ensure(32 * (size_t)n))) return rc;
     SSLAM_HIP(hipMemcpyAsync(ctx->scratch[SCR_UPLOAD].p, desc, 32 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     return bow_core(ctx, vocab, ctx->scratch[SCR_UPLOAD].as<uint8_t>(), n, levelsup, word_out, weight_out, node_out);
+}
+
+// ---- the descent for B frames that are already on the device (the batch extractors' descriptor buffer), asynchronous: one launch, no scratch
+extern "C" int sslam_bow_transform_batch_dev(sslam_ctx* ctx, const sslam_vocab* vocab, const uint8_t* d_desc, const int32_t* d_n, int cap, int nframes,
+                                             int levelsup, int32_t* d_word, double* d_weight, int32_t* d_node, void* stream) {
+    const uintptr_t align4 = (uintptr_t)d_n | (uintptr_t)d_word | (uintptr_t)d_node;
+    if (!ctx || !vocab || vocab->ctx != ctx || !d_desc || !d_n || !d_node || cap < 0 || nframes < 0 || levelsup < 0 || (long long)nframes * (long long)cap >= (1ll << 31) ||
+        ((uintptr_t)d_desc & 15) || (align4 & 3) || ((uintptr_t)d_weight & 7)) {
+        set_error("sslam_bow_transform_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    const int rows = nframes * cap;
+    if (rows == 0) return SSLAM_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    SSLAM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    { sslam::ProfScope _ps(ctx, "k_bow_transform", st);
+      hipLaunchKernelGGL(k_bow_transform, dim3(((unsigned)rows + 255u) / 256u), dim3(256), 0, st, d_desc, rows, d_n, cap, vocab->childPtr.as<int>(), vocab->children.as<int>(),
+                         vocab->desc.as<uint8_t>(), vocab->wordId.as<int>(), vocab->weight.as<double>(), vocab->levels - levelsup, d_word, d_weight, d_node); }
+    SSLAM_HIP(hipGetLastError());
+    return SSLAM_OK;
+}
+
+// ---- SearchByBoW for pairs of frames that are already on the device, from per-feature node ids (sslam_bow_transform_batch_dev), asynchronous
+extern "C" int sslam_orb_search_by_bow_batch_dev(sslam_ctx* ctx,
+        const sslam_keypoint* d_kf_kp, const uint8_t* d_kf_desc, const int32_t* d_kf_node, const uint8_t* d_kf_valid, const int32_t* d_nkf, int kfcap, int nkeyframes,
+        const sslam_keypoint* d_f_kp, const uint8_t* d_f_desc, const int32_t* d_f_node, const int32_t* d_nf, int cap, int nframes,
+        const int32_t* d_pair_kf, const int32_t* d_pair_f, int npairs,
+        float nnratio, int check_orientation, int32_t* d_assigned, int32_t* d_nmatches, void* stream) {
+    const uintptr_t align4 = (uintptr_t)d_kf_kp | (uintptr_t)d_kf_node | (uintptr_t)d_nkf | (uintptr_t)d_f_kp | (uintptr_t)d_f_node | (uintptr_t)d_nf | (uintptr_t)d_pair_kf |
+                             (uintptr_t)d_pair_f | (uintptr_t)d_assigned | (uintptr_t)d_nmatches;
+    const uintptr_t align16 = (uintptr_t)d_kf_desc | (uintptr_t)d_f_desc;      // descriptor rows are read as two 16-byte words
+    if (!ctx || !d_kf_kp || !d_kf_desc || !d_kf_node || !d_kf_valid || !d_nkf || !d_f_kp || !d_f_desc || !d_f_node || !d_nf || !d_assigned || !d_nmatches ||
+        kfcap < 0 || kfcap >= (1 << 19) || cap < 0 || cap >= (1 << 19) || nkeyframes < 0 || nframes < 0 || npairs < 0 || (align4 & 3) || (align16 & 15) ||
+        (!d_pair_kf && nkeyframes != npairs) || (!d_pair_f && nframes != npairs)) {
+        set_error("sslam_orb_search_by_bow_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (npairs == 0) return SSLAM_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    SSLAM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    const BowBatchPlan P = bow_batch_plan(cap, npairs);      // match_plan.h: the frame side in LDS or in global memory, by the row capacity alone
+    BowBatchArgs A;
+    A.kpKF = d_kf_kp; A.dKF = d_kf_desc; A.nodeKF = d_kf_node; A.validKF = d_kf_valid; A.nKF = d_nkf; A.kfcap = kfcap; A.nkeyframes = nkeyframes;
+    A.kpF = d_f_kp; A.dF = d_f_desc; A.nodeF = d_f_node; A.nF = d_nf; A.cap = cap; A.nframes = nframes;
+    A.pairKF = d_pair_kf; A.pairF = d_pair_f; A.nnratio = nnratio; A.checkOri = check_orientation; A.assigned = d_assigned; A.nmatches = d_nmatches;
+    switch (P.form) {
+    case BowBatchForm::Lds: {
+        int rc;
+        if ((rc = allow_dynamic_lds((const void*)k_search_bow_batch<true>, P.ldsBytes))) return rc;
+        sslam::ProfScope _ps(ctx, "k_search_bow_batch", st);
+        hipLaunchKernelGGL(k_search_bow_batch<true>, dim3(P.grid), dim3(P.threads), P.ldsBytes, st, A);
+        break;
+    }
+    case BowBatchForm::Global: {
+        sslam::ProfScope _ps(ctx, "k_search_bow_batch", st);
+        hipLaunchKernelGGL(k_search_bow_batch<false>, dim3(P.grid), dim3(P.threads), 0, st, A);
+        break;
+    }
+    }
+    SSLAM_HIP(hipGetLastError());
+    return SSLAM_OK;
 }

@@ -179,11 +179,19 @@ __global__ __launch_bounds__(256) void k_tri_finish(int* __restrict__ m12, const
 // TemplatedVocabulary::transform(feature, word_id, weight, nid, levelsup), Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1216-1259:
 // from the root, move to the child with the smallest Hamming distance (the FIRST such child: `d < best_d`) until a leaf;
 // remember the node passed at level L - levelsup.  Features are independent: one lane per feature.
-__global__ __launch_bounds__(256) void k_bow_transform(const uint8_t* __restrict__ feat, int n, const int* __restrict__ childPtr, const int* __restrict__ children,
+// n rows in all (< 2^31).  The batch call (sslam_bow_transform_batch_dev) passes the per-frame counts: row i is row i % cap of frame i / cap, and
+// the rows at or past the frame's count (clamped to [0, cap]) are left alone; counts == nullptr: the single call, every row < n is a feature.
+// wordOut / weightOut may be null (the batch call's optional outputs).
+__global__ __launch_bounds__(256) void k_bow_transform(const uint8_t* __restrict__ feat, int n, const int* __restrict__ counts, int cap,
+                                                       const int* __restrict__ childPtr, const int* __restrict__ children,
                                                        const uint8_t* __restrict__ nodeDesc, const int* __restrict__ wordId, const double* __restrict__ weight,
                                                        int nidLevel, int* __restrict__ wordOut, double* __restrict__ weightOut, int* __restrict__ nodeOut) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)n) return;
+    if (counts) {
+        const unsigned f = i / (unsigned)cap;
+        if ((int)(i - f * (unsigned)cap) >= min(max(counts[f], 0), cap)) return;
+    }
     const uint4 q0 = ((const uint4*)(feat + (size_t)i * 32))[0], q1 = ((const uint4*)(feat + (size_t)i * 32))[1];
     int node = 0, level = 0, nid = 0;
     while (childPtr[node + 1] > childPtr[node]) {
@@ -201,7 +209,9 @@ __global__ __launch_bounds__(256) void k_bow_transform(const uint8_t* __restrict
         node = best;
         if (level == nidLevel) nid = node;
     }
-    wordOut[i] = wordId[node]; weightOut[i] = weight[node]; nodeOut[i] = nid;
+    if (wordOut) wordOut[i] = wordId[node];
+    if (weightOut) weightOut[i] = weight[node];
+    nodeOut[i] = nid;
 }
 
 // ------------------------------------------------------------------ distinctive descriptor of an observation set

@@ -1052,3 +1052,125 @@ __global__ __launch_bounds__(256) void k_bow_finish(int* __restrict__ assigned, 
     __syncthreads();
     if (t == 0) *nmatches = total;
 }
+
+// ---------------------------------------------------------------- SearchByBoW of a batch (sslam_orb_search_by_bow_batch_dev)
+// The same matcher on per-feature NODE IDS instead of CSR lists, for pairs of device-resident frames: no sort, no scratch, no traffic between
+// workgroups.  One workgroup of BOW_BATCH_WAVES waves per pair (match_plan.h); wave w owns the nodes with node % BOW_BATCH_WAVES == w, so
+// every frame row -- it has one node -- is read and written as "taken" by one wave only, and the waves never wait for each other while they walk.
+// A wave walks the keyframe rows in ascending index, 64 node ids per ballot, and takes the rows that are valid and of a node it owns in
+// bit order; for each it scans the frame side for rows of that node that are still free, with the frame index in the reduction key: inside a
+// node both sides are visited in ascending index, which is the order of the lists FeatureVector::addFeature builds.  A node id below 0 is in no
+// node on either side.  After the one barrier behind the walk the workgroup builds the rotation histogram -- the bin is recomputed from
+// assigned[j] and the two angles -- prunes, counts and writes the pair's rows.
+// Every loop is bounded by a clamped count, a ballot's set bits or a constant: bytes past a count are never read.
+struct BowBatchArgs {
+    const sslam_keypoint* kpKF; const uint8_t* dKF; const int* nodeKF; const uint8_t* validKF; const int* nKF; int kfcap, nkeyframes;
+    const sslam_keypoint* kpF; const uint8_t* dF; const int* nodeF; const int* nF; int cap, nframes;
+    const int* pairKF; const int* pairF;      // null: slot p
+    float nnratio; int checkOri;
+    int* assigned; int* nmatches;
+};
+__device__ __forceinline__ int bow_rot_bin(float angleKF, float angleF) {
+    float rot = __fsub_rn(angleKF, angleF);
+    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+    int bin = (int)roundf(__fmul_rn(rot, 1.0f / HISTO_LENGTH));
+    if (bin == HISTO_LENGTH) bin = 0;
+    return min(max(bin, 0), HISTO_LENGTH - 1);      // angles of [0, 360) never need it; the histogram index stays in range whatever a row holds
+}
+// kLds: the frame side in dynamic LDS -- descriptors [2 cap] uint4, node ids [cap], live assignment [cap] (BOW_BATCH_ROW_BYTES per row);
+// otherwise descriptors and node ids in the caller's buffers and the live assignment in the pair's output rows
+template <bool kLds>
+__global__ __launch_bounds__(64 * BOW_BATCH_WAVES) void k_search_bow_batch(BowBatchArgs A) {
+    extern __shared__ __align__(16) unsigned bwl[];
+    __shared__ int hist[HISTO_LENGTH];
+    __shared__ int keep[3];
+    __shared__ int total;
+    constexpr int NT = 64 * BOW_BATCH_WAVES;
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int k = A.pairKF ? A.pairKF[p] : p, f = A.pairF ? A.pairF[p] : p;
+    if (k < 0 || k >= A.nkeyframes || f < 0 || f >= A.nframes) {      // (uniform over the workgroup, ahead of every barrier)
+        if (tid == 0) A.nmatches[p] = 0;
+        return;
+    }
+    const int nkf = min(max(A.nKF[k], 0), A.kfcap), nf = min(max(A.nF[f], 0), A.cap);
+    const size_t rk = (size_t)k * (size_t)A.kfcap, rf = (size_t)f * (size_t)A.cap;
+    const sslam_keypoint* kpKF = A.kpKF + rk; const uint8_t* dKF = A.dKF + rk * 32; const int* nodeKF = A.nodeKF + rk; const uint8_t* validKF = A.validKF + rk;
+    const sslam_keypoint* kpF = A.kpF + rf;
+    int* out = A.assigned + (size_t)p * (size_t)A.cap;
+    const uint4* fdesc; const int* fnode; int* asg;
+    if (kLds) {
+        uint4* ld = (uint4*)bwl; int* ln = (int*)(ld + 2 * (size_t)A.cap); int* la = ln + A.cap;
+        const uint4* gd = (const uint4*)(A.dF + rf * 32);
+        for (int j = tid; j < 2 * nf; j += NT) ld[j] = gd[j];
+        for (int j = tid; j < nf; j += NT) { ln[j] = A.nodeF[rf + j]; la[j] = -1; }
+        fdesc = ld; fnode = ln; asg = la;
+    } else {
+        for (int j = tid; j < nf; j += NT) out[j] = -1;
+        fdesc = (const uint4*)(A.dF + rf * 32); fnode = A.nodeF + rf; asg = out;
+    }
+    if (tid < HISTO_LENGTH) hist[tid] = 0;
+    if (tid == 0) total = 0;
+    __syncthreads();
+    // the walk: no workgroup barrier in here (the waves' trip counts differ); a taken flag is written and read by one wave only
+    for (int i0 = 0; i0 < nkf; i0 += 64) {
+        const int i = i0 + lane;
+        int nd = -1; bool own = false;
+        if (i < nkf) { nd = nodeKF[i]; own = nd >= 0 && validKF[i] != 0 && (nd % BOW_BATCH_WAVES) == wave; }
+        unsigned long long todo = __ballot(own);
+        while (todo) {
+            const int bit = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int ik = i0 + bit;
+            const int node = __builtin_amdgcn_readlane(nd, bit);
+            const uint4 q0 = ((const uint4*)(dKF + (size_t)ik * 32))[0], q1 = ((const uint4*)(dKF + (size_t)ik * 32))[1];
+            unsigned long long b = ~0ull, s = ~0ull;
+            for (int j = lane; j < nf; j += 64) {
+                if (fnode[j] != node) continue;
+                if (__hip_atomic_load(&asg[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= 0) continue;      // already matched (:216-217)
+                const unsigned long long kk = ((unsigned long long)hamming256(q0, q1, fdesc[2 * j], fdesc[2 * j + 1]) << 32) | (unsigned)j;
+                if (kk < b) { s = b; b = kk; } else if (kk < s) s = kk;
+            }
+            const unsigned long long best = wave_min_u64(b);
+            const unsigned long long second = wave_min_u64(b == best ? s : b);
+            int bestDist1 = 256, bestDist2 = 256, bestIdxF = -1;
+            if (best != ~0ull) { bestDist1 = (int)(best >> 32); bestIdxF = (int)(unsigned)best; }
+            if (second != ~0ull) bestDist2 = (int)(second >> 32);
+            if (bestIdxF >= 0 && bestDist1 <= TH_LOW && (float)bestDist1 < __fmul_rn(A.nnratio, (float)bestDist2)) {
+                if (lane == 0) __hip_atomic_store(&asg[bestIdxF], ik, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // the wave's next keyframe row of this node must see the assignment
+            }
+        }
+    }
+    __syncthreads();
+    if (A.checkOri) {
+        for (int j = tid; j < nf; j += NT) {
+            const int a = asg[j];
+            if (a >= 0) atomicAdd(&hist[bow_rot_bin(kpKF[a].angle, kpF[j].angle)], 1);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;      // ComputeThreeMaxima
+            for (int i = 0; i < HISTO_LENGTH; ++i) {
+                const int c = hist[i];
+                if (c > max1) { max3 = max2; max2 = max1; max1 = c; ind3 = ind2; ind2 = ind1; ind1 = i; }
+                else if (c > max2) { max3 = max2; max2 = c; ind3 = ind2; ind2 = i; }
+                else if (c > max3) { max3 = c; ind3 = i; }
+            }
+            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
+            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+            keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
+        }
+        __syncthreads();
+    }
+    int cnt = 0;
+    for (int j = tid; j < nf; j += NT) {
+        int a = asg[j];
+        if (a >= 0 && A.checkOri) { const int bn = bow_rot_bin(kpKF[a].angle, kpF[j].angle); if (bn != keep[0] && bn != keep[1] && bn != keep[2]) a = -1; }
+        cnt += a >= 0;
+        out[j] = a;
+    }
+    cnt = wave_sum(cnt);
+    if (lane == 0 && cnt) atomicAdd(&total, cnt);
+    __syncthreads();
+    if (tid == 0) A.nmatches[p] = total;
+}

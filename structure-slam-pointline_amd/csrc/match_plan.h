@@ -152,6 +152,36 @@ inline ProjBatchArena proj_batch_arena(int cap, int qcap, int slice, int projK) 
     return a;
 }
 
+// -------------------------------------------------------------- SearchByBoW of a batch (sslam_orb_search_by_bow_batch_dev)
+// One workgroup of BOW_BATCH_WAVES waves per (keyframe slot, frame slot) pair -- k_search_bow_batch; wave w owns the vocabulary nodes with
+// node % BOW_BATCH_WAVES == w.  The form follows the FRAME side's row capacity alone (every pair of a launch runs the same kernel):
+//   Lds     the frame side of the pair sits in the workgroup's LDS: 32 bytes of descriptor, the node id and the live assignment per row,
+//           BOW_BATCH_ROW_BYTES * cap bytes in all, while that is at most BOW_BATCH_LDS_MAX (64 KB: two pairs per compute unit at the bound, three
+//           at 1000 rows); more than DYNAMIC_LDS_DEFAULT_MAX needs the per-kernel opt-in
+//   Global  beyond that: the same kernel reads descriptors and node ids from the caller's buffers and keeps the live assignment in d_assigned
+// No scratch: every byte of a pair's state is in its workgroup's LDS or in the pair's own output rows.
+constexpr int BOW_BATCH_WAVES = 8;
+constexpr int BOW_BATCH_ROW_BYTES = 40;
+constexpr size_t BOW_BATCH_LDS_MAX = 64 * 1024;
+enum class BowBatchForm { Lds, Global };
+struct BowBatchPlan {
+    BowBatchForm form;
+    size_t ldsBytes;          // dynamic LDS per workgroup (0: Global)
+    int ldsOptIn;             // ldsBytes is more than a launch may ask for without hipFuncSetAttribute
+    unsigned threads;         // workgroup size
+    unsigned grid;            // workgroups: one per pair
+};
+inline BowBatchPlan bow_batch_plan(int cap, int npairs) {
+    BowBatchPlan P{};
+    const size_t lds = (size_t)BOW_BATCH_ROW_BYTES * (size_t)cap;
+    P.form = lds <= BOW_BATCH_LDS_MAX ? BowBatchForm::Lds : BowBatchForm::Global;
+    P.ldsBytes = P.form == BowBatchForm::Lds ? lds : 0;
+    P.ldsOptIn = P.ldsBytes > DYNAMIC_LDS_DEFAULT_MAX ? 1 : 0;
+    P.threads = 64u * BOW_BATCH_WAVES;
+    P.grid = (unsigned)npairs;
+    return P;
+}
+
 // arena of search_proj_core.  occ | q | qdesc go up in ONE copy (occ .. assigned), assigned | count come back in one (assigned .. count + 4);
 // only that head (.. count + 256) has a pinned mirror.  projK = list length of k_proj_topk (PROJ_K).
 struct ProjArena {

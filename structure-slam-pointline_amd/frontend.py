@@ -192,6 +192,23 @@ class Context:
                                            _p(assigned), C.byref(nm)))
         return assigned, nm.value
 
+    def bow_transform_batch_dev(self, vocab, d_desc, d_n, cap, nframes, d_node, d_word=None, d_weight=None, levelsup=4, stream=None):
+        """sslam_bow_transform_batch_dev on device tensors / pointers laid out like sslam_orb_extract_batch_dev's descriptors (rows f*cap ..): per valid
+        row the node at level L - levelsup into d_node (int32) and, where given, the word into d_word (int32) and its weight into d_weight (float64);
+        enqueues on `stream` (None: the context's) and returns without synchronising"""
+        _chk(lib().sslam_bow_transform_batch_dev(self.h, vocab.h if vocab is not None else None, _p(d_desc), _p(d_n), int(cap), int(nframes), int(levelsup),
+                                                 _p(d_word), _p(d_weight), _p(d_node), C.c_void_p(stream or 0)))
+
+    def search_by_bow_batch_dev(self, d_kf_kp, d_kf_desc, d_kf_node, d_kf_valid, d_nkf, kfcap, nkeyframes, d_f_kp, d_f_desc, d_f_node, d_nf, cap, nframes,
+                                npairs, d_assigned, d_nmatches, d_pair_kf=None, d_pair_f=None, nnratio=0.9, check_orientation=True, stream=None):
+        """sslam_orb_search_by_bow_batch_dev on device tensors / pointers: pair p matches keyframe slot d_pair_kf[p] (None: p) against frame slot
+        d_pair_f[p] (None: p) from the per-feature node ids of bow_transform_batch_dev; d_assigned [npairs, cap] int32, d_nmatches [npairs] int32;
+        enqueues on `stream` (None: the context's) and returns without synchronising"""
+        _chk(lib().sslam_orb_search_by_bow_batch_dev(self.h, _p(d_kf_kp), _p(d_kf_desc), _p(d_kf_node), _p(d_kf_valid), _p(d_nkf), int(kfcap), int(nkeyframes),
+                                                     _p(d_f_kp), _p(d_f_desc), _p(d_f_node), _p(d_nf), int(cap), int(nframes), _p(d_pair_kf), _p(d_pair_f),
+                                                     int(npairs), C.c_float(nnratio), int(bool(check_orientation)), _p(d_assigned), _p(d_nmatches),
+                                                     C.c_void_p(stream or 0)))
+
     def search_by_bow_keyframes(self, kp1, d1, valid1, kp2, d2, valid2, ptr1, ptr2, idx1, idx2, nnratio=0.8, check_orientation=True):
         """ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (src/ORBmatcher.cc:525-658): -> (matches12, nmatches)"""
         kp1 = np.ascontiguousarray(kp1); kp2 = np.ascontiguousarray(kp2)

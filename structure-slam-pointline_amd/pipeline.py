@@ -163,6 +163,36 @@ class FrontendBatch:
         cur.wait_stream(s1)
         return assigned, nm
 
+    def search_by_bow(self, vocab, kf_valid=None, nnratio=0.9, check_orientation=True, levelsup=4):
+        """Tracking::TrackReferenceKeyFrame's matching (src/Tracking.cc:1009-1020) for the B sessions of the batch: the vocabulary descent
+        (sslam_bow_transform_batch_dev) of the `prev` and the `cur` extraction, then SearchByBoW (sslam_orb_search_by_bow_batch_dev) with frame i of
+        `prev` as the keyframe of frame i of `cur`.  vocab: a Vocabulary of this context; kf_valid: uint8 [B, cap], which `prev` keypoints own a good
+        map point (None: all of them).  Runs on the pipeline's point stream; the caller's current stream is ordered before and after.  Returns the
+        [B, cap] assigned tensor (the `prev` keypoint matched to each `cur` keypoint, or -1) and the [B] match counts, both owned by the pipeline:
+        the next call overwrites them; rows at or past a frame's count are not written."""
+        p, c = self.feat["prev"], self.feat["cur"]
+        B, cap = self.B, self.cap
+        assert kf_valid is None or (kf_valid.is_cuda and kf_valid.dtype == torch.uint8 and kf_valid.shape == (B, cap) and kf_valid.is_contiguous())
+        if not hasattr(self, "_bow"):          # on first use: a pipeline that never calls this holds no memory for it
+            self._bow = dict(node_kf=torch.zeros(B, cap, dtype=torch.int32, device=self.dev), node_f=torch.zeros(B, cap, dtype=torch.int32, device=self.dev),
+                             all_valid=torch.ones(B, cap, dtype=torch.uint8, device=self.dev),
+                             assigned=torch.full((B, cap), -1, dtype=torch.int32, device=self.dev), nm=torch.zeros(B, dtype=torch.int32, device=self.dev))
+        w = self._bow
+        valid = w["all_valid"] if kf_valid is None else kf_valid
+        s1, _ = self._streams()
+        cur = torch.cuda.current_stream(self.dev)
+        s1.wait_stream(cur)
+        with torch.cuda.stream(s1):
+            st = self._stream()
+            self.ctx.bow_transform_batch_dev(vocab, p["desc"], p["n"], cap, B, w["node_kf"], levelsup=levelsup, stream=st)
+            self.ctx.bow_transform_batch_dev(vocab, c["desc"], c["n"], cap, B, w["node_f"], levelsup=levelsup, stream=st)
+            self.ctx.search_by_bow_batch_dev(p["kp"], p["desc"], w["node_kf"], valid, p["n"], cap, B, c["kp"], c["desc"], w["node_f"], c["n"], cap, B, B,
+                                             w["assigned"], w["nm"], nnratio=nnratio, check_orientation=check_orientation, stream=st)
+            if kf_valid is not None:
+                kf_valid.record_stream(s1)
+        cur.wait_stream(s1)
+        return w["assigned"], w["nm"]
+
     def step(self, images, overlap=False, lines_first=False, join=True):
         """One pass of the hot path.  overlap=True runs the point branch (ORB extract + ORB matching)
         and the line branch (LSD/LBD extract + line matching) on two HIP streams: the line branch is
