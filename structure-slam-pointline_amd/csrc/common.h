@@ -40,6 +40,34 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
+// A device buffer of the context whose user runs on the CALLER's stream and returns without synchronising: kernels still read and write it after
+// the call.  acquire() orders a call behind the previous one -- on another stream it waits on the device for the event behind the previous call's
+// last kernel; a call that has to grow the buffer waits for that event on the host first, since growing frees it -- and mark() records the event
+// behind the call's last kernel.  One user per buffer, under ctx->mu.
+struct StreamOrderedBuf {
+    DevBuf buf;
+    hipEvent_t done = nullptr;
+    void* lastStream = nullptr;
+    int acquire(hipStream_t st, size_t bytes) {
+        if (!done) SSLAM_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        else if (bytes > buf.cap) SSLAM_HIP(hipEventSynchronize(done));
+        else if (lastStream != (void*)st) SSLAM_HIP(hipStreamWaitEvent(st, done, 0));
+        return buf.ensure(bytes);
+    }
+    int mark(hipStream_t st) {
+        SSLAM_HIP(hipEventRecord(done, st));
+        lastStream = (void*)st;
+        return SSLAM_OK;
+    }
+    // a call may still run on a caller's stream: wait for it, then free
+    void release() {
+        if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); done = nullptr; }
+        lastStream = nullptr;
+        buf.release();
+    }
+    template <class T> T* as() const { return buf.as<T>(); }
+};
+
 struct HostPinned {
     void* p = nullptr;
     size_t cap = 0;
@@ -59,7 +87,8 @@ struct HostPinned {
 struct sslam_prof_rec { const char* name; hipEvent_t a, b; };
 
 // Slots of sslam_ctx::scratch and ::pinned (match.hip) with their users.  A slot with several users is safe to share because every one of
-// them holds ctx->mu for the whole call and synchronises the stream before it returns (SCR_PROJ_BATCH does neither and has one user).
+// them holds ctx->mu for the whole call and synchronises the stream before it returns.  The two buffers whose users return with kernels still
+// running on the caller's stream are no slots: sslam_ctx::knnExpand and ::projBatch, a StreamOrderedBuf each.
 enum {
     SCR_KNN_Q = 0, SCR_KNN_T = 1, SCR_KNN_OUT = 2,      // sslam_hamming_knn2, sslam_hamming_matrix: query rows, train rows, result
     SCR_SFI_STATE = 3,       // sslam_orb_search_for_initialization_batch_dev: per-pair state (SfiArgs::scratch)
@@ -67,8 +96,7 @@ enum {
     SCR_LINE_MATCH = 5,      // sslam_line_match
     SCR_CALL = 6,            // the arena of search_proj_core, sslam_hamming_knn2_frames, sslam_distinctive_descriptors, sslam_fuse_search, sslam_orb_search_for_triangulation, bow_core
     SCR_UPLOAD = 7,          // host features that a core with an arena in SCR_CALL reads (sslam_search_by_projection, sslam_bow_transform); the arena of search_by_bow_core
-    SCR_PROJ_BATCH = 8,      // sslam_search_by_projection_batch_dev: the arena of one slice of frames.  Its user runs on the CALLER's stream and returns without synchronising, so it shares the slot with nobody; calls are ordered on it by projBatchDone
-    SCR_COUNT = 9
+    SCR_COUNT = 8
 };
 enum {
     PIN_BOW = 1,             // search_by_bow_core
@@ -86,11 +114,8 @@ struct sslam_ctx {
     sslam::DevBuf scratch[SCR_COUNT];      // matcher staging (SCR_*)
     sslam::DevBuf camKp;           // sslam_undistort_keypoints: the host rows on the device (camera.hip)
     sslam::DevBuf colorIn, colorGray;      // sslam_gray_from_color: the host frame and its gray plane on the device (color.hip)
-    sslam::DevBuf knnExpand;       // sslam_hamming_knn2_batch_dev: the train rows as int8 matrix-core operands (match_knn.h)
-    hipEvent_t knnDone = nullptr;  // recorded behind the kernel that reads knnExpand: a call on ANOTHER stream waits for it before it overwrites the buffer
-    void* knnLastStream = nullptr;
-    hipEvent_t projBatchDone = nullptr;      // recorded behind the last kernel that uses scratch[SCR_PROJ_BATCH]: a call on another stream waits for it on the device, a call that has to grow the slot on the host
-    void* projBatchLastStream = nullptr;
+    sslam::StreamOrderedBuf knnExpand;      // sslam_hamming_knn2_batch_dev: the train rows as int8 matrix-core operands (match_knn.h)
+    sslam::StreamOrderedBuf projBatch;      // sslam_search_by_projection_batch_dev: the arena of one slice of frames
     sslam::DevBuf recordOffsets[4];   // sslam_pack_records_dev: per-frame offsets of the record stream, one buffer per stream that packs
     void* recordOffsetsStream[4] = {nullptr, nullptr, nullptr, nullptr};
     unsigned long recordOffsetsUse[4] = {0, 0, 0, 0}, recordOffsetsClock = 0;      // least-recently-used recycling of the four slots

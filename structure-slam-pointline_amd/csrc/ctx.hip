@@ -73,14 +73,11 @@ extern "C" int sslam_ctx_destroy(sslam_ctx* c) {
     if (!c) return SSLAM_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    if (c->projBatchDone) (void)hipEventSynchronize(c->projBatchDone);      // a batch matcher call may still run on a caller's stream: its scratch is freed below
+    c->knnExpand.release(); c->projBatch.release();      // a batch matcher call may still run on a caller's stream: release() waits for it
     if (c->batchCache && c->batchCacheFree) { c->batchCacheFree(c->batchCache); c->batchCache = nullptr; }
     for (auto& b : c->scratch) b.release();
-    c->knnExpand.release();
     c->camKp.release();
     c->colorIn.release(); c->colorGray.release();
-    if (c->knnDone) (void)hipEventDestroy(c->knnDone);
-    if (c->projBatchDone) (void)hipEventDestroy(c->projBatchDone);
     for (auto& b : c->recordOffsets) b.release();
     for (auto& b : c->pinned) b.release();
     (void)hipStreamDestroy(c->stream);

@@ -9,6 +9,7 @@
 // point reads as validate, lock, lay out, stage, switch on the plan's form with one launch per case, copy back.
 #include "common.h"
 #include "match_plan.h"
+#include "match_check.h"
 #include <algorithm>
 
 using namespace sslam;
@@ -16,6 +17,7 @@ using namespace sslam;
 namespace {
 
 #include "match_knn.h"
+#include "match_rot.h"
 #include "match_ordered.h"
 #include "match_independent.h"
 
@@ -23,9 +25,9 @@ namespace {
 
 // =============================================================== host side
 static hipStream_t pick(sslam_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
-// a launch with more than the default 48 KB of dynamic LDS has to be allowed per kernel
+// a launch with more dynamic LDS than the default maximum has to be allowed per kernel
 static int allow_dynamic_lds(const void* kernel, size_t bytes) {
-    if (bytes > 48 * 1024) SSLAM_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (bytes > DYNAMIC_LDS_DEFAULT_MAX) SSLAM_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return SSLAM_OK;
 }
 
@@ -50,14 +52,12 @@ extern "C" int sslam_hamming_knn2_batch_dev(sslam_ctx* ctx, const uint8_t* d_q, 
     case Knn2Form::MatrixCore: {       // match_knn.h: train rows expanded to +-64 bytes in operand order, then 64 queries per wave
         int rc;
         // ONE expand buffer per context (256 B per train row: 3 GB at 12 288 frames of 1 000 rows, never shrunk; sslam_frontend_batch counts it in its chunk estimate).
-        // k_knn2_expand writes it and k_knn2_mfma reads it on the caller's stream: a call on another stream first waits for the event behind the previous reader.
-        if (ctx->knnDone && ctx->knnLastStream != (void*)st) SSLAM_HIP(hipStreamWaitEvent(st, ctx->knnDone, 0));
-        if (!ctx->knnDone) SSLAM_HIP(hipEventCreateWithFlags(&ctx->knnDone, hipEventDisableTiming));
-        if ((rc = ctx->knnExpand.ensure(P.expandBytes))) return rc;
+        // k_knn2_expand writes it and k_knn2_mfma reads it on the caller's stream after this call has returned (StreamOrderedBuf, common.h).
+        if ((rc = ctx->knnExpand.acquire(st, P.expandBytes))) return rc;
         { sslam::ProfScope _ps(ctx, "k_knn2_expand", st); hipLaunchKernelGGL(k_knn2_expand, dim3(P.tilesCap, nframes), dim3(64), 0, st, d_t, d_nt, cap, P.tilesCap, ctx->knnExpand.as<uint8_t>()); }
         { sslam::ProfScope _ps(ctx, "k_knn2_batch", st);
           hipLaunchKernelGGL(k_knn2_mfma<2>, dim3(P.grid), dim3(64), 0, st, d_q, d_nq, ctx->knnExpand.as<uint8_t>(), d_nt, cap, P.tilesCap, P.qblocks, nframes, d_idx, d_dist); }
-        SSLAM_HIP(hipEventRecord(ctx->knnDone, st)); ctx->knnLastStream = (void*)st;
+        if ((rc = ctx->knnExpand.mark(st))) return rc;
         break;
     }
     case Knn2Form::Popcount: {         // more than 4096 rows per frame: xor + popcount
@@ -243,6 +243,13 @@ extern "C" int sslam_line_match(sslam_ctx* ctx, const uint8_t* l1, int n1, const
     return SSLAM_OK;
 }
 
+// the fields of ProjArgs that a single call and a batch call fill alike
+static void proj_shared_args(ProjArgs& A, int kind, int mode, const float bounds[4], float nnratio, int th_dist, int check_orientation) {
+    A.kind = kind; A.mode = mode;
+    A.minX = bounds[0]; A.maxX = bounds[1]; A.minY = bounds[2]; A.maxY = bounds[3];
+    A.nnratio = nnratio; A.thDist = th_dist; A.checkOri = check_orientation;
+}
+
 // shared body of the projection matchers: features already on the device (d_feats / d_desc / d_uright), per-call inputs staged here
 static int search_proj_core(sslam_ctx* ctx, int kind, int mode, const void* d_feats, const uint8_t* d_desc, int n, const float bounds[4],
                             const float* d_uright, const uint8_t* occupied, const sslam_proj_query* queries, const uint8_t* qdesc, int nq,
@@ -261,10 +268,10 @@ static int search_proj_core(sslam_ctx* ctx, int kind, int mode, const void* d_fe
     memcpy(H + L.qdesc, qdesc, 32 * (size_t)nq);
     SSLAM_HIP(hipMemcpyAsync(B + L.occ, H + L.occ, L.assigned - L.occ, hipMemcpyHostToDevice, st));
     ProjArgs A;
-    A.kind = kind; A.mode = mode; A.feats = (const uint8_t*)d_feats; A.desc = d_desc; A.n = n;
-    A.minX = bounds[0]; A.maxX = bounds[1]; A.minY = bounds[2]; A.maxY = bounds[3];
+    proj_shared_args(A, kind, mode, bounds, nnratio, th_dist, check_orientation);
+    A.feats = (const uint8_t*)d_feats; A.desc = d_desc; A.n = n;
     A.uright = d_uright; A.occIn = occupied ? B + L.occ : nullptr;
-    A.q = (const sslam_proj_query*)(B + L.q); A.qdesc = B + L.qdesc; A.nq = nq; A.nnratio = nnratio; A.thDist = th_dist; A.checkOri = check_orientation;
+    A.q = (const sslam_proj_query*)(B + L.q); A.qdesc = B + L.qdesc; A.nq = nq;
     A.assigned = (int*)(B + L.assigned); A.nmatches = (int*)(B + L.count); A.scratch = (int*)(B + L.scratch);
     A.stats = getenv("SSLAM_PROJ_STATS") ? (long long*)(B + L.stats()) : nullptr;      // development aid: seven counters behind the match count
     const ProjPlan P = proj_plan(n, nq);
@@ -353,21 +360,15 @@ extern "C" int sslam_search_by_projection_batch_dev(sslam_ctx* ctx, int kind, in
 #endif
     const ProjBatchPlan P = proj_batch_plan(cap, qcap, nframes, tune);      // match_plan.h: the kernels by row capacity, the slice by scratch
     const ProjBatchArena L = proj_batch_arena(cap, qcap, P.slice, PROJ_K);
-    // ONE arena per context, used by the kernels of this call on the caller's stream after the call has returned.  A call on another stream waits (on the
-    // device) for the event behind the previous call's last kernel; a call that has to grow the arena waits for it on the host first, since growing frees it.
-    sslam::DevBuf& S = ctx->scratch[SCR_PROJ_BATCH];
-    if (!ctx->projBatchDone) SSLAM_HIP(hipEventCreateWithFlags(&ctx->projBatchDone, hipEventDisableTiming));
-    else if (L.total > S.cap) SSLAM_HIP(hipEventSynchronize(ctx->projBatchDone));
-    else if (ctx->projBatchLastStream != (void*)st) SSLAM_HIP(hipStreamWaitEvent(st, ctx->projBatchDone, 0));
+    // ONE arena per context, used by the kernels of this call on the caller's stream after the call has returned (StreamOrderedBuf, common.h)
     int rc;
-    if ((rc = S.ensure(L.total))) return rc;
-    uint8_t* B = S.as<uint8_t>();
+    if ((rc = ctx->projBatch.acquire(st, L.total))) return rc;
+    uint8_t* B = ctx->projBatch.as<uint8_t>();
     ProjBatchArgs T;
     ProjArgs& A = T.A;
-    A.kind = kind; A.mode = mode; A.feats = d_feats; A.desc = d_desc; A.n = 0;
-    A.minX = bounds[0]; A.maxX = bounds[1]; A.minY = bounds[2]; A.maxY = bounds[3];
+    proj_shared_args(A, kind, mode, bounds, nnratio, th_dist, check_orientation);
+    A.feats = d_feats; A.desc = d_desc; A.n = 0;
     A.uright = d_uright; A.occIn = d_occupied; A.q = d_queries; A.qdesc = d_qdesc; A.nq = 0;
-    A.nnratio = nnratio; A.thDist = th_dist; A.checkOri = check_orientation;
     A.assigned = d_assigned; A.nmatches = d_nmatches; A.scratch = nullptr; A.stats = nullptr;
     T.n = d_n; T.nq = d_nq; T.cap = cap; T.qcap = qcap; T.frame0 = 0;
     T.scratch = (int*)(B + L.scratch); T.top = (unsigned long long*)(B + L.top); T.cnt = (int*)(B + L.cnt);
@@ -390,8 +391,7 @@ extern "C" int sslam_search_by_projection_batch_dev(sslam_ctx* ctx, int kind, in
         }
     }
     SSLAM_HIP(hipGetLastError());
-    SSLAM_HIP(hipEventRecord(ctx->projBatchDone, st)); ctx->projBatchLastStream = (void*)st;
-    return SSLAM_OK;
+    return ctx->projBatch.mark(st);
 }
 
 // ---- device-resident frames
@@ -504,16 +504,15 @@ static int search_by_bow_core(sslam_ctx* ctx, const sslam_keypoint* kf_kp, const
     *nmatches_out = 0;
     for (int i = 0; i < nf; ++i) assigned_out[i] = -1;
     if (nnodes == 0 || nf == 0 || nkf == 0) return SSLAM_OK;
+    int rc;
+    if ((rc = check_csr("sslam_orb_search_by_bow", "keyframe feature", node_kf_ptr, nnodes, kf_idx, nkf)) ||
+        (rc = check_csr("sslam_orb_search_by_bow", "frame feature", node_f_ptr, nnodes, f_idx, nf))) return rc;
     const int nk = node_kf_ptr[nnodes], nfi = node_f_ptr[nnodes];
-    if (node_kf_ptr[0] != 0 || node_f_ptr[0] != 0 || nk < 0 || nfi < 0) { set_error("sslam_orb_search_by_bow: invalid node offsets"); return SSLAM_ERR_INVALID; }
-    for (int i = 0; i < nk; ++i) if (kf_idx[i] < 0 || kf_idx[i] >= nkf) { set_error("sslam_orb_search_by_bow: keyframe feature index out of range"); return SSLAM_ERR_INVALID; }
-    for (int i = 0; i < nfi; ++i) if (f_idx[i] < 0 || f_idx[i] >= nf) { set_error("sslam_orb_search_by_bow: frame feature index out of range"); return SSLAM_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t ks = sizeof(sslam_keypoint);
     const BowArena L = bow_arena(nkf, nf, nnodes, nk, nfi);
-    int rc;
     if ((rc = ctx->scratch[SCR_UPLOAD].ensure(L.total))) return rc;
     uint8_t* B = ctx->scratch[SCR_UPLOAD].as<uint8_t>();
     // every input (and the -1 fill of the two result arrays) goes through ONE pinned staging buffer and one H2D copy: ten small pageable
@@ -540,7 +539,7 @@ static int search_by_bow_core(sslam_ctx* ctx, const sslam_keypoint* kf_kp, const
     // (a fused form -- the last workgroup to finish runs this pass, saving the launch -- was measured: the two agent-scope fences per
     // workgroup cost more than the launch, 0.111 against 0.103 ms per call; both passes in ONE workgroup of sixteen waves, no fences at
     // all: 0.235 ms -- two nodes per wave in series instead of one workgroup per node)
-    { sslam::ProfScope _ps(ctx, "k_bow_finish", st); hipLaunchKernelGGL(k_bow_finish, dim3(1), dim3(256), 0, st, A.assigned, A.qbin, nf, check_orientation, A.nmatches); }
+    { sslam::ProfScope _ps(ctx, "k_bow_finish", st); hipLaunchKernelGGL(k_rot_finish, dim3(1), dim3(256), 0, st, A.assigned, A.qbin, nf, check_orientation, A.nmatches); }
     SSLAM_HIP(hipGetLastError());
     SSLAM_HIP(hipMemcpyAsync(H + L.assigned, B + L.assigned, L.count + 4 - L.assigned, hipMemcpyDeviceToHost, st));      // assigned + the count, back through the same staging
     SSLAM_HIP(hipStreamSynchronize(st));
@@ -581,11 +580,12 @@ extern "C" int sslam_orb_search_by_bow_keyframes(sslam_ctx* ctx, const sslam_key
 extern "C" int sslam_distinctive_descriptors(sslam_ctx* ctx, const uint8_t* desc, const int32_t* ptr, int nsets, int32_t* best_out) {
     if (!ctx || nsets < 0 || (nsets > 0 && (!ptr || !best_out))) { set_error("sslam_distinctive_descriptors: invalid arguments"); return SSLAM_ERR_INVALID; }
     if (nsets == 0) return SSLAM_OK;
+    int rc;
+    if ((rc = check_csr("sslam_distinctive_descriptors", "set", ptr, nsets, nullptr, 0))) return rc;
     const int total = ptr[nsets];
-    if (ptr[0] != 0 || total < 0 || (total > 0 && !desc)) { set_error("sslam_distinctive_descriptors: invalid set offsets"); return SSLAM_ERR_INVALID; }
+    if (total > 0 && !desc) { set_error("sslam_distinctive_descriptors: invalid arguments"); return SSLAM_ERR_INVALID; }
     for (int s2 = 0; s2 < nsets; ++s2) {
         const int n = ptr[s2 + 1] - ptr[s2];
-        if (n < 0) { set_error("sslam_distinctive_descriptors: offsets must be non-decreasing"); return SSLAM_ERR_INVALID; }
         if (n > DISTINCT_MAXN) { set_error("sslam_distinctive_descriptors: a set of %d descriptors exceeds the supported %d", n, DISTINCT_MAXN); return SSLAM_ERR_UNSUPPORTED; }
     }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -593,7 +593,6 @@ extern "C" int sslam_distinctive_descriptors(sslam_ctx* ctx, const uint8_t* desc
     hipStream_t st = ctx->stream;
     ArenaLayout L;
     const size_t oD = L.take(32 * (size_t)std::max(total, 1)), oP = L.take(4 * (size_t)(nsets + 1)), oB = L.take(4 * (size_t)nsets);
-    int rc;
     if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
     uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
     if (total > 0) SSLAM_HIP(hipMemcpyAsync(B + oD, desc, 32 * (size_t)total, hipMemcpyHostToDevice, st));
@@ -655,10 +654,10 @@ extern "C" int sslam_orb_search_for_triangulation(sslam_ctx* ctx, const sslam_fr
     const int n1 = kf1->n, n2 = kf2->n;
     for (int i = 0; i < n1; ++i) matches12_out[i] = -1;
     if (n1 == 0 || n2 == 0 || nnodes == 0) return SSLAM_OK;
+    int rc;
+    if ((rc = check_csr("sslam_orb_search_for_triangulation", "keyframe-1", node_kf1_ptr, nnodes, kf1_idx, n1)) ||
+        (rc = check_csr("sslam_orb_search_for_triangulation", "keyframe-2", node_kf2_ptr, nnodes, kf2_idx, n2))) return rc;
     const int total1 = node_kf1_ptr[nnodes], total2 = node_kf2_ptr[nnodes];
-    if (node_kf1_ptr[0] != 0 || node_kf2_ptr[0] != 0 || total1 < 0 || total2 < 0) { set_error("sslam_orb_search_for_triangulation: invalid node offsets"); return SSLAM_ERR_INVALID; }
-    for (int i = 0; i < total1; ++i) if (kf1_idx[i] < 0 || kf1_idx[i] >= n1) { set_error("sslam_orb_search_for_triangulation: keyframe-1 index out of range"); return SSLAM_ERR_INVALID; }
-    for (int i = 0; i < total2; ++i) if (kf2_idx[i] < 0 || kf2_idx[i] >= n2) { set_error("sslam_orb_search_for_triangulation: keyframe-2 index out of range"); return SSLAM_ERR_INVALID; }
     if (total1 == 0 || total2 == 0) return SSLAM_OK;
     std::vector<int32_t> nodeOf((size_t)total1);
     for (int nd = 0; nd < nnodes; ++nd) for (int a = node_kf1_ptr[nd]; a < node_kf1_ptr[nd + 1]; ++a) nodeOf[a] = nd;
@@ -669,7 +668,6 @@ extern "C" int sslam_orb_search_for_triangulation(sslam_ctx* ctx, const sslam_fr
     const size_t oF1 = L.take(n1), oF2 = L.take(n2), oP1 = L.take(4 * (size_t)(nnodes + 1)), oP2 = L.take(4 * (size_t)(nnodes + 1)), oI1 = L.take(4 * (size_t)total1),
                  oI2 = L.take(4 * (size_t)total2), oNO = L.take(4 * (size_t)total1), oSF = L.take(4 * (size_t)nlevels), oSG = L.take(4 * (size_t)nlevels),
                  oM = L.take(4 * (size_t)n1), oQB = L.take(4 * (size_t)n1), oN = L.take(4);
-    int rc;
     if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
     uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
     SSLAM_HIP(hipMemcpyAsync(B + oF1, free1, n1, hipMemcpyHostToDevice, st));
@@ -692,7 +690,7 @@ extern "C" int sslam_orb_search_for_triangulation(sslam_ctx* ctx, const sslam_fr
     A.onlyStereo = only_stereo; A.checkOri = check_orientation;
     A.m12 = (int*)(B + oM); A.qbin = (int*)(B + oQB); A.nmatches = (int*)(B + oN);
     { sslam::ProfScope _ps(ctx, "k_tri_search", st); hipLaunchKernelGGL(k_tri_search, dim3(std::min(total1, 8192)), dim3(64), 0, st, A); }
-    { sslam::ProfScope _ps(ctx, "k_tri_finish", st); hipLaunchKernelGGL(k_tri_finish, dim3(1), dim3(256), 0, st, A.m12, A.qbin, n1, check_orientation, A.nmatches); }
+    { sslam::ProfScope _ps(ctx, "k_tri_finish", st); hipLaunchKernelGGL(k_rot_finish, dim3(1), dim3(256), 0, st, A.m12, A.qbin, n1, check_orientation, A.nmatches); }
     SSLAM_HIP(hipGetLastError());
     SSLAM_HIP(hipMemcpyAsync(matches12_out, B + oM, 4 * (size_t)n1, hipMemcpyDeviceToHost, st));
     SSLAM_HIP(hipMemcpyAsync(nmatches_out, B + oN, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -704,9 +702,10 @@ extern "C" int sslam_orb_search_for_triangulation(sslam_ctx* ctx, const sslam_fr
 extern "C" int sslam_vocab_create(sslam_ctx* ctx, int nnodes, int levels, const int32_t* child_ptr, const int32_t* children, const uint8_t* node_desc,
                                   const int32_t* word_id, const double* weight, sslam_vocab** out) {
     if (!ctx || !out || nnodes < 1 || levels < 1 || !child_ptr || !node_desc || !word_id || !weight) { set_error("sslam_vocab_create: invalid arguments"); return SSLAM_ERR_INVALID; }
+    int rc;
+    if ((rc = check_csr("sslam_vocab_create", "child", child_ptr, nnodes, nullptr, 0))) return rc;
     const int nch = child_ptr[nnodes];
-    if (child_ptr[0] != 0 || nch < 0 || (nch > 0 && !children)) { set_error("sslam_vocab_create: invalid child offsets"); return SSLAM_ERR_INVALID; }
-    for (int i = 0; i < nnodes; ++i) if (child_ptr[i + 1] < child_ptr[i]) { set_error("sslam_vocab_create: child offsets must be non-decreasing"); return SSLAM_ERR_INVALID; }
+    if (nch > 0 && !children) { set_error("sslam_vocab_create: invalid arguments"); return SSLAM_ERR_INVALID; }
     for (int i = 0; i < nch; ++i) if (children[i] <= 0 || children[i] >= nnodes) { set_error("sslam_vocab_create: child id out of range"); return SSLAM_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
@@ -714,7 +713,6 @@ extern "C" int sslam_vocab_create(sslam_ctx* ctx, int nnodes, int levels, const 
     HandleGuard<sslam_vocab, sslam_vocab_destroy> guard(v);
     v->ctx = ctx; v->nnodes = nnodes; v->levels = levels;
     for (int i = 1; i < nnodes; ++i) v->nwords += child_ptr[i + 1] == child_ptr[i];
-    int rc;
     if ((rc = v->childPtr.ensure(4 * (size_t)(nnodes + 1))) || (rc = v->children.ensure(std::max<size_t>(4 * (size_t)nch, 256))) || (rc = v->desc.ensure(32 * (size_t)nnodes)) ||
         (rc = v->wordId.ensure(4 * (size_t)nnodes)) || (rc = v->weight.ensure(8 * (size_t)nnodes))) return rc;
     hipStream_t st = ctx->stream;

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64) void k_fuse_search(FuseArgs A) {
 // src/ORBmatcher.cc:660-826 (+ CheckDistEpipolarLine :140-157).  The reference never sets vbMatched2, so every keyframe-1
 // feature is an independent query over the keyframe-2 features of its vocabulary node: one wave per query, candidates
 // lane-parallel.  `dist > bestDist` (not >=) lets a later candidate with an equal distance win, hence the inverted position
-// in the min-reduction key.  k_tri_finish applies the rotation-histogram pruning and counts.
+// in the min-reduction key.  k_rot_finish (match_rot.h) applies the rotation-histogram pruning and counts.
 struct TriArgs {
     const sslam_keypoint* kp1; const uint8_t* d1; const float* ur1; const uint8_t* free1; int n1;
     const sslam_keypoint* kp2; const uint8_t* d2; const float* ur2; const uint8_t* free2;
@@ -129,50 +129,9 @@ __global__ __launch_bounds__(64) void k_tri_search(TriArgs A) {
         if (b != ~0ull && lane == 0) {
             const int i2 = A.idx2[f0 + (0x7FFFFFFF - (int)(unsigned)b)];
             A.m12[i1] = i2;
-            if (A.checkOri) {
-                float rot = __fsub_rn(k1.angle, A.kp2[i2].angle);
-                if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                int bin = (int)roundf(__fmul_rn(rot, 1.0f / HISTO_LENGTH));
-                if (bin == HISTO_LENGTH) bin = 0;
-                A.qbin[i1] = bin;
-            }
+            if (A.checkOri) A.qbin[i1] = rot_bin(k1.angle, A.kp2[i2].angle);
         }
     }
-}
-__global__ __launch_bounds__(256) void k_tri_finish(int* __restrict__ m12, const int* __restrict__ qbin, int n1, int checkOri, int* __restrict__ nmatches) {
-    __shared__ int hist[HISTO_LENGTH];
-    __shared__ int keep[3];
-    __shared__ int total;
-    const int t = threadIdx.x;
-    if (t < HISTO_LENGTH) hist[t] = 0;
-    if (t == 0) total = 0;
-    __syncthreads();
-    if (checkOri) {
-        for (int i = t; i < n1; i += 256) if (m12[i] >= 0) atomicAdd(&hist[qbin[i]], 1);
-        __syncthreads();
-        if (t == 0) {
-            int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < HISTO_LENGTH; ++i) {
-                const int c = hist[i];
-                if (c > max1) { max3 = max2; max2 = max1; max1 = c; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (c > max2) { max3 = max2; max2 = c; ind3 = ind2; ind2 = i; }
-                else if (c > max3) { max3 = c; ind3 = i; }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-            keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-        }
-        __syncthreads();
-    }
-    int cnt = 0;
-    for (int i = t; i < n1; i += 256) {
-        if (m12[i] < 0) continue;
-        if (checkOri) { const int bn = qbin[i]; if (bn != keep[0] && bn != keep[1] && bn != keep[2]) { m12[i] = -1; continue; } }
-        ++cnt;
-    }
-    atomicAdd(&total, cnt);
-    __syncthreads();
-    if (t == 0) *nmatches = total;
 }
 
 // ------------------------------------------------------------------ DBoW2 vocabulary descent (Frame::ComputeBoW)

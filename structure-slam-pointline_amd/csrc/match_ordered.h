@@ -19,6 +19,21 @@ struct SfiArgs {
     int ccap;                      // k_search_init_lds: LDS capacity in level-0 candidates / level-0 keypoints of F1, always > 0 (SfiPlan::ccap; the kernel's 0 = "the pair's own counts" has no caller)
 };
 
+// the two ends every form of the matcher shares.  rot_prune_wave's un-match: an F1 keypoint whose match a later one took over is no match any more
+__device__ __forceinline__ bool sfi_unmatch(int* m12, int i) {
+    if (m12[i] < 0) return false;
+    m12[i] = -1;
+    return true;
+}
+// the epilogue, by nt threads of which this is tid: vbPrevMatched takes the matched keypoints' positions (src/ORBmatcher.cc:519-521), then the count
+__device__ __forceinline__ void sfi_write_back(const SfiArgs& A, int p, int n1, const sslam_keypoint* kp2, float* pm, const int* m12, int nmatches, int tid, int nt) {
+    for (int i = tid; i < n1; i += nt) {
+        const int m = m12[i];
+        if (m >= 0) { pm[i * 2] = kp2[m].x; pm[i * 2 + 1] = kp2[m].y; }
+    }
+    if (tid == 0) A.nmatches[p] = nmatches;
+}
+
 // the pair's state in global memory (what a pair falls back to when its level-0 features do not fit the LDS capacity of the batch launch)
 __device__ __forceinline__ void sfi_global_body(const SfiArgs& A, int p, int lane, int* __restrict__ hist) {
     const int n1 = A.n1 ? A.n1[p] : A.n1s, n2 = A.n2 ? A.n2[p] : A.n2s;
@@ -88,45 +103,16 @@ __device__ __forceinline__ void sfi_global_body(const SfiArgs& A, int p, int lan
             if (lane == 0) { m12[i1] = bestIdx2; m21[bestIdx2] = i1; matchedDist[bestIdx2] = bestDist; }
             nmatches++;
             if (A.checkOri) {
-                float rot = __fsub_rn(kp1[i1].angle, kp2[bestIdx2].angle);
-                if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                int bin = (int)roundf(__fmul_rn(rot, 1.0f / HISTO_LENGTH));
-                if (bin == HISTO_LENGTH) bin = 0;
+                const int bin = rot_bin(kp1[i1].angle, kp2[bestIdx2].angle);
                 if (lane == 0) { binOf[i1] = bin; hist[bin]++; }
             }
             __syncthreads();
         }
     }
     __syncthreads();
-    if (A.checkOri) {
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;      // ComputeThreeMaxima
-        for (int i = 0; i < HISTO_LENGTH; ++i) {
-            const int s = hist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-        int removed = 0;
-        for (int i0 = 0; i0 < n1; i0 += 64) {
-            int i = i0 + lane;
-            bool rm = false;
-            if (i < n1) {
-                int bn = binOf[i];
-                rm = bn >= 0 && bn != ind1 && bn != ind2 && bn != ind3 && m12[i] >= 0;
-                if (rm) m12[i] = -1;
-            }
-            removed += __popcll(__ballot(rm));
-        }
-        nmatches -= removed;
-    }
+    if (A.checkOri) nmatches -= rot_prune_wave(hist, n1, lane, [&](int i) { return binOf[i]; }, [&](int i) { return sfi_unmatch(m12, i); });
     __syncthreads();
-    for (int i = lane; i < n1; i += 64) {
-        int m = m12[i];
-        if (m >= 0) { pm[i * 2] = kp2[m].x; pm[i * 2 + 1] = kp2[m].y; }
-    }
-    if (lane == 0) A.nmatches[p] = nmatches;
+    sfi_write_back(A, p, n1, kp2, pm, m12, nmatches, lane, 64);
 }
 
 __global__ __launch_bounds__(64) void k_search_init(SfiArgs A) {
@@ -232,45 +218,16 @@ __global__ __launch_bounds__(64) void k_search_init_lds(SfiArgs A) {
             if (lane == 0) { m12[i1] = bestIdx2; owner[slot] = i1; md[slot] = bestDist; }
             nmatches++;
             if (A.checkOri) {
-                float rot = __fsub_rn(kp1[i1].angle, kp2[bestIdx2].angle);
-                if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                int bin = (int)roundf(__fmul_rn(rot, 1.0f / HISTO_LENGTH));
-                if (bin == HISTO_LENGTH) bin = 0;
+                const int bin = rot_bin(kp1[i1].angle, kp2[bestIdx2].angle);
                 if (lane == 0) { binOf[t] = bin; hist[bin]++; }
             }
             __syncthreads();
         }
     }
     __syncthreads();
-    if (A.checkOri) {
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;      // ComputeThreeMaxima
-        for (int i = 0; i < HISTO_LENGTH; ++i) {
-            const int sh = hist[i];
-            if (sh > max1) { max3 = max2; max2 = max1; max1 = sh; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (sh > max2) { max3 = max2; max2 = sh; ind3 = ind2; ind2 = i; }
-            else if (sh > max3) { max3 = sh; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-        int removed = 0;
-        for (int t0 = 0; t0 < nl; t0 += 64) {
-            const int t = t0 + lane;
-            bool rm = false;
-            if (t < nl) {
-                const int bn = binOf[t], i = list1[t];
-                rm = bn >= 0 && bn != ind1 && bn != ind2 && bn != ind3 && m12[i] >= 0;
-                if (rm) m12[i] = -1;
-            }
-            removed += __popcll(__ballot(rm));
-        }
-        nmatches -= removed;
-    }
+    if (A.checkOri) nmatches -= rot_prune_wave(hist, nl, lane, [&](int t) { return binOf[t]; }, [&](int t) { return sfi_unmatch(m12, list1[t]); });      // bins per entry of list1
     __syncthreads();
-    for (int i = lane; i < n1; i += 64) {
-        const int m = m12[i];
-        if (m >= 0) { pm[i * 2] = kp2[m].x; pm[i * 2 + 1] = kp2[m].y; }
-    }
-    if (lane == 0) A.nmatches[p] = nmatches;
+    sfi_write_back(A, p, n1, kp2, pm, m12, nmatches, lane, 64);
 }
 
 // Speculative form of the single call (round 3): sixteen waves evaluate sixteen consecutive level-0 keypoints of F1 against the state at the
@@ -369,12 +326,7 @@ __global__ __launch_bounds__(SFI_WAVES * 64) void k_search_init_spec(SfiArgs A) 
         const unsigned sec = second == ~0ull ? 0x7FFFFFFFu : (unsigned)(second >> 32);
         if (bestDist <= TH_LOW && (float)bestDist < __fmul_rn((float)(int)sec, A.nnratio)) {
             acc = 1; dist = bestDist;
-            if (A.checkOri) {
-                float rot = __fsub_rn(kp1[i1].angle, kp2[S.cj[slot]].angle);
-                if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                bin = (int)roundf(__fmul_rn(rot, 1.0f / HISTO_LENGTH));
-                if (bin == HISTO_LENGTH) bin = 0;
-            }
+            if (A.checkOri) bin = rot_bin(kp1[i1].angle, kp2[S.cj[slot]].angle);
         }
     };
     for (int base = 0; base < nl; base += SFI_WAVES) {
@@ -441,37 +393,9 @@ __global__ __launch_bounds__(SFI_WAVES * 64) void k_search_init_spec(SfiArgs A) 
     }
     int nmatches = sh_nm;
     __syncthreads();
-    if (A.checkOri) {
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;      // ComputeThreeMaxima
-        for (int i = 0; i < HISTO_LENGTH; ++i) {
-            const int sh = hist[i];
-            if (sh > max1) { max3 = max2; max2 = max1; max1 = sh; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (sh > max2) { max3 = max2; max2 = sh; ind3 = ind2; ind2 = i; }
-            else if (sh > max3) { max3 = sh; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-        if (wave == 0) {
-            int removed = 0;
-            for (int i0 = 0; i0 < n1; i0 += 64) {
-                const int i = i0 + lane;
-                bool rm = false;
-                if (i < n1) {
-                    const int bn = binOf[i];
-                    rm = bn >= 0 && bn != ind1 && bn != ind2 && bn != ind3 && m12[i] >= 0;
-                    if (rm) m12[i] = -1;
-                }
-                removed += __popcll(__ballot(rm));
-            }
-            nmatches -= removed;
-        }
-    }
+    if (A.checkOri && wave == 0) nmatches -= rot_prune_wave(hist, n1, lane, [&](int i) { return binOf[i]; }, [&](int i) { return sfi_unmatch(m12, i); });      // (tid 0, which stores the count, is in wave 0)
     __syncthreads();
-    for (int i = tid; i < n1; i += NT) {
-        const int m = m12[i];
-        if (m >= 0) { pm[i * 2] = kp2[m].x; pm[i * 2 + 1] = kp2[m].y; }
-    }
-    if (tid == 0) A.nmatches[p] = nmatches;
+    sfi_write_back(A, p, n1, kp2, pm, m12, nmatches, tid, NT);
 }
 
 // ---------------------------------------------------------------- projection-window matchers
@@ -492,6 +416,12 @@ struct ProjArgs {
     int* scratch;          // occ[n], key[n], qbin[nq], qidx[nq]
     long long* stats;      // SSLAM_PROJ_STATS (development aid, two-kernel form): commit steps, re-scans, cycles in re-scans, total cycles
 };
+
+// the rotation check behind the walk of either form: a query matched and then removed leaves -2 on its feature (the reference NULLs the pointer,
+// src/ORBmatcher.cc:1465).  qbin[iq]: the query's rotation bin or -1, qidx[iq]: the feature it took
+__device__ __forceinline__ int proj_rot_prune(const ProjArgs& A, const int* hist, const int* qbin, const int* qidx, int lane) {
+    return rot_prune_wave(hist, A.nq, lane, [&](int iq) { return qbin[iq]; }, [&](int iq) { A.assigned[qidx[iq]] = -2; return true; });
+}
 
 // one frame by one wave; hist: HISTO_LENGTH ints of the workgroup's LDS
 __device__ __forceinline__ void search_proj_body(const ProjArgs& A, int lane, int* __restrict__ hist) {
@@ -576,35 +506,14 @@ __device__ __forceinline__ void search_proj_body(const ProjArgs& A, int lane, in
             ++nmatches;
             if (lane == 0) { A.assigned[bestIdx] = iq; occ[bestIdx] = Q.obs_positive ? 1 : 0; }
             if (A.mode == 1 && A.checkOri) {
-                float rot = __fsub_rn(Q.angle, kps[bestIdx].angle);
-                if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                int bin = (int)roundf(__fmul_rn(rot, 1.0f / HISTO_LENGTH));
-                if (bin == HISTO_LENGTH) bin = 0;
+                const int bin = rot_bin(Q.angle, kps[bestIdx].angle);
                 if (lane == 0) { qbin[iq] = bin; qidx[iq] = bestIdx; hist[bin]++; }
             }
             __syncthreads();
         }
     }
     __syncthreads();
-    if (A.mode == 1 && A.checkOri) {
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < HISTO_LENGTH; ++i) {
-            const int c = hist[i];
-            if (c > max1) { max3 = max2; max2 = max1; max1 = c; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (c > max2) { max3 = max2; max2 = c; ind3 = ind2; ind2 = i; }
-            else if (c > max3) { max3 = c; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-        int removed = 0;
-        for (int i0 = 0; i0 < nq; i0 += 64) {
-            const int i = i0 + lane;
-            bool rm = false;
-            if (i < nq) { const int bn = qbin[i]; rm = bn >= 0 && bn != ind1 && bn != ind2 && bn != ind3; if (rm) A.assigned[qidx[i]] = -2; }      // matched, then removed by the rotation check: the reference NULLs the pointer (src/ORBmatcher.cc:1465)
-            removed += __popcll(__ballot(rm));
-        }
-        nmatches -= removed;
-    }
+    if (A.mode == 1 && A.checkOri) nmatches -= proj_rot_prune(A, hist, qbin, qidx, lane);
     if (lane == 0) *A.nmatches = nmatches;
 }
 __global__ __launch_bounds__(64) void k_search_proj(ProjArgs A) {
@@ -731,12 +640,7 @@ __device__ __forceinline__ void proj_decide_keys(const ProjArgs& A, float qAngle
     if (bestDist > A.thDist || bestDist >= 256) return;
     if (A.mode == 0 && bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(A.nnratio, (float)bestDist2)) return;
     acc = 1;
-    if (A.mode == 1 && A.checkOri) {
-        float rot = __fsub_rn(qAngle, ((const sslam_keypoint*)A.feats)[proj_key_feature(b)].angle);
-        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-        bin = (int)roundf(__fmul_rn(rot, 1.0f / HISTO_LENGTH));
-        if (bin == HISTO_LENGTH) bin = 0;
-    }
+    if (A.mode == 1 && A.checkOri) bin = rot_bin(qAngle, ((const sslam_keypoint*)A.feats)[proj_key_feature(b)].angle);
 }
 
 // the same test on a copy of the frame's features in LDS (k_proj_commit's re-scan); every field first, the tests afterwards: one LDS round
@@ -885,25 +789,7 @@ __device__ __forceinline__ void proj_commit_body(const ProjTopArgs& T, int feats
         }
     }
     __syncthreads();
-    if (A.mode == 1 && A.checkOri) {
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < HISTO_LENGTH; ++i) {
-            const int c = hist[i];
-            if (c > max1) { max3 = max2; max2 = max1; max1 = c; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (c > max2) { max3 = max2; max2 = c; ind3 = ind2; ind2 = i; }
-            else if (c > max3) { max3 = c; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-        int removed = 0;
-        for (int i0 = 0; i0 < nq; i0 += 64) {
-            const int i = i0 + lane;
-            bool rm = false;
-            if (i < nq) { const int bn = qbin[i]; rm = bn >= 0 && bn != ind1 && bn != ind2 && bn != ind3; if (rm) A.assigned[qidx[i]] = -2; }      // matched, then removed by the rotation check (src/ORBmatcher.cc:1465)
-            removed += __popcll(__ballot(rm));
-        }
-        nmatches -= removed;
-    }
+    if (A.mode == 1 && A.checkOri) nmatches -= proj_rot_prune(A, hist, qbin, qidx, lane);
     if (lane == 0) *A.nmatches = nmatches;
     if (lane == 0 && A.stats) { A.stats[0] = it; A.stats[1] = stRescan; A.stats[2] = cyRescan; A.stats[3] = __builtin_readcyclecounter() - tK0; }
 }
@@ -979,7 +865,7 @@ struct BowArgs {
 // A frame feature belongs to one vocabulary node, so the only order dependence of SearchByBoW -- a frame feature that is
 // already matched is skipped (:216-217) -- stays inside a node: one wave per node walks that node's keyframe features in order
 // (grid = 1 replays all nodes in order, used when a caller's lists share a feature between nodes).  The rotation histogram
-// only needs counts; k_bow_finish builds it, prunes and counts.  assigned / qbin arrive as -1, *nmatches as 0.
+// only needs counts; k_rot_finish (match_rot.h) builds it, prunes and counts.  assigned / qbin arrive as -1, *nmatches as 0.
 __global__ __launch_bounds__(64) void k_search_bow(BowArgs A) {
     const int lane = threadIdx.x;
     for (int nd = blockIdx.x; nd < A.nnodes; nd += gridDim.x) {
@@ -1003,54 +889,13 @@ __global__ __launch_bounds__(64) void k_search_bow(BowArgs A) {
             if (second != ~0ull && (int)(second >> 32) < 256) bestDist2 = (int)(second >> 32);
             if ((A.strictTh ? bestDist1 < TH_LOW : bestDist1 <= TH_LOW) && (float)bestDist1 < __fmul_rn(A.nnratio, (float)bestDist2)) {
                 if (lane == 0) {
-                    if (A.checkOri) {
-                        float rot = __fsub_rn(A.kpKF[ik].angle, A.kpF[bestIdxF].angle);
-                        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                        int bin = (int)roundf(__fmul_rn(rot, 1.0f / HISTO_LENGTH));
-                        if (bin == HISTO_LENGTH) bin = 0;
-                        A.qbin[bestIdxF] = bin;
-                    }
+                    if (A.checkOri) A.qbin[bestIdxF] = rot_bin(A.kpKF[ik].angle, A.kpF[bestIdxF].angle);
                     A.assigned[bestIdxF] = ik;
                 }
                 __syncthreads();          // the next keyframe feature of this node must see the assignment
             }
         }
     }
-}
-__global__ __launch_bounds__(256) void k_bow_finish(int* __restrict__ assigned, const int* __restrict__ qbin, int nF, int checkOri, int* __restrict__ nmatches) {
-    __shared__ int hist[HISTO_LENGTH];
-    __shared__ int keep[3];
-    __shared__ int total;
-    const int t = threadIdx.x;
-    if (t < HISTO_LENGTH) hist[t] = 0;
-    if (t == 0) total = 0;
-    __syncthreads();
-    if (checkOri) {
-        for (int i = t; i < nF; i += 256) if (assigned[i] >= 0) atomicAdd(&hist[qbin[i]], 1);
-        __syncthreads();
-        if (t == 0) {
-            int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < HISTO_LENGTH; ++i) {
-                const int c = hist[i];
-                if (c > max1) { max3 = max2; max2 = max1; max1 = c; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (c > max2) { max3 = max2; max2 = c; ind3 = ind2; ind2 = i; }
-                else if (c > max3) { max3 = c; ind3 = i; }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-            keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-        }
-        __syncthreads();
-    }
-    int cnt = 0;
-    for (int i = t; i < nF; i += 256) {
-        if (assigned[i] < 0) continue;
-        if (checkOri) { const int bn = qbin[i]; if (bn != keep[0] && bn != keep[1] && bn != keep[2]) { assigned[i] = -1; continue; } }
-        ++cnt;
-    }
-    atomicAdd(&total, cnt);
-    __syncthreads();
-    if (t == 0) *nmatches = total;
 }
 
 // ---------------------------------------------------------------- SearchByBoW of a batch (sslam_orb_search_by_bow_batch_dev)
@@ -1070,13 +915,6 @@ struct BowBatchArgs {
     float nnratio; int checkOri;
     int* assigned; int* nmatches;
 };
-__device__ __forceinline__ int bow_rot_bin(float angleKF, float angleF) {
-    float rot = __fsub_rn(angleKF, angleF);
-    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-    int bin = (int)roundf(__fmul_rn(rot, 1.0f / HISTO_LENGTH));
-    if (bin == HISTO_LENGTH) bin = 0;
-    return min(max(bin, 0), HISTO_LENGTH - 1);      // angles of [0, 360) never need it; the histogram index stays in range whatever a row holds
-}
 // kLds: the frame side in dynamic LDS -- descriptors [2 cap] uint4, node ids [cap], live assignment [cap] (BOW_BATCH_ROW_BYTES per row);
 // otherwise descriptors and node ids in the caller's buffers and the live assignment in the pair's output rows
 template <bool kLds>
@@ -1145,27 +983,16 @@ __global__ __launch_bounds__(64 * BOW_BATCH_WAVES) void k_search_bow_batch(BowBa
     if (A.checkOri) {
         for (int j = tid; j < nf; j += NT) {
             const int a = asg[j];
-            if (a >= 0) atomicAdd(&hist[bow_rot_bin(kpKF[a].angle, kpF[j].angle)], 1);
+            if (a >= 0) atomicAdd(&hist[min(max(rot_bin(kpKF[a].angle, kpF[j].angle), 0), HISTO_LENGTH - 1)], 1);      // angles of [0, 360) never need the clamp; the histogram index stays in range whatever a row holds
         }
         __syncthreads();
-        if (tid == 0) {
-            int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;      // ComputeThreeMaxima
-            for (int i = 0; i < HISTO_LENGTH; ++i) {
-                const int c = hist[i];
-                if (c > max1) { max3 = max2; max2 = max1; max1 = c; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (c > max2) { max3 = max2; max2 = c; ind3 = ind2; ind2 = i; }
-                else if (c > max3) { max3 = c; ind3 = i; }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-            keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-        }
+        if (tid == 0) three_maxima(hist, keep[0], keep[1], keep[2]);
         __syncthreads();
     }
     int cnt = 0;
     for (int j = tid; j < nf; j += NT) {
         int a = asg[j];
-        if (a >= 0 && A.checkOri) { const int bn = bow_rot_bin(kpKF[a].angle, kpF[j].angle); if (bn != keep[0] && bn != keep[1] && bn != keep[2]) a = -1; }
+        if (a >= 0 && A.checkOri && !rot_kept(min(max(rot_bin(kpKF[a].angle, kpF[j].angle), 0), HISTO_LENGTH - 1), keep[0], keep[1], keep[2])) a = -1;
         cnt += a >= 0;
         out[j] = a;
     }

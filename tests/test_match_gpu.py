@@ -645,6 +645,43 @@ def test_search_by_bow_overlapping_nodes(fe, ctx, oracle):
     np.testing.assert_array_equal(a, oa)
 
 
+@pytest.mark.parametrize("entry", ["bow", "bow_keyframes", "triangulation"])
+def test_decreasing_node_offsets_are_rejected(fe, ctx, entry):
+    """node offsets that go down -- {0, 100, 5}: the total says 5, the first list 100 -- in either list of every matcher that takes CSR node lists:
+    SSLAM_ERR_INVALID before anything is staged or launched (no kernel is recorded), the count at 0 and the output at -1"""
+    import ctypes as C
+    L = fe.lib()
+    rng = np.random.default_rng(17)
+    n = 8
+    kp = np.zeros(n, fe.KP_DTYPE); kp["x"] = rng.uniform(50, 600, n); kp["y"] = rng.uniform(50, 400, n); kp["size"] = 31
+    d = _rand_desc(rng, n); ones = np.ones(n, np.uint8)
+    good = np.array([0, 3, 5], np.int32); bad = np.array([0, 100, 5], np.int32); idx = np.arange(5, dtype=np.int32)
+    sc = np.ones(8, np.float32); F = (C.c_float * 9)(*([0.0] * 8 + [1.0]))
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    f1 = ctx.frame_upload(0, kp, d); f2 = ctx.frame_upload(0, kp, d)
+    assert L.sslam_profile_enable(ctx.h, 1) == 0
+    try:
+        for ptr1, ptr2 in ((good, good), (bad, good), (good, bad)):
+            out = np.full(n, -7, np.int32); nm = C.c_int(-7)
+            if entry == "bow":
+                rc = L.sslam_orb_search_by_bow(ctx.h, p(kp), p(d), p(ones), n, p(kp), p(d), n, p(ptr1), p(ptr2), 2, p(idx), p(idx), C.c_float(0.9), 1, p(out), C.byref(nm))
+            elif entry == "bow_keyframes":
+                rc = L.sslam_orb_search_by_bow_keyframes(ctx.h, p(kp), p(d), p(ones), n, p(kp), p(d), p(ones), n, p(ptr1), p(ptr2), 2, p(idx), p(idx), C.c_float(0.8), 1, p(out),
+                                                         C.byref(nm))
+            else:
+                rc = L.sslam_orb_search_for_triangulation(ctx.h, f1.h, f2.h, p(ones), p(ones), p(ptr1), p(ptr2), 2, p(idx), p(idx), F, C.c_float(-2000.0), C.c_float(300.0),
+                                                          p(sc), p(sc), 8, 0, 1, p(out), C.byref(nm))
+            launched = L.sslam_profile_drain(ctx.h, None, None, None, 0)
+            if ptr1 is good and ptr2 is good:
+                assert rc == 0 and launched == 2 and nm.value >= 0, (rc, launched, L.sslam_last_error())      # the same call with well-formed lists runs
+            else:
+                assert rc == fe.SSLAM_ERR_INVALID and b"non-decreasing" in L.sslam_last_error(), (rc, L.sslam_last_error())
+                assert launched == 0 and nm.value == 0 and (out == -1).all()
+    finally:
+        L.sslam_profile_enable(ctx.h, 0)
+        f1.close(); f2.close()
+
+
 def _bow_sets(bw, bv, fn, fp, ff):
     return {int(w): float(v) for w, v in zip(bw, bv)}, {int(fn[j]): ff[fp[j]:fp[j + 1]].tolist() for j in range(len(fn))}
 

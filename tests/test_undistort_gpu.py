@@ -71,6 +71,7 @@ def test_batch_undistortion(fe, ctx, model):
     d_out = torch.from_numpy(np.tile(sentinel, nf * cap)).cuda()
     ctx.undistort_keypoints_batch_dev(cam, d_kp, d_cnt, nf, cap, d_out)
     d_inplace = d_kp.clone()
+    torch.cuda.synchronize()          # the clone runs on torch's stream, the call below on the context's
     ctx.undistort_keypoints_batch_dev(cam, d_inplace, d_cnt, nf, cap, d_inplace)
     torch.cuda.synchronize()
     out = d_out.cpu().numpy().view(fe.KP_DTYPE).reshape(nf, cap)
