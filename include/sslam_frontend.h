@@ -613,7 +613,9 @@ int sslam_group_rank(const sslam_group* group);      /* 0 in the single-process 
 
 /* Compacts the per-frame results of a *_batch_dev call into the record stream above: frame i of the batch becomes the record with
  * header.frame = frame0 + i*frame_step.  d_kl / d_ldesc / d_linefn / d_nl may be NULL (no lines).  d_out[out_capacity]; *d_total_bytes
- * (device) receives the stream length, or UINT64_MAX when it does not fit.  Enqueued on `stream`, no synchronisation. */
+ * (device) receives the stream length, or UINT64_MAX when it does not fit.  Enqueued on `stream`, no synchronisation.  Calls on different streams
+ * of one context are ordered on the context's buffer of per-frame offsets by an event (the later call's kernels wait for the earlier call's); a call
+ * that needs a larger buffer than the context holds waits on the host for the previous call before it replaces it. */
 int sslam_pack_records_dev(sslam_ctx* ctx, int nframes, int frame0, int frame_step,
                            const sslam_keypoint* d_kp, const uint8_t* d_desc, const int32_t* d_nkp, int cap,
                            const sslam_keyline* d_kl, const uint8_t* d_ldesc, const double* d_linefn, const int32_t* d_nl, int lcap,

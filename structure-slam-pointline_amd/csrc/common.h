@@ -88,7 +88,7 @@ struct sslam_prof_rec { const char* name; hipEvent_t a, b; };
 
 // Slots of sslam_ctx::scratch and ::pinned (match.hip) with their users.  A slot with several users is safe to share because every one of
 // them holds ctx->mu for the whole call and synchronises the stream before it returns.  The two buffers whose users return with kernels still
-// running on the caller's stream are no slots: sslam_ctx::knnExpand and ::projBatch, a StreamOrderedBuf each.
+// running on the caller's stream are no slots: sslam_ctx::knnExpand, ::projBatch and ::recordOffsets, a StreamOrderedBuf each.
 enum {
     SCR_KNN_Q = 0, SCR_KNN_T = 1, SCR_KNN_OUT = 2,      // sslam_hamming_knn2, sslam_hamming_matrix: query rows, train rows, result
     SCR_SFI_STATE = 3,       // sslam_orb_search_for_initialization_batch_dev: per-pair state (SfiArgs::scratch)
@@ -116,9 +116,7 @@ struct sslam_ctx {
     sslam::DevBuf colorIn, colorGray;      // sslam_gray_from_color: the host frame and its gray plane on the device (color.hip)
     sslam::StreamOrderedBuf knnExpand;      // sslam_hamming_knn2_batch_dev: the train rows as int8 matrix-core operands (match_knn.h)
     sslam::StreamOrderedBuf projBatch;      // sslam_search_by_projection_batch_dev: the arena of one slice of frames
-    sslam::DevBuf recordOffsets[4];   // sslam_pack_records_dev: per-frame offsets of the record stream, one buffer per stream that packs
-    void* recordOffsetsStream[4] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned long recordOffsetsUse[4] = {0, 0, 0, 0}, recordOffsetsClock = 0;      // least-recently-used recycling of the four slots
+    sslam::StreamOrderedBuf recordOffsets;  // sslam_pack_records_dev: per-frame offsets of the record stream (group.hip)
     sslam::HostPinned pinned[PIN_COUNT];   // staging mirrors of the matcher arenas (PIN_*)
     int num_cus = 0;
     void* batchCache = nullptr;                  // sslam_frontend_batch: staging buffers, streams, events kept between calls (batch.hip)

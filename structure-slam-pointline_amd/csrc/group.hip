@@ -1,43 +1,33 @@
 // Multi-GPU batch mode (SURVEY.md §8(b),(e); north_star: "shards independent images across the 8 GPUs of one node with RCCL over
 // xGMI only for the final keypoint/line gather").  Frames are independent units, so the path has exactly one exchange step: the
 // compacted per-frame records of every GPU go to the root GPU.  This file holds
+//   * the binding of librccl with dlopen (the table and the grouped ncclSend / ncclRecv to the root: group_exchange.h; the testing library's stand-in: rccl_standin.h),
 //   * the record stream (pack kernels, host-side unpack),
-//   * the group handle in its two forms (one process driving G devices / one process per GPU) over RCCL bound with dlopen,
-//   * the gather (sizes first, then grouped ncclSend / ncclRecv),
-//   * sslam_frontend_batch_sharded, the host-buffer batch entry point over all GPUs of a single-process group.
+//   * the group handle in its two forms (one process driving G devices / one process per GPU),
+//   * sslam_group_gather_dev (the lengths first, all-gathered; then the exchange),
+//   * the shard layout and sslam_frontend_batch_sharded, the host-buffer batch entry point over all GPUs of a single-process group.
 // xGMI is point to point (7 links per GPU): a gather to one root is bound by the root's ingest, G-1 links x ~50 GB/s effective.  At
 // ~80 KB per 640x480 frame that is >4 M frames/s of ingest, two orders of magnitude above what eight GPUs extract; the exchange is
 // latency, not bandwidth.
-#include "common.h"
-#include <atomic>
+#include "group_exchange.h"
 #include <dlfcn.h>
 #include <algorithm>
-#include <chrono>
 #include <condition_variable>
 #include <thread>
+#ifdef SSLAM_TESTING      // libsslam_frontend_testing.so only: groups created while the TEST entry point (include/sslam_testing.h) is on bind the in-process stand-in
+#include "rccl_standin.h" // instead of librccl, and may hold more members than GPUs are visible (dealt round-robin).  The entry point returns the previous setting.
+extern "C" int sslam_testing_use_rccl_standin(int on) { return sslam::gStandinRequested.exchange(on ? 1 : 0); }
+static bool fake_rccl_requested() { return sslam::gStandinRequested.load() != 0; }
+#else                     // the product library holds no stand-in: a group binds librccl or fails
+static bool fake_rccl_requested() { return false; }
+static sslam::Rccl* rccl_fake() { return nullptr; }
+#endif
 
 using namespace sslam;
 
 namespace {
 
 // ------------------------------------------------------------------ RCCL, bound at run time
-typedef struct ncclComm* ncclComm_t;
-struct NcclUid { char internal[128]; };
-struct Rccl {
-    void* h = nullptr;
-    int (*GetUniqueId)(NcclUid*) = nullptr;
-    int (*CommInitRank)(ncclComm_t*, int, NcclUid, int) = nullptr;
-    int (*CommInitAll)(ncclComm_t*, int, const int*) = nullptr;
-    int (*CommDestroy)(ncclComm_t) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    int (*Send)(const void*, size_t, int, int, ncclComm_t, hipStream_t) = nullptr;
-    int (*Recv)(void*, size_t, int, int, ncclComm_t, hipStream_t) = nullptr;
-    int (*AllGather)(const void*, void*, size_t, int, ncclComm_t, hipStream_t) = nullptr;
-    const char* (*GetErrorString)(int) = nullptr;
-};
-constexpr int kNcclUint8 = 1, kNcclUint64 = 5;      // ncclDataType_t (rccl.h)
-
 Rccl* rccl_real() {
     static Rccl R;
     static std::once_flag once;
@@ -64,161 +54,13 @@ Rccl* rccl_real() {
     return R.h ? &R : nullptr;
 }
 
-#ifdef SSLAM_TESTING      // libsslam_frontend_testing.so only
-// ------------------------------------------------------------------ sslam_testing_use_rccl_standin(1) (include/sslam_testing.h): an in-process stand-in for the RCCL entry points
-// N > 1 has never run on hardware here (one GPU per box), so the group code's multi-member paths -- a host thread per device, uneven tails,
-// the collective error agreement, grouped send / receive to the root -- had no execution at all.  With this table selected at group creation
-// the "devices" of a group are contexts (streams) of whatever GPUs are visible, dealt round-robin, and the collectives are host-mediated
-// device-to-device copies with NCCL's matching rules: a send to p pairs with p's receive from the sender in posting order, calls between
-// GroupStart / GroupEnd are issued together, an all-gather is a rendezvous of all ranks.  Same process only (ranks are threads).  It moves
-// real bytes between real device buffers through the same code paths; it says nothing about xGMI -- the scaling run stays the driver's.
-struct FakeWorld {
-    int nranks = 0, refs = 0;
-    std::mutex mu; std::condition_variable cv;
-    struct Msg { unsigned long id; int src, dst; const void* ptr; size_t bytes; bool taken; };
-    std::vector<Msg> box;                           // posted sends, in posting order (entries are named by id: the vector shifts when a sender clears its own)
-    unsigned long nextId = 1;
-    std::vector<const void*> agPtr; int agArrived = 0, agLeft = 0, agGen = 0;
-};
-struct FakeComm { FakeWorld* w; int rank; };
-struct FakeOp { int kind; const void* sptr; void* rptr; size_t bytes; int peer; FakeComm* c; hipStream_t st; unsigned long id; };      // 0 send, 1 recv
-// every wait of the stand-in is bounded: a protocol error of the group code must fail a test, not hang the suite
-constexpr std::chrono::seconds kFakeWait(60);
-thread_local int tFakeDepth = 0;
-thread_local std::vector<FakeOp> tFakeOps;
-std::mutex gFakeMu;
-std::vector<std::pair<NcclUid, FakeWorld*>> gFakeWorlds;      // worlds being assembled by ncclCommInitRank, keyed by unique id
-int gFakeIdCounter = 0;
-
-size_t fake_dtype_bytes(int dt) { return dt == kNcclUint64 ? 8 : 1; }
-int fake_flush_ops(std::vector<FakeOp>& ops);
-int fake_flush() {
-    std::vector<FakeOp> ops; ops.swap(tFakeOps);
-    const int rc = fake_flush_ops(ops);
-    if (rc != 0)      // an error leaves nothing behind: the rank's own posted sends (device pointers that may die with the caller's buffers) are withdrawn, or a later receive could match them
-        for (FakeOp& o : ops) if (o.kind == 0 && o.id) {
-            std::lock_guard<std::mutex> lk(o.c->w->mu);
-            for (size_t i = 0; i < o.c->w->box.size(); ++i) if (o.c->w->box[i].id == o.id) { o.c->w->box.erase(o.c->w->box.begin() + i); break; }
-            o.c->w->cv.notify_all();
-        }
-    return rc;
-}
-int fake_flush_ops(std::vector<FakeOp>& ops) {
-    // sends first: publish (the data must be final: drain the sender's stream), then receives (wait for the partner's publication, copy,
-    // acknowledge), then wait until every own send was taken -- a rank that posts both directions in one group cannot block itself
-    for (FakeOp& o : ops) if (o.kind == 0) {
-        if (hipStreamSynchronize(o.st) != hipSuccess) return 1;
-        std::lock_guard<std::mutex> lk(o.c->w->mu);
-        o.id = o.c->w->nextId++;
-        o.c->w->box.push_back({o.id, o.c->rank, o.peer, o.sptr, o.bytes, false});
-        o.c->w->cv.notify_all();
-    }
-    auto find = [](FakeWorld* w, unsigned long id) -> FakeWorld::Msg* { for (auto& m : w->box) if (m.id == id) return &m; return nullptr; };
-    for (FakeOp& o : ops) if (o.kind == 1) {
-        FakeWorld* w = o.c->w; const void* src = nullptr; unsigned long id = 0; size_t bytes = 0;
-        {
-            std::unique_lock<std::mutex> lk(w->mu);
-            // the oldest untaken send of that peer to this rank (receives of one rank are issued by one thread, one after the other)
-            if (!w->cv.wait_for(lk, kFakeWait, [&] { for (auto& m : w->box) if (!m.taken && m.src == o.peer && m.dst == o.c->rank) { id = m.id; return true; } return false; })) return 4;
-            FakeWorld::Msg* m = find(w, id);
-            src = m->ptr; bytes = m->bytes;
-        }
-        if (bytes != o.bytes) return 2;               // NCCL would hang or corrupt on mismatched sizes: here it is an error
-        // stream-ordered on the receiver's stream like the real receive, then drained: the sender may reuse its buffer once this returns
-        if (o.bytes && hipMemcpyAsync(o.rptr, src, o.bytes, hipMemcpyDeviceToDevice, o.st) != hipSuccess) return 1;
-        if (hipStreamSynchronize(o.st) != hipSuccess) return 1;
-        std::lock_guard<std::mutex> lk(w->mu);
-        if (FakeWorld::Msg* m = find(w, id)) m->taken = true;
-        w->cv.notify_all();
-    }
-    for (FakeOp& o : ops) if (o.kind == 0) {
-        FakeWorld* w = o.c->w;
-        std::unique_lock<std::mutex> lk(w->mu);
-        if (!w->cv.wait_for(lk, kFakeWait, [&] { FakeWorld::Msg* m = find(w, o.id); return !m || m->taken; })) return 4;
-        for (size_t i = 0; i < w->box.size(); ++i) if (w->box[i].id == o.id) { w->box.erase(w->box.begin() + i); break; }
-    }
-    return 0;
-}
-int fakeGetUniqueId(NcclUid* u) { std::lock_guard<std::mutex> lk(gFakeMu); memset(u, 0, sizeof(*u)); snprintf(u->internal, sizeof(u->internal), "sslam-fake-rccl-%d", ++gFakeIdCounter); return 0; }
-int fakeCommInitAll(ncclComm_t* comms, int n, const int*) {
-    FakeWorld* w = new FakeWorld(); w->nranks = n; w->refs = n; w->agPtr.assign(n, nullptr);
-    for (int r = 0; r < n; ++r) comms[r] = (ncclComm_t) new FakeComm{w, r};
-    return 0;
-}
-int fakeCommInitRank(ncclComm_t* comm, int n, NcclUid id, int rank) {
-    std::lock_guard<std::mutex> lk(gFakeMu);
-    FakeWorld* w = nullptr;
-    for (auto& e : gFakeWorlds) if (memcmp(e.first.internal, id.internal, sizeof(id.internal)) == 0) w = e.second;
-    if (!w) { w = new FakeWorld(); w->nranks = n; w->agPtr.assign(n, nullptr); gFakeWorlds.push_back({id, w}); }
-    if (w->nranks != n || rank < 0 || rank >= n) return 3;
-    ++w->refs;
-    *comm = (ncclComm_t) new FakeComm{w, rank};
-    return 0;
-}
-int fakeCommDestroy(ncclComm_t c_) {
-    FakeComm* c = (FakeComm*)c_; if (!c) return 0;
-    std::lock_guard<std::mutex> lk(gFakeMu);
-    if (--c->w->refs == 0) {
-        for (size_t i = 0; i < gFakeWorlds.size(); ++i) if (gFakeWorlds[i].second == c->w) { gFakeWorlds.erase(gFakeWorlds.begin() + i); break; }
-        delete c->w;
-    }
-    delete c; return 0;
-}
-int fakeGroupStart() { ++tFakeDepth; return 0; }
-int fakeGroupEnd() { if (--tFakeDepth > 0) return 0; tFakeDepth = 0; return fake_flush(); }
-int fakeSend(const void* p, size_t count, int dt, int peer, ncclComm_t c, hipStream_t st) {
-    tFakeOps.push_back({0, p, nullptr, count * fake_dtype_bytes(dt), peer, (FakeComm*)c, st, 0});
-    return tFakeDepth ? 0 : fake_flush();
-}
-int fakeRecv(void* p, size_t count, int dt, int peer, ncclComm_t c, hipStream_t st) {
-    tFakeOps.push_back({1, nullptr, p, count * fake_dtype_bytes(dt), peer, (FakeComm*)c, st, 0});
-    return tFakeDepth ? 0 : fake_flush();
-}
-int fakeAllGather(const void* sp, void* rp, size_t count, int dt, ncclComm_t c_, hipStream_t st) {
-    FakeComm* c = (FakeComm*)c_; FakeWorld* w = c->w; const size_t bytes = count * fake_dtype_bytes(dt);
-    if (hipStreamSynchronize(st) != hipSuccess) return 1;
-    std::vector<const void*> ptrs;
-    {
-        std::unique_lock<std::mutex> lk(w->mu);
-        if (!w->cv.wait_for(lk, kFakeWait, [&] { return w->agLeft == 0; })) return 4;              // the previous round has been left by everybody
-        const int gen = w->agGen;
-        w->agPtr[c->rank] = sp;
-        if (++w->agArrived == w->nranks) { w->agLeft = w->nranks; w->agArrived = 0; ++w->agGen; w->cv.notify_all(); }
-        else if (!w->cv.wait_for(lk, kFakeWait, [&] { return w->agGen != gen; })) return 4;
-        ptrs = w->agPtr;
-    }
-    int rc = 0;
-    for (int r = 0; r < w->nranks && !rc; ++r) if (bytes && hipMemcpyAsync((char*)rp + (size_t)r * bytes, ptrs[r], bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = 1;
-    if (hipStreamSynchronize(st) != hipSuccess) rc = 1;
-    std::unique_lock<std::mutex> lk(w->mu);
-    if (--w->agLeft == 0) w->cv.notify_all();
-    if (!w->cv.wait_for(lk, kFakeWait, [&] { return w->agLeft == 0; })) return 4;                  // nobody's send buffer is reused before everybody has copied it
-    return rc;
-}
-const char* fakeGetErrorString(int e) { return e == 4 ? "fake rccl: a peer did not show up within 60 s" : e == 2 ? "fake rccl: send / receive sizes differ" : e == 3 ? "fake rccl: inconsistent communicator arguments" : "fake rccl: HIP error"; }
-Rccl* rccl_fake() {
-    static Rccl F;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        F.h = (void*)&F; F.GetUniqueId = fakeGetUniqueId; F.CommInitRank = fakeCommInitRank; F.CommInitAll = fakeCommInitAll; F.CommDestroy = fakeCommDestroy;
-        F.GroupStart = fakeGroupStart; F.GroupEnd = fakeGroupEnd; F.Send = fakeSend; F.Recv = fakeRecv; F.AllGather = fakeAllGather; F.GetErrorString = fakeGetErrorString;
-    });
-    return &F;
-}
-// selected by a TEST entry point only (sslam_testing_use_rccl_standin, include/sslam_testing.h) -- no environment variable changes which library a product group binds
-std::atomic<int> gStandinRequested{0};
-bool fake_rccl_requested() { return gStandinRequested.load() != 0; }
-#else       // the product library holds no stand-in: a group binds librccl or fails
-bool fake_rccl_requested() { return false; }
-Rccl* rccl_fake() { return nullptr; }
-#endif      // SSLAM_TESTING
 // the table a NEW group binds (kept in the group: a process may hold real and stand-in groups side by side)
 Rccl* rccl() { return fake_rccl_requested() ? rccl_fake() : rccl_real(); }
 #define SSLAM_NCCL(api, expr)                                                                                         \
     do {                                                                                                              \
         int _r = (expr);                                                                                              \
         if (_r != 0) {                                                                                                \
-            sslam::set_error("%s failed: %s (rccl status %d)", #expr, (api) && (api)->GetErrorString ? (api)->GetErrorString(_r) : "rccl error", _r);      \
+            sslam::set_error("%s failed: %s (rccl status %d)", #expr, rccl_error_text((api), _r), _r);      \
             return SSLAM_ERR_HIP;                                                                                     \
         }                                                                                                             \
     } while (0)
@@ -321,34 +163,16 @@ extern "C" int sslam_pack_records_dev(sslam_ctx* ctx, int nframes, int frame0, i
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);      // the whole call: launches included (every entry point serialises on the context)
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    int rc;
-    // the per-frame offsets live in a buffer that belongs to the STREAM of the call (a small ring of them per context): packs on different
-    // streams never share one, and a buffer is only ever freed (to grow) after its own stream has drained
-    DevBuf* offBuf = nullptr;
-    for (int i = 0; i < 4 && !offBuf; ++i) if (ctx->recordOffsetsStream[i] == (void*)st && ctx->recordOffsets[i].p) offBuf = &ctx->recordOffsets[i];
-    if (!offBuf) {
-        int slot = -1;
-        for (int i = 0; i < 4 && slot < 0; ++i) if (!ctx->recordOffsets[i].p) slot = i;
-        if (slot < 0) {                                      // more than four streams: recycle the least recently used slot once its work is done
-            slot = 0;
-            for (int i = 1; i < 4; ++i) if (ctx->recordOffsetsUse[i] < ctx->recordOffsetsUse[slot]) slot = i;
-            // the remembered handle may belong to a stream the caller has destroyed since (or to a new stream that reuses the handle): a failed
-            // synchronise is not an error of this call -- drain the device instead, after which nothing can still read the buffer
-            if (hipStreamSynchronize((hipStream_t)ctx->recordOffsetsStream[slot]) != hipSuccess) { (void)hipGetLastError(); SSLAM_HIP(hipDeviceSynchronize()); }
-        }
-        ctx->recordOffsetsStream[slot] = (void*)st; offBuf = &ctx->recordOffsets[slot];
-    }
-    ctx->recordOffsetsUse[offBuf - ctx->recordOffsets] = ++ctx->recordOffsetsClock;
-    if ((size_t)(nframes + 1) * 8 > offBuf->cap) SSLAM_HIP(hipStreamSynchronize(st));      // a growing buffer is freed first: nothing may still read it
-    if ((rc = offBuf->ensure(sizeof(unsigned long long) * ((size_t)nframes + 1)))) return rc;
-    unsigned long long* off = offBuf->as<unsigned long long>();
+    // k_record_offsets writes the per-frame offsets and k_record_copy reads them on the caller's stream after this call has returned (StreamOrderedBuf, common.h)
+    if (int rc = ctx->recordOffsets.acquire(st, sizeof(unsigned long long) * ((size_t)nframes + 1))) return rc;
+    unsigned long long* off = ctx->recordOffsets.as<unsigned long long>();
     hipLaunchKernelGGL(k_record_offsets, dim3(1), dim3(1024), 0, st, d_nkp, lines ? d_nl : nullptr, nframes, cap, lcap, off, (unsigned long long)out_capacity,
                        (unsigned long long*)d_total_bytes);
     hipLaunchKernelGGL(k_record_copy, dim3(nframes), dim3(256), 0, st, frame0, frame_step, (const unsigned*)d_kp, (const unsigned*)d_desc, d_nkp, cap,
                        (const unsigned*)d_kl, (const unsigned*)d_ldesc, (const unsigned*)d_linefn, lines ? d_nl : nullptr, lcap, off, nframes, (unsigned*)d_out,
                        (const unsigned long long*)d_total_bytes);
     SSLAM_HIP(hipGetLastError());
-    return SSLAM_OK;
+    return ctx->recordOffsets.mark(st);
 }
 
 extern "C" int sslam_unpack_records(const uint8_t* stream, uint64_t bytes, int nframes,
@@ -394,12 +218,6 @@ static void member_release(Member& m) {
     m = Member();
 }
 
-// TEST entry point (include/sslam_testing.h): groups created while this is on bind the in-process stand-in above instead of librccl, and may hold more members than
-// GPUs are visible (dealt round-robin).  Returns the previous setting.
-#ifdef SSLAM_TESTING
-extern "C" int sslam_testing_use_rccl_standin(int on) { return gStandinRequested.exchange(on ? 1 : 0); }
-#endif
-
 extern "C" int sslam_group_create(int ngpu, sslam_group** out) {
     if (!out || ngpu <= 0 || ngpu > 64) { set_error("sslam_group_create: invalid arguments"); return SSLAM_ERR_INVALID; }
     int have = 0;
@@ -417,7 +235,7 @@ extern "C" int sslam_group_create(int ngpu, sslam_group** out) {
         std::vector<int> devs(ngpu); std::vector<ncclComm_t> comms(ngpu, nullptr);
         for (int d = 0; d < ngpu; ++d) devs[d] = d % have;
         const int r = R->CommInitAll(comms.data(), ngpu, devs.data());
-        if (r != 0) { set_error("ncclCommInitAll failed: %s", R->GetErrorString ? R->GetErrorString(r) : "rccl error"); rc = SSLAM_ERR_HIP; }
+        if (r != 0) { set_error("ncclCommInitAll failed: %s", rccl_error_text(R, r)); rc = SSLAM_ERR_HIP; }
         else for (int d = 0; d < ngpu; ++d) { g->mem[d].comm = comms[d]; g->mem[d].api = R; }
     }
     if (rc != SSLAM_OK) { for (auto& m : g->mem) member_release(m); delete g; return rc; }
@@ -445,7 +263,7 @@ extern "C" int sslam_group_create_rank(int device, int rank, int nranks, const u
     g->mem.resize(1);
     NcclUid u; memcpy(u.internal, id, SSLAM_GROUP_ID_BYTES);
     const int r = g->api->CommInitRank(&g->mem[0].comm, nranks, u, rank);
-    if (r != 0) { set_error("ncclCommInitRank failed: %s", g->api->GetErrorString ? g->api->GetErrorString(r) : "rccl error"); delete g; return SSLAM_ERR_HIP; }
+    if (r != 0) { set_error("ncclCommInitRank failed: %s", rccl_error_text(g->api, r)); delete g; return SSLAM_ERR_HIP; }
     g->mem[0].api = g->api;
     if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess || g->dSizes.ensure(16 * (size_t)nranks + 16) != SSLAM_OK ||
         g->hSizes.ensure(16 * (size_t)nranks + 16) != SSLAM_OK) {
@@ -489,8 +307,7 @@ extern "C" int sslam_group_gather_dev(sslam_group* g, const uint8_t* d_send, con
     SSLAM_NCCL(R, R->AllGather(dPair, dAll, 2, kNcclUint64, comm, st));
     SSLAM_HIP(hipMemcpyAsync(hAll, dAll, 16 * (size_t)g->nranks, hipMemcpyDeviceToHost, st));
     SSLAM_HIP(hipStreamSynchronize(st));
-    std::vector<uint64_t> hSv((size_t)g->nranks);
-    uint64_t* hS = hSv.data();
+    std::vector<uint64_t> hS((size_t)g->nranks);
     uint64_t total = 0;
     for (int r = 0; r < g->nranks; ++r) {
         hS[r] = hAll[2 * r];
@@ -501,22 +318,11 @@ extern "C" int sslam_group_gather_dev(sslam_group* g, const uint8_t* d_send, con
         set_error("sslam_group_gather_dev: %llu bytes do not fit the root's receive buffer of %llu", (unsigned long long)total, (unsigned long long)hAll[1]);
         return SSLAM_ERR_CAPACITY;
     }
-    // 2. payload: one grouped send / receive per peer; the root's own stream is a device-to-device copy (or, for tests on one GPU, a
-    //    self send/recv through RCCL with SSLAM_GROUP_SELF_SENDRECV=1)
-    const bool selfRccl = getenv("SSLAM_GROUP_SELF_SENDRECV") != nullptr;
-    SSLAM_NCCL(R, R->GroupStart());
-    int rcN = 0;
-    if (g->rank == 0) {
-        uint64_t off = 0;
-        for (int r = 0; r < g->nranks && rcN == 0; ++r) {
-            if (hS[r] && (r != 0 || selfRccl)) rcN = R->Recv(d_recv + off, (size_t)hS[r], kNcclUint8, r, comm, st);
-            off += hS[r];
-        }
-        if (rcN == 0 && selfRccl && hS[0]) rcN = R->Send(d_send, (size_t)hS[0], kNcclUint8, 0, comm, st);
-    } else if (hS[g->rank]) rcN = R->Send(d_send, (size_t)hS[g->rank], kNcclUint8, 0, comm, st);
-    const int rcE = R->GroupEnd();
-    if (rcN != 0 || rcE != 0) { set_error("sslam_group_gather_dev: ncclSend / ncclRecv failed: %s", R->GetErrorString ? R->GetErrorString(rcN ? rcN : rcE) : "rccl error"); return SSLAM_ERR_HIP; }
-    if (g->rank == 0 && !selfRccl && hS[0]) SSLAM_HIP(hipMemcpyAsync(d_recv, d_send, (size_t)hS[0], hipMemcpyDeviceToDevice, st));
+    // 2. payload: one grouped send / receive per peer, the root's own stream a device-to-device copy or a self send / receive (group_exchange.h)
+    const GatherStatus x = gather_to_root(R, comm, g->rank, g->nranks, hS.data(), d_send, d_recv, root_sends_to_itself(), st);
+    if (x.rccl != 0 && !x.started) { set_error("R->GroupStart() failed: %s (rccl status %d)", rccl_error_text(R, x.rccl), x.rccl); return SSLAM_ERR_HIP; }
+    if (x.rccl != 0) { set_error("sslam_group_gather_dev: ncclSend / ncclRecv failed: %s", rccl_error_text(R, x.rccl)); return SSLAM_ERR_HIP; }
+    if (x.hip != hipSuccess) { set_error("hipMemcpyAsync(d_recv, d_send, (size_t)hS[0], hipMemcpyDeviceToDevice, st) failed: %s (%s:%d)", hipGetErrorString(x.hip), __FILE__, __LINE__); return SSLAM_ERR_HIP; }
     SSLAM_HIP(hipStreamSynchronize(st));
     if (g->rank == 0) for (int r = 0; r < g->nranks; ++r) bytes_per_rank_out[r] = hS[r];
     return SSLAM_OK;
@@ -542,9 +348,8 @@ extern "C" int sslam_shard_frame(int n, int ngpu, int chunk, int gpu, int slot) 
 extern "C" int sslam_shard_chunk_count(int n, int ngpu, int chunk, int gpu) {      // frames GPU `gpu` holds in chunk `chunk` (its slots 0 .. count-1)
     int C = 0, nChunks = 0;
     if (sslam_shard_layout(n, ngpu, &C, &nChunks) != SSLAM_OK || chunk < 0 || chunk >= nChunks || gpu < 0 || gpu >= ngpu) return 0;
-    int c = 0;
-    for (int j = 0; j < C; ++j) if (sslam_shard_frame(n, ngpu, chunk, gpu, j) >= 0) c = j + 1;
-    return c;
+    const int mine = (n - gpu + ngpu - 1) / ngpu;      // frames gpu, gpu + ngpu, ... below n
+    return std::max(0, std::min(mine - chunk * C, C));
 }
 
 // ------------------------------------------------------------------ host-buffer batch over all GPUs of a single-process group
@@ -586,7 +391,7 @@ extern "C" int sslam_frontend_batch_sharded(sslam_group* g, const sslam_frontend
     (void)sslam_shard_layout(n, G, &C, &nChunks);
     const size_t fpx = (size_t)w * h;
     const uint64_t sendCap = sslam_record_stream_capacity(C, cap, lines ? lcap : 0);
-    const bool selfRccl = getenv("SSLAM_GROUP_SELF_SENDRECV") != nullptr;
+    const bool selfRccl = root_sends_to_itself();
     Barrier bar; bar.count = G;
     std::vector<int> status(G, SSLAM_OK), soft(G, SSLAM_OK), allocOk(G, 1);
     std::vector<std::string> errs(G), softErrs(G);
@@ -651,21 +456,12 @@ extern "C" int sslam_frontend_batch_sharded(sslam_group* g, const sslam_frontend
             if (rc != SSLAM_OK) myBytes = 0;      // a member with a real failure still takes part in the exchange (with nothing), so that nobody hangs
             sizes[d] = myBytes;
             bar.wait();
-            // the exchange step: grouped ncclSend / ncclRecv to device 0
+            // the exchange step: grouped ncclSend / ncclRecv to device 0 (group_exchange.h)
             uint64_t total = 0;
             for (int r = 0; r < G; ++r) total += sizes[r];
-            int e1 = R->GroupStart(), e2 = 0;
-            if (d == 0) {
-                uint64_t off = 0;
-                for (int r = 0; r < G; ++r) {
-                    if (sizes[r] && (r != 0 || selfRccl) && !e2) e2 = R->Recv(m.dRecv.as<uint8_t>() + off, (size_t)sizes[r], kNcclUint8, r, m.comm, st);
-                    off += sizes[r];
-                }
-                if (selfRccl && sizes[0] && !e2) e2 = R->Send(m.dSend.p, (size_t)sizes[0], kNcclUint8, 0, m.comm, st);
-            } else if (sizes[d]) e2 = R->Send(m.dSend.p, (size_t)sizes[d], kNcclUint8, 0, m.comm, st);
-            const int e3 = R->GroupEnd();
-            if (e1 || e2 || e3) fail(SSLAM_ERR_HIP, "ncclSend / ncclRecv failed");
-            if (d == 0 && !selfRccl && sizes[0] && hipMemcpyAsync(m.dRecv.p, m.dSend.p, (size_t)sizes[0], hipMemcpyDeviceToDevice, st) != hipSuccess) fail(SSLAM_ERR_HIP, "D2D failed");
+            const GatherStatus x = gather_to_root(R, m.comm, d, G, sizes.data(), m.dSend.p, m.dRecv.p, selfRccl, st);
+            if (x.rccl != 0) fail(SSLAM_ERR_HIP, "ncclSend / ncclRecv failed");
+            if (x.hip != hipSuccess) fail(SSLAM_ERR_HIP, "D2D failed");
             if (d == 0 && total) {
                 if (hipMemcpyAsync(m.hRecv.p, m.dRecv.p, (size_t)total, hipMemcpyDeviceToHost, st) != hipSuccess) fail(SSLAM_ERR_HIP, "D2H failed");
             }

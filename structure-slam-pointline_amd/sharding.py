@@ -53,6 +53,23 @@ def gather_streams(dist, stream, world, rank):
     return torch.cat([bufs[r][:sizes[r]] for r in range(world)]), sizes
 
 
+def pack_step(fe, ctx, pipe, rank, world, send, cap_bytes, total):
+    """sslam_pack_records_dev of the step pipe has just run (torch's current stream) into send / total.  The pack runs on the pipeline's own
+    (non-default) stream, ordered after this step's kernels of both branches and before the next step's (stream handle 0 would mean "the context's
+    stream" in the C ABI, which is not ordered with the pipeline at all).  Returns the pipeline's stream."""
+    p, c = pipe, pipe.feat["cur"]
+    lines = p.with_lines
+    s1, _ = p._streams()
+    cur = torch.cuda.current_stream(p.dev)
+    s1.wait_stream(cur)
+    with torch.cuda.stream(s1):
+        fe.pack_records_dev(ctx, p.B, rank, world, c["kp"], c["desc"], c["n"], p.cap,
+                            c["kl"] if lines else None, c["ldesc"] if lines else None, c["linefn"] if lines else None, c["nl"] if lines else None, p.lcap,
+                            send, cap_bytes, total, p._stream())
+    cur.wait_stream(s1)
+    return s1
+
+
 class GroupGather:
     """The exchange step through the C ABI (one process per GPU): pack the step's results into the record stream on the device, then
     sslam_group_gather_dev on a side thread -- the gather of step k runs while the kernels of step k+1 execute; at most one is in flight."""
@@ -73,19 +90,8 @@ class GroupGather:
         """call on the stream the step's kernels were launched on (torch's current stream)"""
         self.wait()
         s = self.k & 1; self.k += 1
-        p, c = self.pipe, self.pipe.feat["cur"]
-        lines = p.with_lines
-        # the pack runs on the pipeline's own (non-default) stream, ordered after this step's kernels of both branches and before the next
-        # step's (stream handle 0 would mean "the context's stream" in the C ABI, which is not ordered with the pipeline at all)
-        s1, _ = p._streams()
-        cur = torch.cuda.current_stream(p.dev)
-        s1.wait_stream(cur)
-        with torch.cuda.stream(s1):
-            self.fe.pack_records_dev(self.ctx, p.B, self.rank, self.world, c["kp"], c["desc"], c["n"], p.cap,
-                                     c["kl"] if lines else None, c["ldesc"] if lines else None, c["linefn"] if lines else None, c["nl"] if lines else None, p.lcap,
-                                     self.send[s], self.cap_bytes, self.total[s], p._stream())
-            ev = torch.cuda.Event(); ev.record(s1)
-        cur.wait_stream(s1)
+        s1 = pack_step(self.fe, self.ctx, self.pipe, self.rank, self.world, self.send[s], self.cap_bytes, self.total[s])
+        ev = torch.cuda.Event(); ev.record(s1)      # right behind the pack: nothing else has been enqueued on that stream since
         self.last = s
 
         def run():
@@ -127,16 +133,7 @@ class TorchGather:
         self.wait_s = 0.0; self.waits = 0
 
     def submit(self):
-        p, c = self.pipe, self.pipe.feat["cur"]
-        lines = p.with_lines
-        s1, _ = p._streams()
-        cur = torch.cuda.current_stream(p.dev)
-        s1.wait_stream(cur)
-        with torch.cuda.stream(s1):
-            self.fe.pack_records_dev(self.ctx, p.B, self.rank, self.world, c["kp"], c["desc"], c["n"], p.cap,
-                                     c["kl"] if lines else None, c["ldesc"] if lines else None, c["linefn"] if lines else None, c["nl"] if lines else None, p.lcap,
-                                     self.send, self.cap_bytes, self.total, p._stream())
-        cur.wait_stream(s1)
+        pack_step(self.fe, self.ctx, self.pipe, self.rank, self.world, self.send, self.cap_bytes, self.total)
         n = int(self.total[0].item())
         if n < 0 or n > self.cap_bytes:      # the pack kernel's overflow sentinel is UINT64_MAX, which reads as -1 here: never slice with it
             raise RuntimeError("record stream overflow: the packed results of rank %d do not fit %d bytes" % (self.rank, self.cap_bytes))

@@ -1,10 +1,11 @@
 // A stand-in for <hip/hip_runtime.h> that lets a plain host compiler build the host-side bookkeeping of csrc/common.h (tests/sim/host_checks.cpp):
-// the handful of runtime calls common.h makes, each appending its name and arguments to hip_stub::log.  Device memory is host memory, an event is
+// the handful of runtime calls common.h and the exchange headers make, those of common.h each appending its name and arguments to hip_stub::log.  Device memory is host memory, an event is
 // a small heap block, a stream is whatever pointer the test makes up: AddressSanitizer then sees a leak, a double free or a use after release.
 #pragma once
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -37,3 +38,8 @@ inline hipError_t hipEventDestroy(hipEvent_t e) { hip_stub::note("hipEventDestro
 inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { hip_stub::note("hipEventRecord", e, s); e->recorded = 1; return hipSuccess; }
 inline hipError_t hipEventSynchronize(hipEvent_t e) { hip_stub::note("hipEventSynchronize", e); (void)e->recorded; return hipSuccess; }
 inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { hip_stub::note("hipStreamWaitEvent", s, e); (void)e->recorded; return hipSuccess; }
+// what the rank threads of the exchange check call (csrc/group_exchange.h, csrc/rccl_standin.h): a copy is done when the call returns, so there is nothing to
+// wait for; neither writes the log, which belongs to the main thread
+enum hipMemcpyKind { hipMemcpyHostToHost = 0, hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };
+inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t) { memcpy(dst, src, n); return hipSuccess; }

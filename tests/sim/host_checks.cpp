@@ -1,11 +1,17 @@
-// Host-only checks of two pieces of the matchers' host side, built by tests/test_host_checks_cpu.py with a plain host compiler under
-// -fsanitize=address,undefined (no GPU, no HIP: tests/sim/hip_stub stands in for the runtime):
+// Host-only checks of the library's host side, built by tests/test_host_checks_cpu.py with a plain host compiler under
+// -fsanitize=address,undefined -DSSLAM_TESTING (no GPU, no HIP: tests/sim/hip_stub stands in for the runtime):
 //   check_csr (csrc/match_check.h)        which CSR lists a call accepts, and that a refused list is never read past what its offsets promise
 //   StreamOrderedBuf (csrc/common.h)      which runtime calls acquire / mark / release make, in which order
-// Every array is a heap block of exactly its length, so a read past it ends the run.  Prints one line per check group, "ok" at the end.
+//   gather_to_root (csrc/group_exchange.h) over the RCCL stand-in (csrc/rccl_standin.h), a thread per rank: the lengths' all-gather and the payload
+//                                         exchange of both group forms, for several rank counts, with and without the root's own bytes through the table
+// Every array is a heap block of exactly its length, so a read or write past it ends the run.  Prints one line per check group, "ok" at the end.
 #include "../../structure-slam-pointline_amd/csrc/common.h"
 #include "../../structure-slam-pointline_amd/csrc/match_check.h"
+#include "../../structure-slam-pointline_amd/csrc/group_exchange.h"
+#include "../../structure-slam-pointline_amd/csrc/rccl_standin.h"
 #include <cstdarg>
+#include <memory>
+#include <thread>
 
 static std::string g_err;
 namespace sslam {
@@ -81,8 +87,62 @@ static int check_stream_ordered_buf() {
     return 0;
 }
 
+// what rank r sends in a round: lengths that differ and are no multiple of anything; the last rank of several never has bytes, the root has none in round 2
+static uint64_t exchange_len(int G, int r, int round) { return (G > 1 && r == G - 1) || (r == 0 && round == 2) ? 0 : 13 + 37 * (uint64_t)r + 101 * (uint64_t)round + (r == 1 ? 4099 : 0); }
+
+// one rank's side of three rounds: the two-word all-gather of (length, root's capacity) as sslam_group_gather_dev makes it, then gather_to_root.  Returns the line that failed, 0 when none did.
+static int exchange_rank(Rccl* R, ncclComm_t comm, int G, int r, bool selfRccl) {
+    hipStream_t st = (hipStream_t)(uintptr_t)(0x1000 + r);
+    for (int round = 0; round < 3; ++round) {
+        const uint64_t mine = exchange_len(G, r, round);
+        uint64_t total = 0;
+        for (int q = 0; q < G; ++q) total += exchange_len(G, q, round);
+        std::unique_ptr<uint64_t[]> pair(new uint64_t[2]{mine, r == 0 ? total : 0}), all(new uint64_t[2 * (size_t)G]);
+        if (R->AllGather(pair.get(), all.get(), 2, kNcclUint64, comm, st) != 0) return __LINE__;
+        std::unique_ptr<uint64_t[]> bytes(new uint64_t[G]);
+        for (int q = 0; q < G; ++q) { bytes[q] = all[2 * q]; if (bytes[q] != exchange_len(G, q, round) || all[2 * q + 1] != (q == 0 ? total : 0)) return __LINE__; }
+        std::unique_ptr<uint8_t[]> send(new uint8_t[mine]), recv(r == 0 ? new uint8_t[total] : nullptr);
+        memset(send.get(), r + 1, mine);
+        if (r == 0) memset(recv.get(), 0xEE, total);
+        const GatherStatus x = gather_to_root(R, comm, r, G, bytes.get(), send.get(), recv.get(), selfRccl, st);
+        if (x.rccl != 0 || !x.started || x.hip != hipSuccess) return __LINE__;
+        if (r == 0) {                                   // the streams back to back in rank order (a write past the total ends the run: the block is exactly that long)
+            uint64_t at = 0;
+            for (int q = 0; q < G; ++q) for (uint64_t i = 0; i < bytes[q]; ++i) if (recv[at++] != q + 1) return __LINE__;
+            if (at != total) return __LINE__;
+        }
+    }
+    return 0;
+}
+
+static int check_exchange() {
+    Rccl* R = rccl_fake();
+    for (int G : {1, 2, 3, 5, 8}) for (int selfRccl = 0; selfRccl < 2; ++selfRccl) for (int form = 0; form < 2; ++form) {
+        std::vector<ncclComm_t> comms(G, nullptr);
+        std::vector<int> failed(G, 0);
+        NcclUid id;
+        if (form == 0) CHECK(R->CommInitAll(comms.data(), G, nullptr) == 0);      // one process driving G devices
+        else CHECK(R->GetUniqueId(&id) == 0);                                     // one process per GPU: every rank joins with the shared id, from its own thread
+        std::vector<std::thread> th;
+        for (int r = 0; r < G; ++r) th.emplace_back([&, r] {
+            if (form == 1 && R->CommInitRank(&comms[r], G, id, r) != 0) { failed[r] = __LINE__; return; }
+            failed[r] = exchange_rank(R, comms[r], G, r, selfRccl != 0);
+        });
+        for (auto& t : th) t.join();
+        for (int r = 0; r < G; ++r) {
+            if (failed[r]) printf("exchange: G %d, own bytes through the table %d, form %d: rank %d failed at line %d\n", G, selfRccl, form, r, failed[r]);
+            CHECK(failed[r] == 0);
+        }
+        for (ncclComm_t c : comms) CHECK(R->CommDestroy(c) == 0);
+        CHECK(gFakeWorlds.empty());                                                // (a world that is not freed is a leak, which ends the run as well)
+    }
+    CHECK(gStandinRequested.load() == 0 && tFakeDepth == 0 && tFakeOps.empty());
+    printf("exchange ok\n");
+    return 0;
+}
+
 int main() {
-    if (check_csr_cases() || check_stream_ordered_buf()) return 1;
+    if (check_csr_cases() || check_stream_ordered_buf() || check_exchange()) return 1;
     printf("ok\n");
     return 0;
 }

@@ -61,6 +61,40 @@ def test_pack_unpack_records(fe, ctx):
     pipe.close()
 
 
+def test_pack_records_on_two_streams_without_synchronising(fe, ctx):
+    """Three packs of one context back to back with no synchronisation between them -- 3 frames on stream A, all 9 on stream B (more offsets than A's pack
+    holds, while A's may still run), 3 frames on A again -- each give the bytes the same pack gives alone on the context's stream: the per-frame offsets
+    a pack leaves for its copy kernel are not touched by the next one.  (At these sizes the offsets of 10 frames still fit the slack DevBuf allocates
+    for 4, so nothing is reallocated here; what a growing buffer waits for is pinned by tests/sim/host_checks.cpp.)"""
+    pipeline = pkg._load("sslam_pipeline", os.path.join(pkg.PKG_DIR, "pipeline.py"))
+    B = 9
+    pipe = pipeline.FrontendBatch(fe, ctx, W, H, B, 400, 80, "cuda:0", with_match=False)
+    pipe.step(torch.from_numpy(_frames(B)).cuda())
+    torch.cuda.synchronize()
+    c = pipe.feat["cur"]
+    capb = fe.record_stream_capacity(B, pipe.cap, pipe.lcap)
+
+    def pack(nframes, stream):
+        out = torch.zeros(capb, dtype=torch.uint8, device="cuda"); tot = torch.zeros(1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()                      # the buffers are zeroed before a pack on another stream may write them
+        return out, tot, lambda: fe.pack_records_dev(ctx, nframes, 5, 3, c["kp"], c["desc"], c["n"], pipe.cap, c["kl"], c["ldesc"], c["linefn"], c["nl"], pipe.lcap, out, capb, tot, stream)
+    ref = {}
+    for nframes in (3, B):
+        out, tot, go = pack(nframes, None)
+        go(); ctx.synchronize()
+        ref[nframes] = (int(tot.item()), out.cpu().numpy())
+    assert 0 < ref[3][0] < ref[B][0] <= capb
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    runs = [pack(3, sa.cuda_stream), pack(B, sb.cuda_stream), pack(3, sa.cuda_stream)]
+    for _, _, go in runs:
+        go()
+    torch.cuda.synchronize()
+    for (out, tot, _), nframes in zip(runs, (3, B, 3)):
+        assert int(tot.item()) == ref[nframes][0]
+        np.testing.assert_array_equal(out.cpu().numpy(), ref[nframes][1])
+    pipe.close()
+
+
 @pytest.mark.parametrize("self_rccl", [False, True])
 def test_group_single_process_ngpu1(fe, ctx, self_rccl):
     """sslam_group_create(1) + sslam_frontend_batch_sharded == sslam_frontend_batch, frame by frame; with SSLAM_GROUP_SELF_SENDRECV the root's
