@@ -442,6 +442,13 @@ int sslam_lines_set_nfa_variant(sslam_lines* ln, int variant);
 int sslam_lines_set_lbd_bit_order(sslam_lines* ln, int variant);
 int sslam_lines_set_resize_variant(sslam_lines* ln, int variant);
 int sslam_lines_set_seed_order(sslam_lines* ln, int variant);
+/* Frame sizes of the line extractor: every line entry point (sslam_lines_extract, sslam_lines_extract_batch_dev, the host batches with lines != NULL) returns
+ * SSLAM_ERR_UNSUPPORTED, before any kernel launch (sslam_lines_extract has enqueued the image's upload by then) and with the size in the message, for a frame with a side below 10 pixels (LSD's 0.8x image below 8 x 8) or whose scaled
+ * side exceeds 65 535.  The stencil kernels reflect a coordinate once (BORDER_REFLECT_101 with radius 3), which is exact from 4 pixels a side on; the bound of 10 lies above
+ * that and is the smallest size the suite runs against the oracle (10 x 10, 10 x 40, 40 x 10).  A refused size leaves the handle as it was: its plan, its workspace and the
+ * last batch's status and segments stay those of the previous size.  An image with w == 0 or h == 0 yields zero lines and SSLAM_OK.
+ * A frame whose LSD stage finds more than 8192 candidate rectangles keeps the first 8192 in seed order: sslam_lines_extract returns SSLAM_ERR_UNSUPPORTED for it, a batch
+ * delivers the lines of those rectangles and reports the frame through sslam_lines_batch_status. */
 /* Batch-of-frames mode over the image layout of sslam_orb_extract_batch_dev (d_images + i*image_stride is frame i, row pitch `pitch`; with padded
  * rows the last frame must be readable for pitch * h bytes): d_kl[nframes*cap], d_ldesc[nframes*cap*32], d_linefn[nframes*cap*3], d_counts[nframes].
  * The layout only chooses how the rows are loaded (aligned dwords for a dword-aligned base, pitch and image_stride; bytes otherwise), never a result.

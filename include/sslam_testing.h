@@ -68,6 +68,16 @@ int sslam_lines_debug_cluster(sslam_lines* ln, int frame, long long* out8);
 int sslam_testing_lines_tail(sslam_lines* ln, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, const float* segs, const uint8_t* accept,
                              const int32_t* nsegs, int nmax, int cap, sslam_keyline* kl_out, uint8_t* ldesc_out, double* linefn_out, int32_t* counts_out, float* lbd_dir_out);
 
+/* What the last sslam_lines_extract_batch_dev of the handle (sslam_lines_extract and the host batches call it) chose among its launch forms, so that a test can assert the form
+ * it means to cover instead of inferring it from the sizes: out[0] = the sequential core (0 cluster form with the NFA stage streaming beside it, 1 cluster form with the stage
+ * behind it, 2 one lone wave per frame, 3 the guest form on a persistent grid, 4 one four-wave workgroup per frame, 5 one six-wave workgroup per frame), out[1] = the guest
+ * form's grid (0 otherwise), out[2] = the gradient came from the fused blur + gradient kernel, out[3] = the seeds were sorted by the tile-sorted runs kernels, out[4] = the NFA
+ * stage (0 streaming beside the core, 1 the 18 launches, 2 k_nfa_all), out[5] / out[6] = its evaluating / counting waves per frame (streaming: the consumer waves and 0),
+ * out[7] = k_lbd's template argument.  Every call starts with -1 in all eight, so a word the call did not reach (before the first call; a call that failed early; out[3]
+ * under sslam_lines_set_seed_order(1), where the host sorts) is -1 and never another call's choice.  The handle records these in plain fields where they are decided; nothing on the
+ * product path reads them. */
+int sslam_testing_lines_last_forms(sslam_lines* ln, int32_t out[8]);
+
 /* The ORB tail -- k_octree (DistributeOctTree, src/ORBextractor.cc:539-763) and k_describe (IC_Angle, the 7x7 blur, computeOrbDescriptor and the KeyPoint fill, :77-147,
  * :835-847, :1085-1101) -- on FAST candidates the CALLER supplies in place of k_fast_cells', so that a test can drive the two kernels at their own edges.  `nframes` gray
  * images of one size on the host (row pitch `stride`, `image_stride` bytes from frame to frame), uploaded the way sslam_orb_extract uploads its frame;

@@ -62,7 +62,25 @@ static inline double log_gamma_lanczos(double x) {
 }
 static inline double log_gamma(double x) { return x > 15 ? log_gamma_windschitl(x) : log_gamma_lanczos(x); }
 
+// What a run of Lsd::detect went through (orc_lsd_trace): 64 ints per frame.  Filled by the detector's own functions when Lsd::tr is set; tests/oracle_lib.py LSD_TRACE names
+// the fields in this order.
+struct LsdTrace {
+    int sw = 0, sh = 0, minRegSize = 0, defined = 0, seeds = 0;          // scaled size, min_reg_size, pixels with an angle, seeds grown
+    int regMinM1 = 0, regMin = 0, reg767 = 0, reg768 = 0, reg769 = 0, regMax = 0;      // first-growth regions of min_reg_size - 1 / min_reg_size / 767 / 768 / 769 points, the largest
+    int refines = 0, refinesBig = 0, regrownMax = 0;          // refine() calls that re-grow, those on more than 768 points, the largest re-grown region
+    int reduceIters = 0, reduceItersBig = 0, refineFalse = 0, candidates = 0;      // reduce_region_radius iterations, those entered with more than 768 points; refine() false; regions past refine
+    int improve[6] = {0, 0, 0, 0, 0, 0}, rejected = 0;          // rectangles accepted at the first test / p halving / width / one side / other side / final p stage, and rejected
+    int nfaZero = 0, nfaAll = 0, nfaTerm0Above = 0, nfaTerm0Below = 0, nfaBreak = 0, nfaFull = 0;      // nfa() returns: n == 0 || k == 0, n == k, term == 0 with k > n p / without, tail loop left by break / run to n
+    int rowsOutside = 0, colsOutside = 0;          // rect_nfa: rows skipped outside the image, pixels skipped in columns outside it
+    int touchRow0 = 0, touchRowLast = 0, touchCol0 = 0, touchColLast = 0;          // first-growth regions of at least min_reg_size points on the first / last gradient row / column
+    int segments = 0;
+    int pad[26] = {0};
+};
+static_assert(sizeof(LsdTrace) == 64 * sizeof(int), "LsdTrace is 64 ints");
+
 struct Lsd {
+    LsdTrace* tr = nullptr;               // orc_lsd_trace
+    std::vector<int>* segCand = nullptr;  // per emitted segment, the ordinal of its candidate rectangle (regions past refine, seed order)
     // LSD_REFINE_ADV defaults of createLineSegmentDetector
     const double SCALE = 0.8, SIGMA_SCALE = 0.6, QUANT = 2.0, ANG_TH = 22.5, LOG_EPS = 0, DENSITY_TH = 0.7;
     const int N_BINS = 1024;
@@ -200,6 +218,7 @@ struct Lsd {
         double radSq1 = distSq(xc, yc, rec.x1, rec.y1), radSq2 = distSq(xc, yc, rec.x2, rec.y2);
         double radSq = radSq1 > radSq2 ? radSq1 : radSq2;
         while (density < density_th) {
+            if (tr) { ++tr->reduceIters; if (reg.size() > 768) ++tr->reduceItersBig; }
             radSq *= 0.75 * 0.75;
             for (size_t i = 0; i < reg.size(); ++i) {
                 if (distSq(xc, yc, double(reg[i].x), double(reg[i].y)) > radSq) {
@@ -219,6 +238,7 @@ struct Lsd {
     bool refine(std::vector<RegionPoint>& reg, double reg_angle, double prec, double p, Rect& rec, double density_th) {
         double density = double(reg.size()) / (dist(rec.x1, rec.y1, rec.x2, rec.y2) * rec.width);
         if (density >= density_th) return true;
+        if (tr) { ++tr->refines; if (reg.size() > 768) ++tr->refinesBig; }
         double xc = double(reg[0].x), yc = double(reg[0].y);
         const double ang_c = reg[0].angle;
         double sum = 0, s_sum = 0;
@@ -234,6 +254,7 @@ struct Lsd {
         double tau = 2.0 * std::sqrt((s_sum - 2.0 * mean_angle * sum) / double(n) + mean_angle * mean_angle);
         int sx = reg[0].x, sy = reg[0].y;
         region_grow(sx, sy, reg, reg_angle, tau);
+        if (tr && (int)reg.size() > tr->regrownMax) tr->regrownMax = (int)reg.size();
         if (reg.size() < 2) return false;
         region2rect(reg, reg_angle, prec, p, rec);
         density = double(reg.size()) / (dist(rec.x1, rec.y1, rec.x2, rec.y2) * rec.width);
@@ -242,19 +263,20 @@ struct Lsd {
     }
 
     double nfa(int n, int k, double p) const {
-        if (n == 0 || k == 0) return -LOG_NT;
-        if (n == k) return -LOG_NT - double(n) * std::log10(p);
+        if (n == 0 || k == 0) { if (tr) ++tr->nfaZero; return -LOG_NT; }
+        if (n == k) { if (tr) ++tr->nfaAll; return -LOG_NT - double(n) * std::log10(p); }
         double p_term = p / (1 - p);
         const double first = g_lsdNfaVariant == 1 ? (double(n) + 1) : log_gamma(double(n) + 1);          // decision D11 (see g_lsdNfaVariant)
         double log1term = first - log_gamma(double(k) + 1) - log_gamma(double(n - k) + 1)
                           + double(k) * std::log(p) + double(n - k) * std::log(1.0 - p);
         double term = std::exp(log1term);
         if (double_equal(term, 0)) {
-            if (k > n * p) return -log1term / M_LN10 - LOG_NT;
-            else return -LOG_NT;
+            if (k > n * p) { if (tr) ++tr->nfaTerm0Above; return -log1term / M_LN10 - LOG_NT; }
+            else { if (tr) ++tr->nfaTerm0Below; return -LOG_NT; }
         }
         double bin_tail = term;
         double tolerance = 0.1;
+        bool broke = false;
         for (int i = k + 1; i <= n; ++i) {
             double bin_term = double(n - i + 1) / double(i);
             double mult_term = bin_term * p_term;
@@ -262,9 +284,10 @@ struct Lsd {
             bin_tail += term;
             if (bin_term < 1) {
                 double err = term * ((1 - std::pow(mult_term, double(n - i + 1))) / (1 - mult_term) - 1);
-                if (err < tolerance * std::fabs(-std::log10(bin_tail) - LOG_NT) * bin_tail) break;
+                if (err < tolerance * std::fabs(-std::log10(bin_tail) - LOG_NT) * bin_tail) { broke = true; break; }
             }
         }
+        if (tr) ++(broke ? tr->nfaBreak : tr->nfaFull);
         return -std::log10(bin_tail) - LOG_NT;
     }
 
@@ -309,9 +332,9 @@ struct Lsd {
         double left_x = min_y->x, right_x = min_y->x;
         int min_iter = min_y->y, max_iter = max_y->y;
         for (int y = min_iter; y <= max_iter; ++y) {
-            if (y < 0 || y >= h) continue;          // NB: also skips the edge stepping below (as upstream)
+            if (y < 0 || y >= h) { if (tr) ++tr->rowsOutside; continue; }          // NB: also skips the edge stepping below (as upstream)
             for (int x = int(left_x); x <= int(right_x); ++x) {
-                if (x < 0 || x >= w) continue;
+                if (x < 0 || x >= w) { if (tr) ++tr->colsOutside; continue; }
                 ++total_pts;
                 if (isAligned(x, y, rec.theta, rec.prec)) ++alg_pts;
             }
@@ -325,14 +348,17 @@ struct Lsd {
     double rect_improve(Rect& rec) const {
         double delta = 0.5, delta_2 = delta / 2.0;
         double log_nfa = rect_nfa(rec);
-        if (log_nfa > LOG_EPS) return log_nfa;
+        int stage = 0;          // (LsdTrace::improve)
+        auto leave = [&](double v) { if (tr) { if (v > LOG_EPS) ++tr->improve[stage]; else ++tr->rejected; } return v; };
+        if (log_nfa > LOG_EPS) return leave(log_nfa);
         Rect r = rec;
         for (int n = 0; n < 5; ++n) {
             r.p /= 2; r.prec = r.p * M_PI;
             double v = rect_nfa(r);
             if (v > log_nfa) { log_nfa = v; rec = r; }
         }
-        if (log_nfa > LOG_EPS) return log_nfa;
+        stage = 1;
+        if (log_nfa > LOG_EPS) return leave(log_nfa);
         r = rec;
         for (unsigned n = 0; n < 5; ++n) {
             if ((r.width - delta) >= 0.5) {
@@ -341,7 +367,8 @@ struct Lsd {
                 if (v > log_nfa) { rec = r; log_nfa = v; }
             }
         }
-        if (log_nfa > LOG_EPS) return log_nfa;
+        stage = 2;
+        if (log_nfa > LOG_EPS) return leave(log_nfa);
         r = rec;
         for (unsigned n = 0; n < 5; ++n) {
             if ((r.width - delta) >= 0.5) {
@@ -351,7 +378,8 @@ struct Lsd {
                 if (v > log_nfa) { rec = r; log_nfa = v; }
             }
         }
-        if (log_nfa > LOG_EPS) return log_nfa;
+        stage = 3;
+        if (log_nfa > LOG_EPS) return leave(log_nfa);
         r = rec;
         for (unsigned n = 0; n < 5; ++n) {
             if ((r.width - delta) >= 0.5) {
@@ -361,7 +389,8 @@ struct Lsd {
                 if (v > log_nfa) { rec = r; log_nfa = v; }
             }
         }
-        if (log_nfa > LOG_EPS) return log_nfa;
+        stage = 4;
+        if (log_nfa > LOG_EPS) return leave(log_nfa);
         r = rec;
         for (unsigned n = 0; n < 5; ++n) {
             if ((r.width - delta) >= 0.5) {
@@ -370,7 +399,8 @@ struct Lsd {
                 if (v > log_nfa) { rec = r; log_nfa = v; }
             }
         }
-        return log_nfa;
+        stage = 5;
+        return leave(log_nfa);
     }
 
     // LineSegmentDetectorImpl::flsd
@@ -390,17 +420,39 @@ struct Lsd {
         const size_t min_reg_size = size_t(-LOG_NT / std::log10(p));
         used.assign((size_t)w * h, 0);
         std::vector<RegionPoint> reg;
+        int cand = 0;
+        if (tr) { *tr = LsdTrace(); tr->sw = w; tr->sh = h; tr->minRegSize = (int)min_reg_size; for (double a : angles) if (a != NOTDEF) ++tr->defined; }
+        if (segCand) segCand->clear();
         for (size_t i = 0; i < order.size(); ++i) {
             const int idx = order[i], px = idx % w, py = idx / w;
             if (used[idx] == 0 && angles[idx] != NOTDEF) {
                 double reg_angle;
                 region_grow(px, py, reg, reg_angle, prec);
+                if (tr) {
+                    const int n = (int)reg.size();
+                    ++tr->seeds;
+                    if (n + 1 == (int)min_reg_size) ++tr->regMinM1;
+                    if (n == (int)min_reg_size) ++tr->regMin;
+                    if (n == 767) ++tr->reg767;
+                    if (n == 768) ++tr->reg768;
+                    if (n == 769) ++tr->reg769;
+                    if (n > tr->regMax) tr->regMax = n;
+                    if (reg.size() >= min_reg_size) {
+                        bool r0 = false, r1 = false, c0 = false, c1 = false;
+                        for (const RegionPoint& q : reg) { r0 |= q.y == 0; r1 |= q.y == h - 2; c0 |= q.x == 0; c1 |= q.x == w - 2; }
+                        tr->touchRow0 += r0; tr->touchRowLast += r1; tr->touchCol0 += c0; tr->touchColLast += c1;
+                    }
+                }
                 if (reg.size() < min_reg_size) continue;
                 Rect rec;
                 region2rect(reg, reg_angle, prec, p, rec);
-                if (!refine(reg, reg_angle, prec, p, rec, DENSITY_TH)) continue;
+                if (!refine(reg, reg_angle, prec, p, rec, DENSITY_TH)) { if (tr) ++tr->refineFalse; continue; }
+                const int ordinal = cand++;
+                if (tr) ++tr->candidates;
                 double log_nfa = rect_improve(rec);
                 if (log_nfa <= LOG_EPS) continue;
+                if (tr) ++tr->segments;
+                if (segCand) segCand->push_back(ordinal);
                 rec.x1 += 0.5; rec.y1 += 0.5; rec.x2 += 0.5; rec.y2 += 0.5;
                 rec.x1 /= SCALE; rec.y1 /= SCALE; rec.x2 /= SCALE; rec.y2 /= SCALE; rec.width /= SCALE;
                 lines.push_back({float(rec.x1), float(rec.y1), float(rec.x2), float(rec.y2)});
@@ -461,6 +513,22 @@ extern "C" double orc_lsd_nfa(int w, int h, int n, int k, double p) {
     Lsd lsd; lsd.w = w; lsd.h = h;
     lsd.LOG_NT = 5 * (std::log10(double(w)) + std::log10(double(h))) / 2 + std::log10(11.0);
     return lsd.nfa(n, k, p);
+}
+// Lsd::detect with its trace: trace_out[64] (LsdTrace); seg_out[cap][4] and cand_out[cap] = the emitted segments and, for each, the ordinal of its candidate rectangle
+// (either may be null).  Returns the number of segments.
+extern "C" int orc_lsd_trace(const uint8_t* gray, int w, int h, size_t stride, int32_t* trace_out, float* seg_out, int32_t* cand_out, int cap) {
+    Img8 im(w, h);
+    for (int y = 0; y < h; ++y) std::memcpy(im.row(y), gray + (size_t)y * stride, (size_t)w);
+    Lsd lsd; LsdTrace t; std::vector<int> sc; std::vector<Seg4f> segs;
+    lsd.tr = &t; lsd.segCand = &sc;
+    lsd.detect(im, segs);
+    if (trace_out) std::memcpy(trace_out, &t, sizeof(t));
+    const int n = (int)segs.size();
+    for (int i = 0; i < n && i < cap; ++i) {
+        if (seg_out) { seg_out[4 * i] = segs[i].x1; seg_out[4 * i + 1] = segs[i].y1; seg_out[4 * i + 2] = segs[i].x2; seg_out[4 * i + 3] = segs[i].y2; }
+        if (cand_out) cand_out[i] = sc[i];
+    }
+    return n;
 }
 extern "C" double orc_log_gamma(double x) { return log_gamma(x); }
 extern "C" int orc_sobel3(const uint8_t* src, int w, int h, int16_t* gx, int16_t* gy) {

@@ -22,7 +22,7 @@
 
 namespace sslam { int launch_nfa_stream(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, uint8_t* clArea, size_t clFrameBytes,
                                         size_t stageOff, int nframes, int waves, long long spinTicks, bool besideCore); }      // lines_nfa.hip
-namespace sslam { int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes); }      // lines_nfa.hip
+namespace sslam { int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes, int* form3); }      // lines_nfa.hip
 
 using namespace sslam;
 
@@ -85,6 +85,10 @@ struct sslam_lines {
     int sMin = 0;                   // smallest |g|^2 of a defined pixel (k_grad_smin, with the gradient table)
     bool fusedGeometry = false;     // lines_build_plan: the plan admits k_lsd_grad_fused
     hipStream_t nfaStream = nullptr; hipEvent_t nfaFork = nullptr, nfaJoin = nullptr;      // the NFA stage next to the cluster form of the core (calls of up to 64 frames)
+    // what the last sslam_lines_extract_batch_dev chose, written where it is decided and read by sslam_testing_lines_last_forms alone (include/sslam_testing.h):
+    // CoreForm, the guest form's grid, fused gradient kernel, tile-sorted runs, NFA form (0 stream, 1 the 18 launches, 2 k_nfa_all) with its evaluating and counting waves
+    // per frame, k_lbd's template argument.  Every batch call starts with -1 in all of them.
+    int lastForms[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
 };
 
 static std::vector<int> taps_q8(int n, double sigma) {
@@ -114,13 +118,16 @@ static std::vector<int> taps_340(int n, double sigma) {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The plan is built in a local and assigned on success.  A size that is refused (the checks up to the first upload touch nothing of the handle) leaves the previous plan, its
+// workspace and the last batch's results as they were: the next call at the previous size runs on the plan it was built for.  From the first upload on the handle holds no
+// plan (planW = planH = 0) until the new one is complete, so a failure in between makes the next call build again.
 static int lines_build_plan(sslam_lines* L, int w, int h) {
-    LsdPlan& P = L->plan;
+    LsdPlan P;
     memset(&P, 0, sizeof(P));
     P.w = w; P.h = h;
     const double SCALE = 0.8;
     P.sw = (int)lrint(w * SCALE); P.sh = (int)lrint(h * SCALE);
-    if (P.sw < 8 || P.sh < 8) { set_error("image %dx%d too small for LSD", w, h); return SSLAM_ERR_UNSUPPORTED; }
+    if (P.sw < 8 || P.sh < 8) { set_error("image %dx%d too small for LSD (each side must be at least 10 pixels)", w, h); return SSLAM_ERR_UNSUPPORTED; }
     P.spitch = (P.sw + 63) & ~63;
     P.npx = P.sw * P.sh;
     if (P.sw > 65535 || P.sh > 65535) { set_error("image %dx%d too large", w, h); return SSLAM_ERR_UNSUPPORTED; }
@@ -172,6 +179,7 @@ static int lines_build_plan(sslam_lines* L, int w, int h) {
     P.tabX = 0; if (P.lsdResize) coeffs_linear(w, P.sw); else coeffs(SCALE, w, P.sw);
     P.tabY = (int)tabs.size(); if (P.lsdResize) coeffs_linear(h, P.sh); else coeffs(SCALE, h, P.sh);
     int rc;
+    L->planW = L->planH = 0; L->lastFrames = 0;      // from here on the device tables are the new size's
     if ((rc = L->dTabs.ensure(tabs.size() * sizeof(int)))) return rc;
     SSLAM_HIP(hipMemcpy(L->dTabs.p, tabs.data(), tabs.size() * sizeof(int), hipMemcpyHostToDevice));
     int taps[16] = {0};
@@ -226,6 +234,7 @@ static int lines_build_plan(sslam_lines* L, int w, int h) {
         for (int y = 0; ok && y < P.sh; ++y) ok = tabs[(size_t)P.tabY + 2 * y] == 5 * (y >> 2) + (y & 3);
         L->fusedGeometry = ok;
     }
+    L->plan = P;
     L->planW = w; L->planH = h; L->wsFrames = 0;
     return SSLAM_OK;
 }
@@ -412,6 +421,7 @@ static int lines_prologue(const LinesCall& c) {
     const int* tabX = L->dTabs.as<int>() + P.tabX; const int* tabY = L->dTabs.as<int>() + P.tabY;
     const int mode = (P.lsdResize ? 1 : 0) | (L->seedOrder ? 2 : 0);      // the gradient kernels' template argument
     const bool fused = L->fusedGeometry && GRAD_ROWS == 8 && ((uintptr_t)c.images & 3) == 0 && (c.pitch & 3) == 0 && (c.imageStride & 3) == 0 && c.pitch <= 0x7FFFFFFF;
+    L->lastForms[2] = fused;
     if (fused) {
         static decltype(&k_lsd_grad_fused<0>) const kGradFused[4] = {k_lsd_grad_fused<0>, k_lsd_grad_fused<1>, k_lsd_grad_fused<2>, k_lsd_grad_fused<3>};
         sslam::ProfScope _ps(L->ctx, "k_lsd_grad", st);
@@ -428,6 +438,7 @@ static int lines_prologue(const LinesCall& c) {
     }
     if (L->seedOrder) return lines_host_seed_order(L, c.ws, c.nframes, st);
     const bool runs = P.sw <= (1 << SORT_XY_BITS) && P.sh <= (1 << SORT_XY_BITS);
+    L->lastForms[3] = runs;
     const dim3 sg(sort_grid(P.nTiles, c.nframes));
     { sslam::ProfScope _ps(L->ctx, "k_lsd_hist", st); hipLaunchKernelGGL(runs ? k_lsd_hist_sort : k_lsd_hist, sg, dim3(64), 0, st, c.ws, P, c.nframes); }
     { sslam::ProfScope _ps(L->ctx, "k_lsd_scan", st); hipLaunchKernelGGL(k_lsd_scan, dim3(c.nframes), dim3(1024), 0, st, c.ws, P); }
@@ -474,6 +485,7 @@ static int lines_core_cluster(const LinesCall& c, const LinesKnobs& K, bool stre
     // 5.4 ms; the join in the tail orders it before k_lbd.  Behind the NFA stage instead: 5.43 -> 5.38 ms p50, GPU call I)
     lines_blur_sobel(c, L->nfaStream);
     if ((rc = sslam::launch_nfa_stream(L->ctx, L->nfaStream, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), clFrame, stageOff, nframes, K.nfaStreamWaves, K.nfaSpinTicks, true))) return rc;
+    L->lastForms[4] = 0; L->lastForms[5] = K.nfaStreamWaves; L->lastForms[6] = 0;
     *nfaStageOff = stageOff;
     return SSLAM_OK;
 }
@@ -510,6 +522,7 @@ static void lines_describe(const LinesCall& c, SideJoin& side, sslam_keyline* d_
     side.join();
     {   // the walk's conversion form (lbd.h): images of up to 16 384 pixels a side; the previous form beyond
         const bool rpi = P.w <= 16384 && P.h <= 16384;
+        L->lastForms[7] = rpi;
         sslam::ProfScope _ps(L->ctx, "k_lbd", st);
         hipLaunchKernelGGL(rpi ? k_lbd<true> : k_lbd<false>, dim3(std::min(L->maxLines, cap), nframes), dim3(64), 0, st, c.ws, P, d_kl, d_counts, d_ldesc, cap);
     }
@@ -536,7 +549,7 @@ static int lines_tail(const LinesCall& c, CoreForm form, size_t nfaStageOff, Sid
     if (form == CoreForm::ClusterStream) {      // what the concurrent consumers left (nothing, unless they gave up waiting): the same kernel behind both, everything published, no waiting
         side.join();
         if ((rc = sslam::launch_nfa_stream(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), L->clFrame, nfaStageOff, nframes, 16, 0, false))) return rc;
-    } else if ((rc = sslam::launch_nfa_stage(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), nframes))) return rc;
+    } else if ((rc = sslam::launch_nfa_stage(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), nframes, L->lastForms + 4))) return rc;
     lines_describe(c, side, d_kl, d_ldesc, d_linefn, d_counts, cap);
     return SSLAM_OK;
 }
@@ -582,6 +595,7 @@ extern "C" int sslam_lines_extract_batch_dev(sslam_lines* L, const uint8_t* d_im
     if (nframes > 1 && image_stride < pitch * (size_t)(h - 1) + (size_t)w) { set_error("sslam_lines_extract_batch_dev: the frames overlap (image_stride < pitch * (h - 1) + w)"); return SSLAM_ERR_INVALID; }
     const LinesKnobs K = lines_knobs();
     std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);      // plan, workspace and profile records are shared state
+    for (int& f : L->lastForms) f = -1;      // (sslam_testing_lines_last_forms: nothing of an earlier call; what this call does not reach stays -1)
     SSLAM_HIP(hipSetDevice(L->ctx->device));
     hipStream_t st = stream_ ? (hipStream_t)stream_ : L->ctx->stream;
     int rc;
@@ -593,6 +607,7 @@ extern "C" int sslam_lines_extract_batch_dev(sslam_lines* L, const uint8_t* d_im
     if ((rc = lines_prologue(c))) return rc;
     int grid = 0;
     const CoreForm form = lines_core_form(L, P, nframes, K, &grid);
+    L->lastForms[0] = (int)form; L->lastForms[1] = form == CoreForm::Guest ? grid : 0;
     size_t nfaStageOff = 0;
     if ((rc = lines_core(c, K, form, grid, side, &nfaStageOff))) return rc;
     if ((rc = lines_tail(c, form, nfaStageOff, side, d_kl, d_ldesc, d_linefn, d_counts, cap))) return rc;
@@ -716,6 +731,14 @@ extern "C" int sslam_lines_debug_cluster(sslam_lines* L, int frame, long long* o
     ClCtl c;
     SSLAM_HIP(hipMemcpy(&c, L->dCl.as<uint8_t>() + (size_t)frame * L->clFrame, sizeof(c), hipMemcpyDeviceToHost));
     for (int i = 0; i < 8; ++i) out8[i] = c.stat[i];
+    return SSLAM_OK;
+}
+
+// what the last sslam_lines_extract_batch_dev of the handle chose (sslam_lines::lastForms)
+extern "C" int sslam_testing_lines_last_forms(sslam_lines* L, int32_t* out8) {
+    if (!L || !out8) { set_error("sslam_testing_lines_last_forms: invalid arguments"); return SSLAM_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
+    for (int i = 0; i < 8; ++i) out8[i] = L->lastForms[i];
     return SSLAM_OK;
 }
 

@@ -32,7 +32,8 @@ NfaKnobs nfa_knobs() {
 
 namespace sslam {
 
-int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes) {
+// form3 (unless null): what was chosen -- {1: the 18 launches, 2: k_nfa_all}, evaluating waves per frame, counting waves per frame (sslam_testing_lines_last_forms)
+int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes, int* form3) {
     if (planBytes != sizeof(LsdPlan)) { set_error("launch_nfa_stage: plan layout mismatch between translation units"); return SSLAM_ERR_INVALID; }
     LsdPlan P; memcpy(&P, plan, sizeof(P));
     const NfaKnobs K = nfa_knobs();
@@ -43,6 +44,7 @@ int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* pl
     // to the stage's 0.6 ms; a one-workgroup form with sixteen waves was measured at 6.42 / 7.70 ms p50 / p90 per frame against 6.25 / 7.40 and removed in round 5).
     // What helped instead: 128 counting and 32 evaluating waves per frame (6.09 / 7.16).
     const bool nfaFused = K.fused == 2 || (K.fused != 0 && countWaves == 1 && evalWaves == 1);
+    if (form3) { form3[0] = nfaFused ? 2 : 1; form3[1] = nfaFused ? 1 : evalWaves; form3[2] = nfaFused ? 1 : countWaves; }
     if (nfaFused) {
         sslam::ProfScope _ps(ctx, "k_nfa_all", st);
         hipLaunchKernelGGL(k_nfa_all<768>, dim3(nframes), dim3(64), 0, st, ws, P, lgam);

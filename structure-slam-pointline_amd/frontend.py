@@ -673,6 +673,26 @@ class LineExtractor:
         _chk(lib().sslam_lines_debug_segments(self.h, frame, _p(out), cap, C.byref(n)))
         return out[:n.value].copy()
 
+    CORE_FORMS = ("cluster_stream", "cluster", "lone", "guest", "per_frame", "six_wave")
+    NFA_FORMS = ("stream", "launches", "all")
+
+    def last_forms(self):
+        """sslam_testing_lines_last_forms (include/sslam_testing.h): what the last batch call of this handle chose -> dict(core, grid, fused_grad, sort_runs, nfa, eval_waves,
+        count_waves, lbd_rpi).  The testing library reads the handle's plain fields, whichever of the two libraries made it."""
+        o = (C.c_int32 * 8)()
+        rc = testing_lib().sslam_testing_lines_last_forms(self.h, o)
+        if rc != 0:
+            raise SslamError("sslam_testing_lines_last_forms: %d" % rc, rc)
+        flag = lambda v: bool(v) if v >= 0 else None          # -1: the call did not get there
+        return dict(core=self.CORE_FORMS[o[0]] if o[0] >= 0 else None, grid=o[1], fused_grad=flag(o[2]), sort_runs=flag(o[3]),
+                    nfa=self.NFA_FORMS[o[4]] if o[4] >= 0 else None, eval_waves=o[5], count_waves=o[6], lbd_rpi=o[7])
+
+    def batch_status(self, cap, stream=None):
+        """sslam_lines_batch_status -> (status code, frames over capacity, frames over the LSD limit, first such frame or -1)"""
+        t, u, f = C.c_int(-9), C.c_int(-9), C.c_int(-9)
+        rc = lib().sslam_lines_batch_status(self.h, int(cap), C.c_void_p(stream or 0), C.byref(t), C.byref(u), C.byref(f))
+        return rc, t.value, u.value, f.value
+
     def close(self):
         if self.h:
             lib().sslam_lines_destroy(self.h)

@@ -321,6 +321,13 @@ KL_DTYPE = np.dtype([("angle", "<f4"), ("class_id", "<i4"), ("octave", "<i4"),
                      ("lineLength", "<f4"), ("numOfPixels", "<i4")])
 
 
+# oracle/lsd_oracle.cpp LsdTrace: what a run of the LSD detector went through, 64 ints per frame
+LSD_TRACE = ("sw", "sh", "min_reg_size", "defined", "seeds", "reg_min_m1", "reg_min", "reg767", "reg768", "reg769", "reg_max", "refines", "refines_big", "regrown_max",
+             "reduce_iters", "reduce_iters_big", "refine_false", "candidates", "improve0", "improve1", "improve2", "improve3", "improve4", "improve5", "rejected",
+             "nfa_zero", "nfa_all", "nfa_term0_above", "nfa_term0_below", "nfa_break", "nfa_full", "rows_outside", "cols_outside",
+             "touch_row0", "touch_row_last", "touch_col0", "touch_col_last", "segments")
+
+
 def _orc_line_methods():
     def lines_extract(self, gray, max_lines=40, want_float=False):
         gray = np.ascontiguousarray(gray, np.uint8)
@@ -367,7 +374,18 @@ def _orc_line_methods():
         self.L.orc_lbd_from_keylines(_p(gray), w, h, gray.strides[0], _p(kl), n, _p(ld), _p(fd))
         return (ld, fd) if want_float else ld
 
-    for f in (lines_extract, lsd_scaled, lines_tail, lbd_from_keylines):
+    def lsd_trace(self, gray):
+        """Lsd::detect with its trace (oracle/lsd_oracle.cpp LsdTrace) -> (dict of LSD_TRACE, segments n x 4, the candidate ordinal of every segment)"""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        h, w = gray.shape
+        cap = 20000
+        tr = np.zeros(64, np.int32); seg = np.zeros((cap, 4), np.float32); cand = np.zeros(cap, np.int32)
+        self.L.orc_lsd_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        n = self.L.orc_lsd_trace(_p(gray), w, h, gray.strides[0], _p(tr), _p(seg), _p(cand), cap)
+        assert 0 <= n <= cap
+        return {k: int(v) for k, v in zip(LSD_TRACE, tr)}, seg[:n].copy(), cand[:n].copy()
+
+    for f in (lines_extract, lsd_scaled, lines_tail, lbd_from_keylines, lsd_trace):
         setattr(Oracle, f.__name__, f)
 
 

@@ -121,8 +121,9 @@ def test_batch_of_19_distinct_frames(fe, ctx, oracle):
 
 @pytest.mark.parametrize("form", ["one_stream", "guest"])
 def test_batch_of_2176_frames_throughput_kernels(fe, ctx, oracle, form, monkeypatch):
-    """from 1024 frames on the LSD core runs its six-waves-per-SIMD flavour (k_lsd_regions<false, 6>) and the NFA stages one wave per frame
-    (from 2048 on also the rectangle counter): the kernels the benchmark times.  2176 = 17 * 128 small frames, 17 distinct ones tiled, so
+    """from 1024 frames on the LSD core runs one workgroup per frame -- here, with 2 176 frames (at most 16 per compute unit), the four-wave instantiation
+    k_lsd_regions<false, 4> (the six-wave one takes larger calls: tests/test_lsd_forms_gpu.py) -- and the NFA stage one wave per frame (from 2048 on also the
+    rectangle counter: k_nfa_all); both asserted through the testing library's form tap.  2176 = 17 * 128 small frames, 17 distinct ones tiled, so
     every distinct frame lands on many different workgroups / XCDs; a sample of slots is compared with the oracle and all copies of a
     frame must agree with each other byte for byte.
     form "guest" (round 6): the two-stream step with a core event announced and a persistent grid of 136 workgroups (SSLAM_LSD_PERSIST; the library's own grid, 16 per
@@ -140,6 +141,9 @@ def test_batch_of_2176_frames_throughput_kernels(fe, ctx, oracle, form, monkeypa
     else:
         pipe.step(imgs)
     torch.cuda.synchronize()
+    forms = pipe.lines.last_forms()
+    assert (forms["core"], forms["grid"]) == (("guest", 136) if form == "guest" else ("per_frame", 0)), forms
+    assert (forms["nfa"], forms["fused_grad"]) == ("all", form == "guest"), forms
     c = pipe.feat["cur"]
     n = c["n"].cpu().numpy(); nl = c["nl"].cpu().numpy()
     kp = c["kp"].cpu().numpy(); desc = c["desc"].cpu().numpy(); kl = c["kl"].cpu().numpy(); ld = c["ldesc"].cpu().numpy(); fn = c["linefn"].cpu().numpy()

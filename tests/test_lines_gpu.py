@@ -18,10 +18,12 @@ def _ulp_diff(a, b):
     return np.abs(ai - bi)
 
 
-def _cmp_lines(fe, ctx, oracle, img, max_lines):
+def _cmp_lines(fe, ctx, oracle, img, max_lines, core=None):
+    """core: the form of the sequential core the call must have taken (LineExtractor.last_forms)"""
     ex = fe.LineExtractor(ctx, max_lines)
     try:
         kl, ld, fn = ex(img)
+        if core is not None: assert ex.last_forms()["core"] == core, ex.last_forms()
         okl, old, ofn, oraw = oracle.lines_extract(img, max_lines)
         raw = ex.debug_segments(0)
         assert raw.shape == oraw.shape, (raw.shape, oraw.shape)
@@ -134,9 +136,10 @@ def test_line_prologue_forms(fe, ctx, oracle):
 
 @pytest.mark.parametrize("flavour", ["cl", "lat", "thr"])
 def test_lsd_core_flavours(fe, ctx, oracle, flavour, monkeypatch):
-    """The sequential core has three launch forms (lsd_regions.h, lsd_cluster.h): cluster (main wave + helper waves on several compute units,
-    results through global memory, monotonic pixel map: what calls of up to 64 frames get), the lone wave and the six-waves-per-SIMD throughput form.
-    Each is forced here over frames that stress the helper protocol in different ways: long lines (helpers give up beyond their reach), 1280x960 (the cluster
+    """Three of the sequential core's launch forms (lsd_regions.h, lsd_cluster.h): cluster (main wave + helper waves on several compute units,
+    results through global memory, monotonic pixel map: what calls of up to 64 frames get), the lone wave (k_lsd_regions<true, 4>) and, under "thr", one
+    four-wave workgroup per frame (k_lsd_regions<false, 4>: a single frame does not reach the six-wave instantiation, which takes calls of more than 16 frames
+    per compute unit -- tests/test_lsd_forms_gpu.py).  Each is forced here, and asserted through the testing library's form tap, over frames that stress the helper protocol in different ways: long lines (helpers give up beyond their reach), 1280x960 (the cluster
     form's main wave keeps its private bitmap in global memory), noise (hundreds of one-pixel regions per chunk: result slots run out), a
     ramp (regions beyond every helper limit) and an odd size."""
     import ctypes as C
@@ -145,7 +148,7 @@ def test_lsd_core_flavours(fe, ctx, oracle, flavour, monkeypatch):
               (noise_frame(3, w=320, h=240), 200), (ramp_frame(), 200)]
     taken = 0
     for img, cap in frames:
-        _cmp_lines(fe, ctx, oracle, img, cap)
+        _cmp_lines(fe, ctx, oracle, img, cap, core={"cl": "cluster_stream", "lat": "lone", "thr": "per_frame"}[flavour])
         if flavour == "cl":
             ex = fe.LineExtractor(ctx, cap); ex(img)
             out = (C.c_longlong * 8)(); fe.lib().sslam_lines_debug_cycles(ex.h, 0, out); ex.close()
