@@ -289,6 +289,45 @@ int sslam_orb_search_for_triangulation(sslam_ctx* ctx, const sslam_frame* kf1, c
                                        const float F12[9], float ex, float ey, const float* scale_factors2, const float* level_sigma2_2, int nlevels,
                                        int only_stereo, int check_orientation, int32_t* matches12_out, int* nmatches_out);
 
+/* The same matcher (src/ORBmatcher.cc:660-826) for `npairs` pairs of device-resident keyframes, asynchronously, from per-feature node ids instead of
+ * CSR lists: the point half of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:367-640, the call at :440) for callers that keep many sessions'
+ * keyframes on the device.  Both sides of a pair are keyframes of the same maps, so there is ONE pool: keyframe slot k owns rows
+ * [k*cap, k*cap + d_n[k]) of d_kp (mvKeysUn; sslam_undistort_keypoints_batch_dev), d_desc (32 bytes per row; sslam_orb_extract_batch_dev), d_node
+ * (what sslam_bow_transform_batch_dev writes to d_node; a row with an id below 0 is in no node) and, where given, d_free (= !GetMapPoint(i)) and
+ * d_uright (mvuRight).  A NULL d_free means every row is free; a NULL d_uright means monocular, so with only_stereo nothing matches.  A count below
+ * 0 is read as 0, one above cap as cap; node ids, free flags and right coordinates at or past a count are never read.
+ * Pair p = d_pairs[p]: kf1 is pKF1 (the queries), kf2 is pKF2 (the candidates), F12 row-major and (ex, ey) the epipole in image 2 as in the single
+ * call.  scale_factors / level_sigma2 are HOST arrays of nlevels floats, 1 <= nlevels <= 64, shared by all pairs (pKF2's mvScaleFactors /
+ * mvLevelSigma2: one extractor); they are read before the call returns, no other host memory is read and none is written.  An octave outside
+ * [0, nlevels) is clamped into it, as in the single call.
+ * Pair p yields exactly what sslam_orb_search_for_triangulation returns for the two FeatureVectors FeatureVector::addFeature(node[i], i) builds in
+ * feature order from the two node arrays: d_matches12[p*cap + i1], i1 < n[kf1], = the matched keyframe-2 row or -1, after the rotation pruning;
+ * rows at or past the count are not touched.  d_nmatches[p] = the count after the pruning.  A pair with a slot outside [0, nkeyframes) is skipped:
+ * d_nmatches[p] = 0 and nothing else of the pair is written.  kf1 == kf2 is legal and computed like any other pair.
+ * THE LIMIT: CreateNewMapPoints adds every newly triangulated point to the current keyframe INSIDE its neighbour loop (src/LocalMapping.cc:624), so
+ * in the reference the free flags of keyframe 1 for neighbour j + 1 depend on the geometry of neighbour j; with the rotation check on a caller cannot
+ * repair that afterwards by dropping matches, because the dropped matches took part in the histogram.  The exact use is therefore one pair per
+ * session per round: round r matches every session's new keyframe against its r-th neighbour, and the caller updates its d_free rows between
+ * rounds.  Naming one keyframe slot in many pairs of one call is allowed and well defined -- every such pair sees the same free flags -- but it is
+ * NOT the reference's sequential loop.
+ * Every pointer but the two level tables is a device pointer; d_desc is 16-byte aligned, the 4-byte typed buffers 4-byte aligned.  One launch on
+ * `stream` (NULL: the context's stream), no scratch, no synchronise; calls on any streams of one context are independent of each other and of the
+ * synchronous matchers.  SSLAM_ERR_INVALID (nothing enqueued): a NULL ctx, d_kp, d_desc, d_node, d_n, d_pairs, d_matches12, d_nmatches,
+ * scale_factors or level_sigma2, a misaligned buffer, a negative cap, nkeyframes or npairs, cap >= 2^19, nlevels outside 1..64,
+ * npairs * cap >= 2^31.  npairs == 0 is SSLAM_OK and enqueues nothing. */
+typedef struct sslam_tri_pair {
+    int32_t kf1, kf2;     /* keyframe slots: pKF1 (the queries), pKF2 (the candidates) */
+    float   F12[9];       /* row-major, as in the single call */
+    float   ex, ey;       /* epipole in image 2 (src/ORBmatcher.cc:667-673) */
+} sslam_tri_pair;         /* 52 bytes, no padding */
+int sslam_orb_search_for_triangulation_batch_dev(sslam_ctx* ctx,
+                                                 const sslam_keypoint* d_kp, const uint8_t* d_desc, const int32_t* d_node,
+                                                 const uint8_t* d_free, const float* d_uright, const int32_t* d_n, int cap, int nkeyframes,
+                                                 const sslam_tri_pair* d_pairs, int npairs,
+                                                 const float* scale_factors, const float* level_sigma2, int nlevels,
+                                                 int only_stereo, int check_orientation,
+                                                 int32_t* d_matches12, int32_t* d_nmatches, void* stream);
+
 /* ---- DBoW2 vocabulary descent: Frame::ComputeBoW, src/Frame.cc:474-481 ->
  * ORBVocabulary::transform(vCurrentDesc, mBowVec, mFeatVec, 4), whose per-feature work is
  * TemplatedVocabulary::transform(feature, word_id, weight, nid, levelsup), Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1216-1259.

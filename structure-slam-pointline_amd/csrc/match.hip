@@ -698,6 +698,47 @@ extern "C" int sslam_orb_search_for_triangulation(sslam_ctx* ctx, const sslam_fr
     return SSLAM_OK;
 }
 
+// ---- SearchForTriangulation for pairs of keyframe slots that are already on the device, from per-feature node ids (sslam_bow_transform_batch_dev), asynchronous
+extern "C" int sslam_orb_search_for_triangulation_batch_dev(sslam_ctx* ctx,
+        const sslam_keypoint* d_kp, const uint8_t* d_desc, const int32_t* d_node,
+        const uint8_t* d_free, const float* d_uright, const int32_t* d_n, int cap, int nkeyframes,
+        const sslam_tri_pair* d_pairs, int npairs,
+        const float* scale_factors, const float* level_sigma2, int nlevels,
+        int only_stereo, int check_orientation,
+        int32_t* d_matches12, int32_t* d_nmatches, void* stream) {
+    const uintptr_t align4 = (uintptr_t)d_kp | (uintptr_t)d_node | (uintptr_t)d_uright | (uintptr_t)d_n | (uintptr_t)d_pairs | (uintptr_t)d_matches12 | (uintptr_t)d_nmatches;
+    if (!ctx || !d_kp || !d_desc || !d_node || !d_n || !d_pairs || !d_matches12 || !d_nmatches || !scale_factors || !level_sigma2 ||
+        cap < 0 || cap >= (1 << 19) || nkeyframes < 0 || npairs < 0 || nlevels < 1 || nlevels > 64 || (long long)npairs * (long long)cap >= (1ll << 31) ||
+        (align4 & 3) || ((uintptr_t)d_desc & 15)) {      // descriptor rows are read as two 16-byte words
+        set_error("sslam_orb_search_for_triangulation_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (npairs == 0) return SSLAM_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    SSLAM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    const TriBatchPlan P = tri_batch_plan(cap, npairs);      // match_plan.h: keyframe 2 in LDS or in global memory, by the row capacity alone
+    TriBatchArgs A;
+    A.kp = d_kp; A.desc = d_desc; A.node = d_node; A.isFree = d_free; A.uright = d_uright; A.n = d_n; A.cap = cap; A.nkeyframes = nkeyframes;
+    A.pairs = d_pairs; A.nlevels = nlevels; A.onlyStereo = only_stereo; A.checkOri = check_orientation; A.m12 = d_matches12; A.nmatches = d_nmatches;
+    for (int i = 0; i < 64; ++i) { A.scale2[i] = i < nlevels ? scale_factors[i] : 0.f; A.sigma2_2[i] = i < nlevels ? level_sigma2[i] : 0.f; }
+    switch (P.form) {
+    case TriBatchForm::Lds: {
+        int rc;
+        if ((rc = allow_dynamic_lds((const void*)k_tri_search_batch<true>, P.ldsBytes))) return rc;
+        sslam::ProfScope _ps(ctx, "k_tri_search_batch", st);
+        hipLaunchKernelGGL(k_tri_search_batch<true>, dim3(P.grid), dim3(P.threads), P.ldsBytes, st, A);
+        break;
+    }
+    case TriBatchForm::Global: {
+        sslam::ProfScope _ps(ctx, "k_tri_search_batch", st);
+        hipLaunchKernelGGL(k_tri_search_batch<false>, dim3(P.grid), dim3(P.threads), 0, st, A);
+        break;
+    }
+    }
+    SSLAM_HIP(hipGetLastError());
+    return SSLAM_OK;
+}
+
 // ---- DBoW2 vocabulary
 extern "C" int sslam_vocab_create(sslam_ctx* ctx, int nnodes, int levels, const int32_t* child_ptr, const int32_t* children, const uint8_t* node_desc,
                                   const int32_t* word_id, const double* weight, sslam_vocab** out) {

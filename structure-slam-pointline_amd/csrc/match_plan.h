@@ -182,6 +182,36 @@ inline BowBatchPlan bow_batch_plan(int cap, int npairs) {
     return P;
 }
 
+// -------------------------------------------------------------- SearchForTriangulation of a batch (sslam_orb_search_for_triangulation_batch_dev)
+// One workgroup of TRI_BATCH_WAVES waves per pair of keyframe slots -- k_tri_search_batch; the waves share the keyframe-1 rows in turns of 64 (the
+// queries do not interact).  The form follows the row capacity alone (every pair of a launch runs the same kernel):
+//   Lds     keyframe 2 of the pair sits in the workgroup's LDS: 32 bytes of descriptor, the node id, x, y and octave | free | stereo in one word per
+//           row, TRI_BATCH_ROW_BYTES * cap bytes in all, while that is at most TRI_BATCH_LDS_MAX (64 KB, the SearchByBoW batch's bound: two pairs per
+//           compute unit at the bound, three at 1000 rows); more than DYNAMIC_LDS_DEFAULT_MAX needs the per-kernel opt-in
+//   Global  beyond that: the same kernel scans the caller's buffers
+// No scratch: a pair's state is in its workgroup's LDS, its registers and the pair's own output rows.
+constexpr int TRI_BATCH_WAVES = 8;
+constexpr int TRI_BATCH_ROW_BYTES = 48;
+constexpr size_t TRI_BATCH_LDS_MAX = 64 * 1024;
+enum class TriBatchForm { Lds, Global };
+struct TriBatchPlan {
+    TriBatchForm form;
+    size_t ldsBytes;          // dynamic LDS per workgroup (0: Global)
+    int ldsOptIn;             // ldsBytes is more than a launch may ask for without hipFuncSetAttribute
+    unsigned threads;         // workgroup size
+    unsigned grid;            // workgroups: one per pair
+};
+inline TriBatchPlan tri_batch_plan(int cap, int npairs) {
+    TriBatchPlan P{};
+    const size_t lds = (size_t)TRI_BATCH_ROW_BYTES * (size_t)cap;
+    P.form = lds <= TRI_BATCH_LDS_MAX ? TriBatchForm::Lds : TriBatchForm::Global;
+    P.ldsBytes = P.form == TriBatchForm::Lds ? lds : 0;
+    P.ldsOptIn = P.ldsBytes > DYNAMIC_LDS_DEFAULT_MAX ? 1 : 0;
+    P.threads = 64u * TRI_BATCH_WAVES;
+    P.grid = (unsigned)npairs;
+    return P;
+}
+
 // arena of search_proj_core.  occ | q | qdesc go up in ONE copy (occ .. assigned), assigned | count come back in one (assigned .. count + 4);
 // only that head (.. count + 256) has a pinned mirror.  projK = list length of k_proj_topk (PROJ_K).
 struct ProjArena {

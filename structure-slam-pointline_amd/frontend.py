@@ -24,6 +24,9 @@ PQ_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("u2", "<f4"), ("v2", "<f4"), (
                      ("angle", "<f4"), ("ur", "<f4"), ("valid", "<i4"), ("obs_positive", "<i4")])
 assert PQ_DTYPE.itemsize == 44
 
+TRI_PAIR_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("F12", "<f4", (9,)), ("ex", "<f4"), ("ey", "<f4")])      # sslam_tri_pair
+assert TRI_PAIR_DTYPE.itemsize == 52
+
 _lib = None
 
 PIX_GRAY, PIX_RGB, PIX_BGR, PIX_RGBA, PIX_BGRA = 0, 1, 2, 3, 4      # SSLAM_PIX_* (include/sslam_frontend.h)
@@ -208,6 +211,21 @@ class Context:
                                                      _p(d_f_kp), _p(d_f_desc), _p(d_f_node), _p(d_nf), int(cap), int(nframes), _p(d_pair_kf), _p(d_pair_f),
                                                      int(npairs), C.c_float(nnratio), int(bool(check_orientation)), _p(d_assigned), _p(d_nmatches),
                                                      C.c_void_p(stream or 0)))
+
+    def search_for_triangulation_batch_dev(self, d_kp, d_desc, d_node, d_n, cap, nkeyframes, d_pairs, npairs, scale_factors, level_sigma2,
+                                           d_matches12, d_nmatches, d_free=None, d_uright=None, only_stereo=False, check_orientation=True, nlevels=None,
+                                           stream=None):
+        """sslam_orb_search_for_triangulation_batch_dev on device tensors / pointers: pair p = d_pairs[p] (TRI_PAIR_DTYPE rows on the device) matches
+        keyframe slot kf1 (the queries) against slot kf2 of the one pool d_kp / d_desc / d_node / d_n [/ d_free / d_uright] from the per-feature node
+        ids of bow_transform_batch_dev; scale_factors / level_sigma2 are HOST arrays (nlevels: their length unless given); d_matches12 [npairs, cap]
+        int32, d_nmatches [npairs] int32; enqueues on `stream` (None: the context's) and returns without synchronising"""
+        sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, np.float32)
+        sg = None if level_sigma2 is None else np.ascontiguousarray(level_sigma2, np.float32)
+        if nlevels is None: nlevels = 0 if sf is None else len(sf)
+        _chk(lib().sslam_orb_search_for_triangulation_batch_dev(self.h, _p(d_kp), _p(d_desc), _p(d_node), _p(d_free), _p(d_uright), _p(d_n), int(cap),
+                                                                int(nkeyframes), _p(d_pairs), int(npairs), _p(sf), _p(sg), int(nlevels),
+                                                                int(bool(only_stereo)), int(bool(check_orientation)), _p(d_matches12), _p(d_nmatches),
+                                                                C.c_void_p(stream or 0)))
 
     def search_by_bow_keyframes(self, kp1, d1, valid1, kp2, d2, valid2, ptr1, ptr2, idx1, idx2, nnratio=0.8, check_orientation=True):
         """ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (src/ORBmatcher.cc:525-658): -> (matches12, nmatches)"""

@@ -1,0 +1,78 @@
+"""The host-side plan of sslam_orb_search_for_triangulation_batch_dev (csrc/match_plan.h: tri_batch_plan).  The header holds no HIP:
+tests/sim/tri_batch_plan_dump.cpp compiles it with plain g++, once as it is and once with -fsanitize=address,undefined, as a stand-alone program;
+nothing is loaded into Python.  Every expected value is worked out here from the documented rule, never read back from the header:
+
+  workgroup   one per pair, 8 waves of 64 lanes (the waves share the keyframe-1 rows in turns of 64)
+  form        keyframe 2 of a pair in LDS -- 32 bytes of descriptor, 4 of node id, 4 + 4 of x and y, 4 of octave | free | stereo per row of the
+              capacity -- while 48 * cap <= 64 KB; beyond that the same kernel on global memory, with no dynamic LDS
+  opt-in      more than 48 KB of dynamic LDS needs the per-kernel opt-in"""
+import os, subprocess
+import pytest
+import tri_batch_cases as tc
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+WAVES, ROW, LDS_MAX, LDS_DEFAULT, LDS_CU = 8, 48, 64 * 1024, 48 * 1024, 160 * 1024
+
+
+@pytest.fixture(scope="module")
+def ask(tmp_path_factory):
+    """ask(lines) -> one list of tokens per line; the plain and the sanitised build must answer alike, and the sanitised one must end clean"""
+    d = tmp_path_factory.mktemp("tri_batch_plan")
+    src = os.path.join(HERE, "sim", "tri_batch_plan_dump.cpp")
+    plain, san = str(d / "tri_batch_plan_dump"), str(d / "tri_batch_plan_dump_san")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", src, "-o", plain])
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", san])
+
+    def run(lines):
+        text = "\n".join(lines) + "\n"
+        outs = []
+        for exe in (plain, san):
+            r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
+            assert r.returncode == 0 and r.stderr == "", (exe, r.returncode, r.stderr)
+            outs.append(r.stdout)
+        assert outs[0] == outs[1]
+        rows = [l.split() for l in outs[0].splitlines()]
+        assert len(rows) == len(lines)
+        return rows
+    return run
+
+
+def expect_plan(cap, npairs):
+    lds = ROW * cap
+    if lds <= LDS_MAX:
+        return ["lds", str(lds), str(int(lds > LDS_DEFAULT)), str(64 * WAVES), str(npairs)]
+    return ["global", "0", "0", str(64 * WAVES), str(npairs)]
+
+
+def test_constants(ask):
+    assert ask(["consts"]) == [[str(WAVES), str(ROW), str(LDS_MAX), str(LDS_DEFAULT)]]
+    assert (tc.W, tc.ROW_BYTES, tc.LDS_MAX, tc.LDS_DEFAULT) == (WAVES, ROW, LDS_MAX, LDS_DEFAULT)          # what the case module and the GPU test assume
+    assert ROW == 32 + 4 + 4 + 4 + 4
+
+
+LAST_LDS = LDS_MAX // ROW                 # 1365
+LAST_PLAIN = LDS_DEFAULT // ROW           # 1024: the last capacity without the opt-in
+CASES = [(0, 1), (1, 1), (64, 5), (1000, 64), (1000, 12288), (LAST_PLAIN, 3), (LAST_PLAIN + 1, 3), (LAST_LDS, 2), (LAST_LDS + 1, 2), (2000, 7), (8192, 1),
+         ((1 << 19) - 1, 4), (1000, (1 << 31) // 1000), (1000, 0)]
+
+
+def test_plan_on_both_sides_of_every_boundary(ask):
+    assert (LAST_LDS, LAST_PLAIN) == (1365, 1024) == (tc.LDS_CAP, tc.PLAIN_CAP)
+    assert ROW * LAST_LDS <= LDS_MAX < ROW * (LAST_LDS + 1) and ROW * LAST_PLAIN <= LDS_DEFAULT < ROW * (LAST_PLAIN + 1)
+    got = dict(zip(CASES, ask(["plan %d %d" % c for c in CASES])))
+    for c in CASES:
+        assert got[c] == expect_plan(*c), (c, got[c])
+    assert got[(LAST_LDS, 2)][:2] == ["lds", str(ROW * LAST_LDS)] and got[(LAST_LDS + 1, 2)][:2] == ["global", "0"]
+    assert got[(LAST_PLAIN, 3)][2] == "0" and got[(LAST_PLAIN + 1, 3)][2] == "1" and got[(LAST_LDS, 2)][2] == "1" and got[(LAST_LDS + 1, 2)][2] == "0"
+    assert got[(1000, 64)][1] == "48000" and got[(1000, 12288)][4] == "12288"        # a 1000-keypoint keyframe: 48 KB, three pairs per compute unit
+    # the form follows the capacity alone, the grid the number of pairs alone
+    assert got[(1000, 64)][:4] == got[(1000, 12288)][:4] == got[(1000, (1 << 31) // 1000)][:4]
+
+
+def test_lds_fits_a_compute_unit(ask):
+    caps = [0, 1, 63, 64, 65, 1000, LAST_PLAIN, LAST_PLAIN + 1, LAST_LDS, LAST_LDS + 1, 5000, (1 << 19) - 1]
+    for c, row in zip(caps, ask(["plan %d 9" % c for c in caps])):
+        lds, opt_in = int(row[1]), int(row[2])
+        assert lds <= LDS_MAX and 2 * (lds + 1024) <= LDS_CU          # two pairs per compute unit beside the kernel's static arrays (level tables, histogram, kept bins, count)
+        assert opt_in == int(lds > LDS_DEFAULT)
+        assert int(row[3]) == 512 <= 1024 and row[4] == "9"
