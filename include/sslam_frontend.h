@@ -278,6 +278,47 @@ int sslam_hamming_knn2_frames(sslam_ctx* ctx, const sslam_frame* query, const ss
 int sslam_fuse_search(sslam_ctx* ctx, const sslam_frame* keyframe, int chi2_mode, const float* inv_level_sigma2, int nlevels,
                       const sslam_proj_query* queries, const uint8_t* qdesc, int nq, int32_t* best_idx_out, int32_t* best_dist_out);
 
+/* The same candidate search for `njobs` jobs on device-resident keyframes, asynchronously: the fusion step of LocalMapping::SearchInNeighbors
+ * (src/LocalMapping.cc:1178-1284, the calls at :1206, :1226, :1243, :1264) and the two directions of SearchBySim3 for callers that keep many sessions'
+ * keyframes on the device.  The pool is sslam_orb_search_for_triangulation_batch_dev's: keyframe slot k owns rows [k*cap, k*cap + d_n[k]) of d_feats
+ * (kind 0: sslam_keypoint, kind 1: sslam_keyline), of d_desc (32 bytes per row) and, where given, of d_uright.  A count below 0 is read as 0, one
+ * above cap as cap; nothing at or past a count is read.  A NULL d_uright means monocular, as in the single call on a handle without right coordinates.
+ * Job j = d_jobs[j] searches keyframe slot kf with nq queries (clamped to [0, qcap]): it owns rows [j*qcap, j*qcap + nq) of d_queries, d_best_idx and
+ * d_best_dist, and its query i reads descriptor row qdesc0 + i of d_qdesc (nqdesc rows in all).  Several jobs may name one qdesc0 -- the current
+ * keyframe's map points projected into 20 neighbours are 20 jobs on ONE descriptor block, each with its own windows -- and several jobs one slot.
+ * For i < nq, d_best_idx[j*qcap + i] / d_best_dist[j*qcap + i] receive exactly what sslam_fuse_search returns for that query on that keyframe with the
+ * same kind, chi2_mode, bounds and level table: ties go to the first in GetFeaturesInArea / GetLinesInArea order, -1 / INT_MAX for a query with
+ * valid == 0 or without an admissible feature, the 5.99 / 7.8 gates under chi2_mode 1, an octave outside [0, nlevels) gated with a weight of 0.
+ * Rows at or past nq are not touched.  d_nfound[j] = the number of the job's queries with a candidate.  A job whose kf is outside [0, nkeyframes),
+ * whose qdesc0 is below 0 or whose qdesc0 + nq (after the clamp) is above nqdesc is skipped: d_nfound[j] = -1 and nothing else of it is written.
+ * WHY ONE CALL IS EXACT: the candidate search of a query depends on nothing another query did.  The reference's inner loop (src/ORBmatcher.cc:897-952,
+ * :1055-1080, src/LSDmatcher.cpp:497-523) reads the keyframe's features, their descriptors and levels, and nothing the bookkeeping behind it
+ * (Replace / AddMapPoint / AddObservation, ORBmatcher.cc:955-975) writes: that bookkeeping can make LATER map points bad or IsInKeyFrame -- which
+ * decides whether the reference runs their search at all -- but it never moves a window or changes a descriptor.  So every neighbour of a keyframe,
+ * both directions of SearchInNeighbors and both directions of SearchBySim3 fit in one call, where the triangulation batch needs one call per round.
+ * The caller replays the bookkeeping in the reference's order (job by job, query by query: `bestDist <= TH_LOW`, then Replace or AddObservation) and
+ * DROPS the result of a query whose map point or line has become bad or attached to that keyframe meanwhile: the reference would have skipped it
+ * (:852-853), and a skipped query changes nothing for the others.
+ * inv_level_sigma2 is a HOST array of nlevels floats (1 <= nlevels <= 64, chi2_mode 1 only; ignored under chi2_mode 0), read before the call returns;
+ * bounds is host memory too.  Every other pointer is a device pointer; d_desc and d_qdesc are 16-byte aligned, the typed buffers 4-byte aligned.
+ * The call enqueues a clear of d_nfound and one launch on `stream` (NULL: the context's stream), uses no scratch, does not synchronise and is
+ * independent of every other call on the context.  SSLAM_ERR_INVALID (nothing enqueued): kind or chi2_mode not 0 or 1, chi2_mode 1 with kind 1,
+ * without a table or with nlevels outside 1..64; a NULL ctx, d_feats, d_desc, d_n, bounds, d_queries, d_qdesc, d_jobs, d_best_idx, d_best_dist or
+ * d_nfound; a misaligned buffer; a negative cap, qcap, nkeyframes, njobs or nqdesc; cap >= 2^19; njobs * qcap >= 2^31; njobs * max(1, ceil(qcap /
+ * 256)) >= 2^31 workgroups.  njobs == 0 is SSLAM_OK and enqueues nothing; qcap == 0 with njobs > 0 is SSLAM_OK and writes d_nfound alone (0, or -1
+ * for a skipped job). */
+typedef struct sslam_fuse_job {
+    int32_t kf;       /* keyframe slot searched (pKF) */
+    int32_t nq;       /* queries of this job */
+    int32_t qdesc0;   /* first descriptor row of this job in d_qdesc */
+} sslam_fuse_job;     /* 12 bytes, no padding */
+int sslam_fuse_search_batch_dev(sslam_ctx* ctx, int kind, int chi2_mode,
+                                const void* d_feats, const uint8_t* d_desc, const float* d_uright, const int32_t* d_n, int cap, int nkeyframes,
+                                const float bounds[4], const float* inv_level_sigma2, int nlevels,
+                                const sslam_proj_query* d_queries, int qcap, const uint8_t* d_qdesc, int nqdesc,
+                                const sslam_fuse_job* d_jobs, int njobs,
+                                int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_nfound, void* stream);
+
 /* ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t,size_t>>&, bOnlyStereo),
  * src/ORBmatcher.cc:660-826 (epipolar test CheckDistEpipolarLine :140-157), on two device-resident keyframes (their
  * mvuRight are in the handles).  free1[i] / free2[i] = !GetMapPoint(i); the two FeatureVectors as CSR lists over the shared

@@ -640,6 +640,57 @@ extern "C" int sslam_fuse_search(sslam_ctx* ctx, const sslam_frame* kf, int chi2
     return SSLAM_OK;
 }
 
+// ---- the same candidate search for jobs (keyframe slot, block of queries) on a device-resident pool of keyframe slots, asynchronous
+extern "C" int sslam_fuse_search_batch_dev(sslam_ctx* ctx, int kind, int chi2_mode,
+        const void* d_feats, const uint8_t* d_desc, const float* d_uright, const int32_t* d_n, int cap, int nkeyframes,
+        const float bounds[4], const float* inv_level_sigma2, int nlevels,
+        const sslam_proj_query* d_queries, int qcap, const uint8_t* d_qdesc, int nqdesc,
+        const sslam_fuse_job* d_jobs, int njobs,
+        int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_nfound, void* stream) {
+    const uintptr_t align4 = (uintptr_t)d_feats | (uintptr_t)d_uright | (uintptr_t)d_n | (uintptr_t)d_queries | (uintptr_t)d_jobs | (uintptr_t)d_best_idx |
+                             (uintptr_t)d_best_dist | (uintptr_t)d_nfound;
+    if (!ctx || (kind != 0 && kind != 1) || (chi2_mode != 0 && chi2_mode != 1) || (chi2_mode == 1 && (kind != 0 || !inv_level_sigma2 || nlevels < 1 || nlevels > 64)) ||
+        !d_feats || !d_desc || !d_n || !bounds || !d_queries || !d_qdesc || !d_jobs || !d_best_idx || !d_best_dist || !d_nfound ||
+        cap < 0 || cap >= (1 << 19) || qcap < 0 || nkeyframes < 0 || njobs < 0 || nqdesc < 0 || (long long)njobs * (long long)qcap >= (1ll << 31) ||
+        (align4 & 3) || (((uintptr_t)d_desc | (uintptr_t)d_qdesc) & 15)) {      // descriptor rows are read as two 16-byte words
+        set_error("sslam_fuse_search_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    const FuseBatchPlan P = fuse_batch_plan(cap, qcap, njobs);      // match_plan.h: the keyframe's geometry in LDS or in global memory, by the row capacity alone
+    if (P.grid >= (1ull << 31)) { set_error("sslam_fuse_search_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID; }
+    if (njobs == 0) return SSLAM_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    SSLAM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    FuseBatchArgs A;
+    A.chi2 = chi2_mode; A.feats = d_feats; A.desc = d_desc; A.uright = d_uright; A.n = d_n; A.cap = cap; A.nkeyframes = nkeyframes;
+    A.minX = bounds[0]; A.maxX = bounds[1]; A.minY = bounds[2]; A.maxY = bounds[3];
+    A.nlevels = chi2_mode ? nlevels : 0;
+    A.q = d_queries; A.qcap = qcap; A.qdesc = d_qdesc; A.nqdesc = nqdesc; A.jobs = d_jobs; A.chunks = P.chunks;
+    A.bestIdx = d_best_idx; A.bestDist = d_best_dist; A.nfound = d_nfound;
+    for (int i = 0; i < 64; ++i) A.invSigma2[i] = (chi2_mode && i < nlevels) ? inv_level_sigma2[i] : 0.f;
+    const dim3 grid((unsigned)P.grid), block(P.threads);
+    switch (P.form) {
+    case FuseBatchForm::Lds: {
+        int rc;
+        if ((rc = allow_dynamic_lds(kind == 0 ? (const void*)k_fuse_search_batch<0, true> : (const void*)k_fuse_search_batch<1, true>, P.ldsBytes))) return rc;
+        SSLAM_HIP(hipMemsetAsync(d_nfound, 0, sizeof(int32_t) * (size_t)njobs, st));      // every workgroup ADDS its chunk's count; a skipped job's chunk 0 stores -1
+        sslam::ProfScope _ps(ctx, "k_fuse_search_batch", st);
+        if (kind == 0) hipLaunchKernelGGL((k_fuse_search_batch<0, true>), grid, block, P.ldsBytes, st, A);
+        else hipLaunchKernelGGL((k_fuse_search_batch<1, true>), grid, block, P.ldsBytes, st, A);
+        break;
+    }
+    case FuseBatchForm::Global: {
+        SSLAM_HIP(hipMemsetAsync(d_nfound, 0, sizeof(int32_t) * (size_t)njobs, st));
+        sslam::ProfScope _ps(ctx, "k_fuse_search_batch", st);
+        if (kind == 0) hipLaunchKernelGGL((k_fuse_search_batch<0, false>), grid, block, 0, st, A);
+        else hipLaunchKernelGGL((k_fuse_search_batch<1, false>), grid, block, 0, st, A);
+        break;
+    }
+    }
+    SSLAM_HIP(hipGetLastError());
+    return SSLAM_OK;
+}
+
 // ORBmatcher::SearchForTriangulation on two device-resident keyframes (their mvuRight travel with the handles).
 extern "C" int sslam_orb_search_for_triangulation(sslam_ctx* ctx, const sslam_frame* kf1, const sslam_frame* kf2, const uint8_t* free1, const uint8_t* free2,
                                                   const int32_t* node_kf1_ptr, const int32_t* node_kf2_ptr, int nnodes, const int32_t* kf1_idx, const int32_t* kf2_idx,

@@ -8,6 +8,55 @@
 // (src/LSDmatcher.cpp:497-523): every query keeps the candidate with the smallest Hamming distance, the first one in
 // KeyFrame::GetFeaturesInArea / GetLinesInArea order on ties.  Queries do not interact, so one wave takes one query and scans
 // the keyframe's features lane-parallel; the candidate order travels in the low bits of the min-reduction key.
+// The rules of one candidate exist once, here, for the single call's kernel and the batch's:
+//   fuse_grid / fuse_cell   the 64 x 48 grid Frame::AssignFeaturesToGrid files a keypoint in (PosInGrid, src/Frame.cc:133-148, :462-472; the keyframe copies it): -1 for a keypoint
+//                           that is in no cell and so in no GetFeaturesInArea result, else the cell's rank in the column-major walk of the window
+//   fuse_point_window       |dx| < r, |dy| < r (KeyFrame::GetFeaturesInArea, src/KeyFrame.cc:610-649) and the level test of src/ORBmatcher.cc:912-915
+//   fuse_inv_sigma2         mvInvLevelSigma2[level]; a level outside the table weighs 0, so that nothing beyond the table is read
+//   fuse_point_chi2         the 7.8 (stereo) / 5.99 (monocular) gates of src/ORBmatcher.cc:917-941
+//   fuse_line_ok            midpoint distance, slope against the keyline's angle (KeyFrame::GetLinesInArea, src/KeyFrame.cc:652-683) and the level test
+//   fuse_key                smallest distance first, then GetFeaturesInArea order: cell by cell, inside a cell by ascending index (lines: the index alone)
+// The float operations and their order are k_fuse_search's own.
+struct FuseGrid { float minX, minY, invW, invH; };
+__device__ __forceinline__ FuseGrid fuse_grid(float minX, float maxX, float minY, float maxY) {
+    return {minX, minY, __fdiv_rn((float)GRID_COLS, __fsub_rn(maxX, minX)), __fdiv_rn((float)GRID_ROWS, __fsub_rn(maxY, minY))};
+}
+__device__ __forceinline__ int fuse_cell(const FuseGrid& G, float x, float y) {
+    const int px = (int)roundf(__fmul_rn(__fsub_rn(x, G.minX), G.invW));
+    const int py = (int)roundf(__fmul_rn(__fsub_rn(y, G.minY), G.invH));
+    if (!(px >= 0 && px < GRID_COLS && py >= 0 && py < GRID_ROWS)) return -1;      // not in the grid at all
+    return px * GRID_ROWS + py;
+}
+__device__ __forceinline__ bool fuse_point_window(const sslam_proj_query& Q, float x, float y, int lvl) {
+    const float dx = __fsub_rn(x, Q.u), dy = __fsub_rn(y, Q.v);
+    if (!(fabsf(dx) < Q.radius && fabsf(dy) < Q.radius)) return false;
+    return !(lvl < Q.min_level || lvl > Q.max_level);
+}
+__device__ __forceinline__ float fuse_inv_sigma2(const float* table, int nlevels, int lvl) { return (lvl >= 0 && lvl < nlevels) ? table[lvl] : 0.f; }
+// ur: the keypoint's right coordinate, below 0 for a monocular keypoint (and for a keyframe without right coordinates)
+__device__ __forceinline__ bool fuse_point_chi2(const sslam_proj_query& Q, float x, float y, float ur, float inv) {
+    const float ex = __fsub_rn(Q.u, x), ey = __fsub_rn(Q.v, y);
+    if (ur >= 0) {
+        const float er = __fsub_rn(Q.ur, ur);
+        const float e2 = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(er, er));
+        return !((double)__fmul_rn(e2, inv) > 7.8);
+    }
+    const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+    return !((double)__fmul_rn(e2, inv) > 5.99);
+}
+__device__ __forceinline__ bool fuse_line_ok(const sslam_proj_query& Q, float pt_x, float pt_y, float angle, int lvl) {
+    const double mxp = 0.5 * (double)__fadd_rn(Q.u, Q.u2) - (double)pt_x, myp = 0.5 * (double)__fadd_rn(Q.v, Q.v2) - (double)pt_y;
+    const float distance = (float)(mxp * mxp + myp * myp);
+    if (distance > __fmul_rn(Q.radius, Q.radius)) return false;
+    const float slope = __fsub_rn(__fdiv_rn(__fsub_rn(Q.v, Q.v2), __fsub_rn(Q.u, Q.u2)), angle);
+    if ((double)slope > (double)Q.radius * 0.01) return false;
+    return !(lvl < Q.min_level || lvl > Q.max_level);
+}
+// cell < 2^12 and i < 2^19: 31 bits; lines pass cell 0
+__device__ __forceinline__ unsigned long long fuse_key(int dist, int cell, int i) { return ((unsigned long long)dist << 32) | (unsigned)((cell << 19) | i); }
+__device__ __forceinline__ int fuse_key_idx(unsigned long long key) { return key == ~0ull ? -1 : (int)(key & 0x7FFFF); }
+__device__ __forceinline__ int fuse_key_dist(unsigned long long key) { return key == ~0ull ? 0x7fffffff : (int)(key >> 32); }
+
 struct FuseArgs {
     int kind, chi2;
     const void* feats; const uint8_t* desc; int n;
@@ -20,59 +69,143 @@ __global__ __launch_bounds__(64) void k_fuse_search(FuseArgs A) {
     const int lane = threadIdx.x;
     const sslam_keypoint* kps = (const sslam_keypoint*)A.feats;
     const sslam_keyline* kls = (const sslam_keyline*)A.feats;
-    const float invW = __fdiv_rn((float)GRID_COLS, __fsub_rn(A.maxX, A.minX));
-    const float invH = __fdiv_rn((float)GRID_ROWS, __fsub_rn(A.maxY, A.minY));
+    const FuseGrid G = fuse_grid(A.minX, A.maxX, A.minY, A.maxY);
     for (int iq = blockIdx.x; iq < A.nq; iq += gridDim.x) {
         const sslam_proj_query Q = A.q[iq];
         unsigned long long b = ~0ull;
         if (Q.valid) {
             const uint4 q0 = ((const uint4*)(A.qdesc + (size_t)iq * 32))[0], q1 = ((const uint4*)(A.qdesc + (size_t)iq * 32))[1];
             for (int i = lane; i < A.n; i += 64) {
-                int key = i, lvl;
+                int cell = 0;
                 if (A.kind == 0) {
                     const sslam_keypoint kp = kps[i];
-                    const int px = (int)roundf(__fmul_rn(__fsub_rn(kp.x, A.minX), invW));
-                    const int py = (int)roundf(__fmul_rn(__fsub_rn(kp.y, A.minY), invH));
-                    if (!(px >= 0 && px < GRID_COLS && py >= 0 && py < GRID_ROWS)) continue;      // not in the grid at all
-                    key = ((px * GRID_ROWS + py) << 19) | i;
-                    const float dx = __fsub_rn(kp.x, Q.u), dy = __fsub_rn(kp.y, Q.v);
-                    if (!(fabsf(dx) < Q.radius && fabsf(dy) < Q.radius)) continue;
-                    lvl = kp.octave;
-                    if (lvl < Q.min_level || lvl > Q.max_level) continue;
-                    if (A.chi2) {
-                        const float ex = __fsub_rn(Q.u, kp.x), ey = __fsub_rn(Q.v, kp.y);
-                        const float inv = (lvl >= 0 && lvl < A.nlevels) ? A.invSigma2[lvl] : 0.f;
-                        const float ur = A.uright ? A.uright[i] : -1.f;
-                        if (ur >= 0) {
-                            const float er = __fsub_rn(Q.ur, ur);
-                            const float e2 = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(er, er));
-                            if ((double)__fmul_rn(e2, inv) > 7.8) continue;
-                        } else {
-                            const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-                            if ((double)__fmul_rn(e2, inv) > 5.99) continue;
-                        }
-                    }
+                    cell = fuse_cell(G, kp.x, kp.y);
+                    if (cell < 0) continue;
+                    if (!fuse_point_window(Q, kp.x, kp.y, kp.octave)) continue;
+                    if (A.chi2 && !fuse_point_chi2(Q, kp.x, kp.y, A.uright ? A.uright[i] : -1.f, fuse_inv_sigma2(A.invSigma2, A.nlevels, kp.octave))) continue;
                 } else {
                     const sslam_keyline kl = kls[i];
-                    const double mxp = 0.5 * (double)__fadd_rn(Q.u, Q.u2) - (double)kl.pt_x, myp = 0.5 * (double)__fadd_rn(Q.v, Q.v2) - (double)kl.pt_y;
-                    const float distance = (float)(mxp * mxp + myp * myp);
-                    if (distance > __fmul_rn(Q.radius, Q.radius)) continue;
-                    const float slope = __fsub_rn(__fdiv_rn(__fsub_rn(Q.v, Q.v2), __fsub_rn(Q.u, Q.u2)), kl.angle);
-                    if ((double)slope > (double)Q.radius * 0.01) continue;
-                    lvl = kl.octave;
-                    if (lvl < Q.min_level || lvl > Q.max_level) continue;
+                    if (!fuse_line_ok(Q, kl.pt_x, kl.pt_y, kl.angle, kl.octave)) continue;
                 }
                 const uint4* tp = (const uint4*)(A.desc + (size_t)i * 32);
-                const unsigned long long kk = ((unsigned long long)hamming256(q0, q1, tp[0], tp[1]) << 32) | (unsigned)key;
+                const unsigned long long kk = fuse_key(hamming256(q0, q1, tp[0], tp[1]), cell, i);
                 b = kk < b ? kk : b;
             }
         }
         b = wave_min_u64(b);
         if (lane == 0) {
-            A.bestIdx[iq] = b == ~0ull ? -1 : (int)(b & 0x7FFFF);
-            A.bestDist[iq] = b == ~0ull ? 0x7fffffff : (int)(b >> 32);
+            A.bestIdx[iq] = fuse_key_idx(b);
+            A.bestDist[iq] = fuse_key_dist(b);
         }
     }
+}
+
+// ------------------------------------------------------------------ Fuse / SearchBySim3 candidate search of a batch (sslam_fuse_search_batch_dev)
+// The same search for jobs (keyframe slot, block of queries) on one device-resident pool of keyframe slots.  One workgroup of FUSE_BATCH_WAVES waves
+// per (job, chunk of FUSE_BATCH_CHUNK queries), the grid flattened job-major (match_plan.h).  Where k_fuse_search recomputes every feature's grid cell
+// for every (query, feature) pair and reads 28 or 68 bytes of a row to test 12, the workgroup stages the keyframe's GEOMETRY once, as four arrays of
+// cap words in dynamic LDS (FUSE_BATCH_ROW_BYTES per row): x, y, uright, octave of a keypoint, pt_x, pt_y, angle, octave of a keyline.  A keypoint in
+// no grid cell is staged with x = NaN: every window test rejects it, which is what the single kernel's first gate does.  Consecutive lanes read
+// consecutive words of one array: no bank conflicts.  Wave w takes the chunk's queries w, w + FUSE_BATCH_WAVES, .. in turn and scans the rows
+// lane-parallel; only a row that passed every gate -- a handful of a thousand under a window of 3 x scale -- has its cell computed and its 32-byte
+// descriptor read, from global memory.  fuse_key and wave_min_u64 reduce as in the single kernel.
+// d_nfound: the host zeroes it ahead of the launch; every workgroup adds the candidates of its chunk with ONE agent-scope atomic (none where it found
+// nothing).  A skipped job gets -1 from its chunk 0 alone and its other chunks leave without adding, so no workgroup races with that store.
+// Every loop is bounded by a clamped count or a constant; the two barriers sit behind conditions that are uniform over the workgroup (the job, its
+// clamped query count and the chunk).  Rows at or past a keyframe's count, queries at or past a job's count and right coordinates of a NULL d_uright
+// are never read.
+struct FuseBatchArgs {
+    int chi2;
+    const void* feats; const uint8_t* desc; const float* uright; const int* n; int cap, nkeyframes;
+    float minX, maxX, minY, maxY;
+    int nlevels;
+    const sslam_proj_query* q; int qcap; const uint8_t* qdesc; int nqdesc;
+    const sslam_fuse_job* jobs; unsigned chunks;
+    int* bestIdx; int* bestDist; int* nfound;
+    float invSigma2[64];                     // the level table travels in the kernel's arguments: read from the caller's host array before the call returns; 0 past nlevels
+};
+// kLds: the keyframe's geometry in dynamic LDS; otherwise the scan reads the caller's buffers, with the single kernel's grid gate per row
+template <int kind, bool kLds>
+__global__ __launch_bounds__(64 * FUSE_BATCH_WAVES) void k_fuse_search_batch(FuseBatchArgs A) {
+    extern __shared__ __align__(16) unsigned fsl[];
+    __shared__ float invS[64];
+    __shared__ int total;
+    constexpr int NT = 64 * FUSE_BATCH_WAVES;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned j = blockIdx.x / A.chunks, chunk = blockIdx.x - j * A.chunks;
+    const sslam_fuse_job J = A.jobs[j];
+    const int nq = min(max(J.nq, 0), A.qcap);
+    // (uniform over the workgroup, ahead of every barrier)
+    if (J.kf < 0 || J.kf >= A.nkeyframes || J.qdesc0 < 0 || (long long)J.qdesc0 + nq > (long long)A.nqdesc) {
+        if (chunk == 0 && tid == 0) A.nfound[j] = -1;
+        return;
+    }
+    const int q0 = (int)chunk * FUSE_BATCH_CHUNK, q1 = min(nq, q0 + FUSE_BATCH_CHUNK);
+    if (q0 >= nq) return;                                        // d_nfound[j] keeps the host's 0 where the job has no query
+    const int n = min(max(A.n[J.kf], 0), A.cap);
+    const size_t r = (size_t)J.kf * (size_t)A.cap;
+    const sslam_keypoint* kps = (const sslam_keypoint*)A.feats + r;
+    const sslam_keyline* kls = (const sslam_keyline*)A.feats + r;
+    const uint8_t* desc = A.desc + r * 32;
+    const float* uright = A.uright ? A.uright + r : nullptr;
+    const sslam_proj_query* qs = A.q + (size_t)j * (size_t)A.qcap;
+    const uint8_t* qdesc = A.qdesc + (size_t)J.qdesc0 * 32;
+    int* outIdx = A.bestIdx + (size_t)j * (size_t)A.qcap; int* outDist = A.bestDist + (size_t)j * (size_t)A.qcap;
+    const FuseGrid G = fuse_grid(A.minX, A.maxX, A.minY, A.maxY);
+    float* la = (float*)fsl; float* lb = la + A.cap; float* lc = lb + A.cap; int* lo = (int*)(lc + A.cap);
+    if (kLds) {
+        for (int i = tid; i < n; i += NT) {
+            if (kind == 0) {
+                const sslam_keypoint kp = kps[i];
+                la[i] = fuse_cell(G, kp.x, kp.y) < 0 ? __int_as_float(0x7fc00000) : kp.x; lb[i] = kp.y;
+                lc[i] = (A.chi2 && uright) ? uright[i] : -1.f; lo[i] = kp.octave;
+            } else {
+                const sslam_keyline kl = kls[i];
+                la[i] = kl.pt_x; lb[i] = kl.pt_y; lc[i] = kl.angle; lo[i] = kl.octave;
+            }
+        }
+    }
+    if (tid < 64) invS[tid] = A.invSigma2[tid];
+    if (tid == 0) total = 0;
+    __syncthreads();
+    // the scan: no workgroup barrier in here
+    int found = 0;
+    for (int iq = q0 + wave; iq < q1; iq += FUSE_BATCH_WAVES) {
+        const sslam_proj_query Q = qs[iq];
+        unsigned long long b = ~0ull;
+        if (Q.valid) {
+            const uint4 d0 = ((const uint4*)(qdesc + (size_t)iq * 32))[0], d1 = ((const uint4*)(qdesc + (size_t)iq * 32))[1];
+            for (int i = lane; i < n; i += 64) {
+                int cell = 0;
+                if (kind == 0) {
+                    float x, y; int lvl;
+                    if (kLds) { x = la[i]; y = lb[i]; lvl = lo[i]; }
+                    else {
+                        const sslam_keypoint kp = kps[i];
+                        x = kp.x; y = kp.y; lvl = kp.octave;
+                        if (fuse_cell(G, x, y) < 0) continue;
+                    }
+                    if (!fuse_point_window(Q, x, y, lvl)) continue;
+                    if (A.chi2 && !fuse_point_chi2(Q, x, y, kLds ? lc[i] : (uright ? uright[i] : -1.f), fuse_inv_sigma2(invS, A.nlevels, lvl))) continue;
+                    cell = fuse_cell(G, x, y);                   // survivors only: k_fuse_search's expression on the same two floats
+                } else {
+                    float px, py, ang; int lvl;
+                    if (kLds) { px = la[i]; py = lb[i]; ang = lc[i]; lvl = lo[i]; }
+                    else { const sslam_keyline* kl = kls + i; px = kl->pt_x; py = kl->pt_y; ang = kl->angle; lvl = kl->octave; }
+                    if (!fuse_line_ok(Q, px, py, ang, lvl)) continue;
+                }
+                const uint4* tp = (const uint4*)(desc + (size_t)i * 32);
+                const unsigned long long kk = fuse_key(hamming256(d0, d1, tp[0], tp[1]), cell, i);
+                b = kk < b ? kk : b;
+            }
+        }
+        b = wave_min_u64(b);
+        if (lane == 0) { outIdx[iq] = fuse_key_idx(b); outDist[iq] = fuse_key_dist(b); }
+        found += b != ~0ull ? 1 : 0;
+    }
+    if (lane == 0 && found) atomicAdd(&total, found);
+    __syncthreads();
+    if (tid == 0 && total) atomicAdd(&A.nfound[j], total);
 }
 
 // ------------------------------------------------------------------ ORBmatcher::SearchForTriangulation

@@ -212,6 +212,42 @@ inline TriBatchPlan tri_batch_plan(int cap, int npairs) {
     return P;
 }
 
+// -------------------------------------------------------------- Fuse / SearchBySim3 candidate search of a batch (sslam_fuse_search_batch_dev)
+// One workgroup of FUSE_BATCH_WAVES waves per (job, chunk of FUSE_BATCH_CHUNK queries) -- k_fuse_search_batch; the grid is flattened to one dimension,
+// job-major: workgroup g serves chunk g % chunks of job g / chunks.  chunks = ceil(qcap / FUSE_BATCH_CHUNK), and 1 where qcap is 0: chunk 0 of a job
+// is the one that reports a skipped job, so it exists for every job.  The form follows the row capacity alone (every job of a launch runs the same
+// kernel), the grid follows njobs and qcap alone:
+//   Lds     the keyframe's GEOMETRY sits in the workgroup's LDS as four arrays of cap words (x, y, uright, octave resp. pt_x, pt_y, angle, octave):
+//           FUSE_BATCH_ROW_BYTES * cap bytes, while that is at most FUSE_BATCH_LDS_MAX (64 KB: cap <= 4096; two workgroups per compute unit at the
+//           bound; at 1000 rows the 32 wave slots admit four and the LDS is no limit); more than DYNAMIC_LDS_DEFAULT_MAX (cap > 3072) needs the per-kernel opt-in.  Descriptors are never staged: a
+//           window admits a handful of rows, and only those rows' descriptors are read
+//   Global  beyond that: the same kernel scans the caller's buffers, with no dynamic LDS
+// No scratch: a job's state is in its workgroups' LDS, their registers and the job's own output rows.
+constexpr int FUSE_BATCH_WAVES = 8;
+constexpr int FUSE_BATCH_ROW_BYTES = 16;
+constexpr int FUSE_BATCH_CHUNK = 256;
+constexpr size_t FUSE_BATCH_LDS_MAX = 64 * 1024;
+enum class FuseBatchForm { Lds, Global };
+struct FuseBatchPlan {
+    FuseBatchForm form;
+    size_t ldsBytes;          // dynamic LDS per workgroup (0: Global)
+    int ldsOptIn;             // ldsBytes is more than a launch may ask for without hipFuncSetAttribute
+    unsigned threads;         // workgroup size
+    unsigned chunks;          // workgroups per job, at least 1
+    unsigned long long grid;  // workgroups: njobs * chunks (the entry point refuses 2^31 and more)
+};
+inline FuseBatchPlan fuse_batch_plan(int cap, int qcap, int njobs) {
+    FuseBatchPlan P{};
+    const size_t lds = (size_t)FUSE_BATCH_ROW_BYTES * (size_t)cap;
+    P.form = lds <= FUSE_BATCH_LDS_MAX ? FuseBatchForm::Lds : FuseBatchForm::Global;
+    P.ldsBytes = P.form == FuseBatchForm::Lds ? lds : 0;
+    P.ldsOptIn = P.ldsBytes > DYNAMIC_LDS_DEFAULT_MAX ? 1 : 0;
+    P.threads = 64u * FUSE_BATCH_WAVES;
+    P.chunks = (unsigned)std::max(1, (int)(((long long)qcap + FUSE_BATCH_CHUNK - 1) / FUSE_BATCH_CHUNK));
+    P.grid = (unsigned long long)njobs * P.chunks;
+    return P;
+}
+
 // arena of search_proj_core.  occ | q | qdesc go up in ONE copy (occ .. assigned), assigned | count come back in one (assigned .. count + 4);
 // only that head (.. count + 256) has a pinned mirror.  projK = list length of k_proj_topk (PROJ_K).
 struct ProjArena {

@@ -27,6 +27,9 @@ assert PQ_DTYPE.itemsize == 44
 TRI_PAIR_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("F12", "<f4", (9,)), ("ex", "<f4"), ("ey", "<f4")])      # sslam_tri_pair
 assert TRI_PAIR_DTYPE.itemsize == 52
 
+FUSE_JOB_DTYPE = np.dtype([("kf", "<i4"), ("nq", "<i4"), ("qdesc0", "<i4")])      # sslam_fuse_job
+assert FUSE_JOB_DTYPE.itemsize == 12
+
 _lib = None
 
 PIX_GRAY, PIX_RGB, PIX_BGR, PIX_RGBA, PIX_BGRA = 0, 1, 2, 3, 4      # SSLAM_PIX_* (include/sslam_frontend.h)
@@ -226,6 +229,20 @@ class Context:
                                                                 int(nkeyframes), _p(d_pairs), int(npairs), _p(sf), _p(sg), int(nlevels),
                                                                 int(bool(only_stereo)), int(bool(check_orientation)), _p(d_matches12), _p(d_nmatches),
                                                                 C.c_void_p(stream or 0)))
+
+    def fuse_search_batch_dev(self, kind, chi2_mode, d_feats, d_desc, d_n, cap, nkeyframes, d_queries, qcap, d_qdesc, nqdesc, d_jobs, njobs,
+                              d_best_idx, d_best_dist, d_nfound, d_uright=None, inv_level_sigma2=None, nlevels=None, bounds=(0.0, 640.0, 0.0, 480.0),
+                              stream=None):
+        """sslam_fuse_search_batch_dev on device tensors / pointers: job j = d_jobs[j] (FUSE_JOB_DTYPE rows on the device) searches keyframe slot kf of
+        the pool d_feats / d_desc / d_n [/ d_uright] with the queries in rows j*qcap .. of d_queries (PQ_DTYPE) and the descriptors in rows qdesc0 .. of
+        d_qdesc; inv_level_sigma2 is a HOST array (chi2_mode 1; nlevels: its length unless given); d_best_idx / d_best_dist [njobs, qcap] int32,
+        d_nfound [njobs] int32; enqueues on `stream` (None: the context's) and returns without synchronising"""
+        sg = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, np.float32)
+        if nlevels is None: nlevels = 0 if sg is None else len(sg)
+        b = None if bounds is None else (C.c_float * 4)(*bounds)
+        _chk(lib().sslam_fuse_search_batch_dev(self.h, int(kind), int(chi2_mode), _p(d_feats), _p(d_desc), _p(d_uright), _p(d_n), int(cap), int(nkeyframes),
+                                               b, _p(sg), int(nlevels), _p(d_queries), int(qcap), _p(d_qdesc), int(nqdesc), _p(d_jobs), int(njobs),
+                                               _p(d_best_idx), _p(d_best_dist), _p(d_nfound), C.c_void_p(stream or 0)))
 
     def search_by_bow_keyframes(self, kp1, d1, valid1, kp2, d2, valid2, ptr1, ptr2, idx1, idx2, nnratio=0.8, check_orientation=True):
         """ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (src/ORBmatcher.cc:525-658): -> (matches12, nmatches)"""
