@@ -428,6 +428,45 @@ int sslam_compute_bow_frame(sslam_ctx* ctx, const sslam_vocab* vocab, const ssla
  * the rest (median = sorted[int(0.5*(N-1))], first row wins ties), -1 for an empty set.  Sets are limited to 1024 rows. */
 int sslam_distinctive_descriptors(sslam_ctx* ctx, const uint8_t* desc, const int32_t* ptr, int nsets, int32_t* best_out);
 
+/* The same choice (src/MapPoint.cc:247-312, src/MapLine.cpp:246-317) for `nsets` observation sets whose descriptors are rows of device-resident
+ * keyframes, asynchronously: the pMP->ComputeDistinctiveDescriptors() behind every triangulated, fused or initialised map point and line
+ * (src/LocalMapping.cc CreateNewMapPoints / CreateNewMapLines2 and SearchInNeighbors, Tracking::CreateInitialMapMonoWithPL) for callers that keep many
+ * sessions' keyframes on the device.  The two reference functions differ only in the descriptor matrix they read (mDescriptors, mLineDescriptors);
+ * ORB and LBD rows are both 32 bytes, so there is no kind argument.  The pool is sslam_orb_search_for_triangulation_batch_dev's and
+ * sslam_fuse_search_batch_dev's: keyframe slot k owns rows [k*cap, k*cap + d_n[k]) of d_desc.  A count below 0 is read as 0, one above cap as cap;
+ * nothing at or past a count is read.
+ * Set s owns the entries d_obs[d_ptr[s] .. d_ptr[s+1]) (d_ptr: nsets + 1 ints), one (keyframe slot, feature row) per observation in the caller's
+ * mObservations iteration order -- the reference walks a std::map<KeyFrame*, size_t>, i.e. in address order; what that order is, is the caller's to
+ * say, and ties go to the first.  An entry is ADMISSIBLE when 0 <= kf < nkeyframes, d_kf_bad is NULL or d_kf_bad[kf] == 0 (pKF->isBad(), :270) and
+ * 0 <= row < the slot's clamped count; any other entry is skipped exactly as the reference skips a bad keyframe.  N is the number of admissible
+ * entries, the median of an entry is sorted[int(0.5 * (N - 1))] of its N distances to the admissible entries (itself included, :283), and the same
+ * (kf, row) twice in a set is legal and counts twice.
+ * d_best[s] = the position inside the set's entry list (0 .. d_ptr[s+1] - d_ptr[s] - 1, skipped entries counted) of the admissible entry with the
+ * least median; the first such entry wins (`median < BestMedian`, :301).  -1 when no entry is admissible (the reference's early returns, :261 and
+ * :274).  -2 when the set is refused: its range fails 0 <= d_ptr[s] <= d_ptr[s+1] <= nobs, or it has more than 1024 entries (the single call's limit;
+ * the batch has no status per set beyond this).  d_median[s] (d_median may be NULL) = that least median, INT_MAX with -1 or -2.  Every set writes
+ * its d_best and d_median, so the call enqueues no clear of them.
+ * d_out_desc (may be NULL) is a table of nout rows of 32 bytes: a set with d_best >= 0 copies the chosen descriptor to row d_out_row[s], or to row s
+ * where d_out_row is NULL; a target outside [0, nout) is not written, and a set with -1 or -2 leaves its row as it was (the reference leaves
+ * mDescriptor unchanged).  When two sets name one row, one of them wins and which one is unspecified.  The table is what
+ * sslam_fuse_search_batch_dev and sslam_search_by_projection_batch_dev take as d_qdesc, without a copy.
+ * WHY ONE CALL IS EXACT: a set's result depends on no other set.  The function reads the observed rows and the bad flags and writes mDescriptor
+ * alone (:310); no other map point's choice reads that, and the caller omits the sets of map points with mbBad (:256).
+ * Every pointer is a device pointer; d_desc and d_out_desc are 16-byte aligned, the typed buffers 4-byte aligned.  The call enqueues two launches on
+ * `stream` (NULL: the context's stream) -- sets of up to 64 entries, and the rare ones of 65 .. 1024 -- uses no scratch, reads and writes no host
+ * memory, does not synchronise and is independent of every other call on the context.  SSLAM_ERR_INVALID (nothing enqueued): a NULL ctx, d_desc,
+ * d_n, d_ptr or d_best; a NULL d_obs with nobs > 0; d_out_row without d_out_desc; a misaligned buffer; a negative cap, nkeyframes, nobs, nsets or
+ * nout; cap >= 2^19; nkeyframes * cap >= 2^31.  nsets == 0 is SSLAM_OK and enqueues nothing. */
+typedef struct sslam_observation {
+    int32_t kf;       /* keyframe slot (mObservations' key) */
+    int32_t row;      /* feature row in that keyframe (mObservations' value) */
+} sslam_observation;  /* 8 bytes, no padding */
+int sslam_distinctive_descriptors_batch_dev(sslam_ctx* ctx,
+                                            const uint8_t* d_desc, const int32_t* d_n, int cap, int nkeyframes, const uint8_t* d_kf_bad,
+                                            const sslam_observation* d_obs, int nobs, const int32_t* d_ptr, int nsets,
+                                            int32_t* d_best, int32_t* d_median,
+                                            uint8_t* d_out_desc, const int32_t* d_out_row, int nout, void* stream);
+
 /* ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches), src/ORBmatcher.cc:159-291.
  * The DBoW2 vocabulary transform stays on the host (the vocabulary file is not part of the reference tree); the
  * matcher takes the two FeatureVectors as CSR lists over the nodes BOTH frames contain, ascending node id:

@@ -20,6 +20,7 @@ namespace {
 #include "match_rot.h"
 #include "match_ordered.h"
 #include "match_independent.h"
+#include "match_distinct.h"
 
 }  // namespace
 
@@ -601,6 +602,32 @@ extern "C" int sslam_distinctive_descriptors(sslam_ctx* ctx, const uint8_t* desc
     SSLAM_HIP(hipGetLastError());
     SSLAM_HIP(hipMemcpyAsync(best_out, B + oB, 4 * (size_t)nsets, hipMemcpyDeviceToHost, st));
     SSLAM_HIP(hipStreamSynchronize(st));
+    return SSLAM_OK;
+}
+
+// ---- the same choice for observation sets that name rows of a device-resident pool of keyframe slots, asynchronous (match_distinct.h)
+extern "C" int sslam_distinctive_descriptors_batch_dev(sslam_ctx* ctx,
+        const uint8_t* d_desc, const int32_t* d_n, int cap, int nkeyframes, const uint8_t* d_kf_bad,
+        const sslam_observation* d_obs, int nobs, const int32_t* d_ptr, int nsets,
+        int32_t* d_best, int32_t* d_median,
+        uint8_t* d_out_desc, const int32_t* d_out_row, int nout, void* stream) {
+    const uintptr_t align4 = (uintptr_t)d_n | (uintptr_t)d_obs | (uintptr_t)d_ptr | (uintptr_t)d_best | (uintptr_t)d_median | (uintptr_t)d_out_row;
+    if (!ctx || !d_desc || !d_n || !d_ptr || !d_best || (nobs > 0 && !d_obs) || (d_out_row && !d_out_desc) ||
+        cap < 0 || cap >= (1 << 19) || nkeyframes < 0 || nobs < 0 || nsets < 0 || nout < 0 || (long long)nkeyframes * (long long)cap >= (1ll << 31) ||
+        (align4 & 3) || (((uintptr_t)d_desc | (uintptr_t)d_out_desc) & 15)) {      // descriptor rows are read and written as two 16-byte words
+        set_error("sslam_distinctive_descriptors_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (nsets == 0) return SSLAM_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    SSLAM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    const DistinctBatchPlan P = distinct_batch_plan(nsets);      // match_plan.h: a set's kernel follows its entry count, which only the device reads
+    DistinctArgs A;
+    A.desc = d_desc; A.n = d_n; A.cap = cap; A.nkeyframes = nkeyframes; A.bad = d_kf_bad; A.obs = d_obs; A.nobs = nobs; A.ptr = d_ptr; A.nsets = nsets;
+    A.best = d_best; A.median = d_median; A.outDesc = d_out_desc; A.outRow = d_out_row; A.nout = nout;
+    { sslam::ProfScope _ps(ctx, "k_distinct_batch", st); hipLaunchKernelGGL(k_distinct_batch, dim3(P.grid), dim3(P.threads), 0, st, A); }      // small and medium sets, refusals
+    { sslam::ProfScope _ps(ctx, "k_distinct_large", st); hipLaunchKernelGGL(k_distinct_large, dim3(P.largeGrid), dim3(P.largeThreads), 0, st, A); }      // the rare large ones
+    SSLAM_HIP(hipGetLastError());
     return SSLAM_OK;
 }
 

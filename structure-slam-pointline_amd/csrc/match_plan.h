@@ -248,6 +248,57 @@ inline FuseBatchPlan fuse_batch_plan(int cap, int qcap, int njobs) {
     return P;
 }
 
+// -------------------------------------------------------------- ComputeDistinctiveDescriptors of a batch (sslam_distinctive_descriptors_batch_dev)
+// A set's kernel follows its ENTRY count, d_ptr[s + 1] - d_ptr[s], which only the device reads: every call enqueues both kernels.
+//   Small    0 .. 8 entries: eight consecutive sets share one wave of k_distinct_batch, each in its own group of eight lanes, lane = entry, rows in
+//            registers, no LDS
+//   Medium   9 .. 64 entries: the wave that owns the set's group of eight runs it alone afterwards, lane = entry: the admissible rows in 2 KB of the
+//            wave's LDS, every pair distance once as 16 bits of an 8 KB matrix (two per word, column = lane) that the nine bisection steps count on
+//   Large    65 .. 1024 entries: k_distinct_large, one wave per workgroup with the rows (32 KB) and their entry positions (2 KB) in LDS; a wave looks at
+//            64 sets at a time (lane = set) and runs the large ones among them, so the reservation never sets the occupancy of the first kernel
+//   Refused  a malformed range or more than 1024 entries: -2, written by k_distinct_batch
+// k_distinct_batch: DISTINCT_BATCH_WAVES waves per workgroup, wave w of the grid takes the units (runs of eight sets) w, w + waves of the grid, ..;
+// the grid is capped at DISTINCT_BATCH_GRID_MAX workgroups (8 per compute unit: the 40 KB of a workgroup admit 4, so two rounds).
+// k_distinct_large: chunk c of 64 sets goes to workgroup c % grid, the grid is capped at DISTINCT_LARGE_GRID_MAX.
+constexpr int DISTINCT_SMALL_MAX = 8;
+constexpr int DISTINCT_MEDIUM_MAX = 64;
+constexpr int DISTINCT_LARGE_MAX = 1024;          // = DISTINCT_MAXN of the single call
+constexpr int DISTINCT_SETS_PER_WAVE = 8;
+constexpr int DISTINCT_BATCH_WAVES = 4;
+constexpr unsigned DISTINCT_BATCH_GRID_MAX = 2048;
+constexpr size_t DISTINCT_MEDIUM_ROW_BYTES = 32 * (size_t)DISTINCT_MEDIUM_MAX;                                   // 2 KB per wave
+constexpr size_t DISTINCT_MEDIUM_DIST_BYTES = 2 * (size_t)DISTINCT_MEDIUM_MAX * (size_t)DISTINCT_MEDIUM_MAX;    // 8 KB per wave
+constexpr int DISTINCT_LARGE_CHUNK = 64;
+constexpr unsigned DISTINCT_LARGE_GRID_MAX = 1024;
+constexpr size_t DISTINCT_LARGE_LDS_BYTES = (32 + 2) * (size_t)DISTINCT_LARGE_MAX;
+enum class DistinctClass { Small, Medium, Large, Refused };
+constexpr DistinctClass distinct_class(long long entries) {
+    return entries < 0 ? DistinctClass::Refused : entries <= DISTINCT_SMALL_MAX ? DistinctClass::Small : entries <= DISTINCT_MEDIUM_MAX ? DistinctClass::Medium :
+           entries <= DISTINCT_LARGE_MAX ? DistinctClass::Large : DistinctClass::Refused;
+}
+struct DistinctBatchPlan {
+    int launches;             // 0 without a set, else 2
+    unsigned threads;         // k_distinct_batch: workgroup size
+    unsigned grid;            // k_distinct_batch: workgroups, at most DISTINCT_BATCH_GRID_MAX (the waves stride over the units)
+    size_t ldsBytes;          // k_distinct_batch: static LDS per workgroup
+    unsigned largeThreads;    // k_distinct_large: workgroup size (one wave)
+    unsigned largeGrid;       // k_distinct_large: workgroups, at most DISTINCT_LARGE_GRID_MAX (they stride over the chunks)
+    size_t largeLdsBytes;     // k_distinct_large: static LDS per workgroup
+};
+inline DistinctBatchPlan distinct_batch_plan(int nsets) {
+    DistinctBatchPlan P{};
+    P.threads = 64u * DISTINCT_BATCH_WAVES;
+    P.ldsBytes = DISTINCT_BATCH_WAVES * (DISTINCT_MEDIUM_ROW_BYTES + DISTINCT_MEDIUM_DIST_BYTES);
+    P.largeThreads = 64;
+    P.largeLdsBytes = DISTINCT_LARGE_LDS_BYTES;
+    if (nsets <= 0) return P;
+    const long long perGroup = (long long)DISTINCT_SETS_PER_WAVE * DISTINCT_BATCH_WAVES;
+    P.launches = 2;
+    P.grid = (unsigned)std::min<long long>(((long long)nsets + perGroup - 1) / perGroup, DISTINCT_BATCH_GRID_MAX);
+    P.largeGrid = (unsigned)std::min<long long>(((long long)nsets + DISTINCT_LARGE_CHUNK - 1) / DISTINCT_LARGE_CHUNK, DISTINCT_LARGE_GRID_MAX);
+    return P;
+}
+
 // arena of search_proj_core.  occ | q | qdesc go up in ONE copy (occ .. assigned), assigned | count come back in one (assigned .. count + 4);
 // only that head (.. count + 256) has a pinned mirror.  projK = list length of k_proj_topk (PROJ_K).
 struct ProjArena {

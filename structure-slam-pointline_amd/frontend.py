@@ -30,6 +30,9 @@ assert TRI_PAIR_DTYPE.itemsize == 52
 FUSE_JOB_DTYPE = np.dtype([("kf", "<i4"), ("nq", "<i4"), ("qdesc0", "<i4")])      # sslam_fuse_job
 assert FUSE_JOB_DTYPE.itemsize == 12
 
+OBS_DTYPE = np.dtype([("kf", "<i4"), ("row", "<i4")])      # sslam_observation
+assert OBS_DTYPE.itemsize == 8
+
 _lib = None
 
 PIX_GRAY, PIX_RGB, PIX_BGR, PIX_RGBA, PIX_BGRA = 0, 1, 2, 3, 4      # SSLAM_PIX_* (include/sslam_frontend.h)
@@ -262,6 +265,16 @@ class Context:
         best = np.full(len(ptr) - 1, -2, np.int32)
         _chk(lib().sslam_distinctive_descriptors(self.h, _p(desc), _p(ptr), len(ptr) - 1, _p(best)))
         return best
+
+    def distinctive_descriptors_batch_dev(self, d_desc, d_n, cap, nkeyframes, d_obs, nobs, d_ptr, nsets, d_best, d_median=None, d_kf_bad=None,
+                                          d_out_desc=None, d_out_row=None, nout=0, stream=None):
+        """sslam_distinctive_descriptors_batch_dev on device tensors / pointers: set s owns the entries d_obs[d_ptr[s] .. d_ptr[s+1]) (OBS_DTYPE rows on the
+        device: keyframe slot, feature row) of the pool d_desc / d_n [/ d_kf_bad]; d_best [nsets] int32 receives the entry position of the chosen
+        descriptor (-1: no admissible entry, -2: refused), d_median [nsets] int32 its median; a set with a choice copies the 32 bytes to row
+        d_out_row[s] (None: s) of d_out_desc [nout, 32]; enqueues on `stream` (None: the context's) and returns without synchronising"""
+        _chk(lib().sslam_distinctive_descriptors_batch_dev(self.h, _p(d_desc), _p(d_n), int(cap), int(nkeyframes), _p(d_kf_bad), _p(d_obs), int(nobs),
+                                                           _p(d_ptr), int(nsets), _p(d_best), _p(d_median), _p(d_out_desc), _p(d_out_row), int(nout),
+                                                           C.c_void_p(stream or 0)))
 
     def frame_upload(self, kind, feats, desc, uright=None, bounds=(0.0, 640.0, 0.0, 480.0)):
         return Frame(self, kind=kind, feats=feats, desc=desc, uright=uright, bounds=bounds)
