@@ -173,6 +173,9 @@ namespace sslam {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// the count of a device-resident slot, clamped to its capacity: the counts are device data that nothing has checked, the capacity is the allocation
+template <class Index> __device__ __forceinline__ int slot_count(const int* n, Index slot, int cap) { return min(max(n[slot], 0), cap); }
+
 // Workgroups are handed to the eight XCDs round-robin (linear id % 8).  With one workgroup per frame a batch whose content
 // repeats with a period of 8 (or drifts slowly) would give every XCD the same kind of frame and the kernel would last as long
 // as the heaviest kind.  Rotating the assignment inside each group of eight frames by a digit sum of the group index gives every

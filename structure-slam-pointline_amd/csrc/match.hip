@@ -6,7 +6,9 @@
 // The path is integer/bitwise: v_bcnt popcounts on 8x u32 XORs, wave-wide min
 // reductions with the tie-break order carried in the key; the knn-2 of a batch alone runs on the matrix cores (match_knn.h).
 // Which kernel a call launches depends on its sizes alone: the rules are the pure host functions of match_plan.h, and an entry
-// point reads as validate, lock, lay out, stage, switch on the plan's form with one launch per case, copy back.
+// point reads as validate, lock, lay out, stage, switch on the plan's form with one launch per case, copy back.  The batches that keep
+// their rows in LDS or in global memory share one plan (match_plan.h: batch_plan) and one launch path (launch_batch); the alignment and
+// size rules of device-resident batches are the named checks of match_check.h.
 #include "common.h"
 #include "match_plan.h"
 #include "match_check.h"
@@ -29,6 +31,16 @@ static hipStream_t pick(sslam_ctx* c, void* s) { return s ? (hipStream_t)s : c->
 // a launch with more dynamic LDS than the default maximum has to be allowed per kernel
 static int allow_dynamic_lds(const void* kernel, size_t bytes) {
     if (bytes > DYNAMIC_LDS_DEFAULT_MAX) SSLAM_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return SSLAM_OK;
+}
+// the one launch of a batch_plan (match_plan.h): the kernel's <true> instantiation with the rows in dynamic LDS, or <false> on global memory
+template <class Args>
+static int launch_batch(sslam_ctx* ctx, const char* name, void (*lds)(Args), void (*global)(Args), const BatchPlan& P, unsigned grid, hipStream_t st, const Args& A) {
+    const bool inLds = P.form == BatchForm::Lds;
+    int rc;
+    if (inLds && (rc = allow_dynamic_lds((const void*)lds, P.ldsBytes))) return rc;
+    sslam::ProfScope _ps(ctx, name, st);
+    hipLaunchKernelGGL(inLds ? lds : global, dim3(grid), dim3(P.threads), P.ldsBytes, st, A);
     return SSLAM_OK;
 }
 
@@ -116,7 +128,7 @@ extern "C" int sslam_orb_search_for_initialization_batch_dev(sslam_ctx* ctx,
         const sslam_keypoint* d_kp2, const uint8_t* d_desc2, const int32_t* d_n2,
         int cap, int npairs, float* d_prev, int32_t* d_m12, int32_t* d_nm,
         int window, float nnratio, int checkOri, const float bounds[4], void* stream) {
-    if (!ctx || !d_kp1 || !d_desc1 || !d_kp2 || !d_desc2 || !d_n1 || !d_n2 || !d_prev || !d_m12 || !d_nm || cap <= 0 || cap >= (1 << 19) || npairs <= 0 || !bounds) {
+    if (!ctx || !d_kp1 || !d_desc1 || !d_kp2 || !d_desc2 || !d_n1 || !d_n2 || !d_prev || !d_m12 || !d_nm || cap <= 0 || !rows_in_range(cap) || npairs <= 0 || !bounds) {
         set_error("sslam_orb_search_for_initialization_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);      // scratch buffers and profile records are shared state
@@ -165,7 +177,7 @@ extern "C" int sslam_orb_search_for_initialization(sslam_ctx* ctx,
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     const int cap = std::max(std::max(n1, n2), 1);
-    if (cap >= (1 << 19)) { set_error("too many keypoints"); return SSLAM_ERR_UNSUPPORTED; }
+    if (cap >= MAX_ROWS) { set_error("too many keypoints"); return SSLAM_ERR_UNSUPPORTED; }
     hipStream_t st = ctx->stream;
     const size_t kb = sizeof(sslam_keypoint) * (size_t)cap, db = 32 * (size_t)cap;
     int rc;
@@ -307,7 +319,7 @@ extern "C" int sslam_search_by_projection(sslam_ctx* ctx, int kind, int mode, co
                                           const float* uright, const uint8_t* occupied, const sslam_proj_query* queries, const uint8_t* qdesc, int nq,
                                           float nnratio, int th_dist, int check_orientation, int32_t* assigned_out, int* nmatches_out) {
     if (!ctx || (kind != 0 && kind != 1) || (mode != 0 && mode != 1) || (kind == 1 && mode == 1 && check_orientation) || n < 0 || nq < 0 || !nmatches_out || !bounds ||
-        (n > 0 && (!feats || !desc || !assigned_out)) || (nq > 0 && (!queries || !qdesc)) || n >= (1 << 19)) {
+        (n > 0 && (!feats || !desc || !assigned_out)) || (nq > 0 && (!queries || !qdesc)) || n >= MAX_ROWS) {
         set_error("sslam_search_by_projection: invalid arguments"); return SSLAM_ERR_INVALID;
     }
     *nmatches_out = 0;
@@ -344,10 +356,9 @@ extern "C" int sslam_search_by_projection_batch_dev(sslam_ctx* ctx, int kind, in
         const float* d_uright, const uint8_t* d_occupied,
         const sslam_proj_query* d_queries, const uint8_t* d_qdesc, const int32_t* d_nq, int qcap,
         float nnratio, int th_dist, int check_orientation, int32_t* d_assigned, int32_t* d_nmatches, void* stream) {
-    const uintptr_t align4 = (uintptr_t)d_feats | (uintptr_t)d_n | (uintptr_t)d_uright | (uintptr_t)d_queries | (uintptr_t)d_nq | (uintptr_t)d_assigned | (uintptr_t)d_nmatches;
-    const uintptr_t align16 = (uintptr_t)d_desc | (uintptr_t)d_qdesc;      // descriptor rows are read as two 16-byte words
-    if (!ctx || (kind != 0 && kind != 1) || (mode != 0 && mode != 1) || (kind == 1 && mode == 1 && check_orientation) || cap < 0 || cap >= (1 << 19) || qcap < 0 ||
-        nframes < 0 || !bounds || !d_feats || !d_desc || !d_n || !d_queries || !d_qdesc || !d_nq || !d_assigned || !d_nmatches || (align4 & 3) || (align16 & 15)) {
+    if (!ctx || (kind != 0 && kind != 1) || (mode != 0 && mode != 1) || (kind == 1 && mode == 1 && check_orientation) || !rows_in_range(cap) || qcap < 0 ||
+        nframes < 0 || !bounds || !d_feats || !d_desc || !d_n || !d_queries || !d_qdesc || !d_nq || !d_assigned || !d_nmatches ||
+        !all_aligned<4>(d_feats, d_n, d_uright, d_queries, d_nq, d_assigned, d_nmatches) || !all_aligned<16>(d_desc, d_qdesc)) {      // descriptor rows are read as two 16-byte words
         set_error("sslam_search_by_projection_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
     if (nframes == 0) return SSLAM_OK;
@@ -409,7 +420,7 @@ template <class T, void (*Destroy)(T*)> struct HandleGuard {
 
 extern "C" int sslam_frame_upload(sslam_ctx* ctx, int kind, const void* feats, const uint8_t* desc, int n, const float* uright, const float bounds[4],
                                   sslam_frame** out) {
-    if (!ctx || !out || (kind != 0 && kind != 1) || n < 0 || n >= (1 << 19) || !bounds || (n > 0 && (!feats || !desc))) {
+    if (!ctx || !out || (kind != 0 && kind != 1) || !rows_in_range(n) || !bounds || (n > 0 && (!feats || !desc))) {
         set_error("sslam_frame_upload: invalid arguments"); return SSLAM_ERR_INVALID;
     }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -611,10 +622,9 @@ extern "C" int sslam_distinctive_descriptors_batch_dev(sslam_ctx* ctx,
         const sslam_observation* d_obs, int nobs, const int32_t* d_ptr, int nsets,
         int32_t* d_best, int32_t* d_median,
         uint8_t* d_out_desc, const int32_t* d_out_row, int nout, void* stream) {
-    const uintptr_t align4 = (uintptr_t)d_n | (uintptr_t)d_obs | (uintptr_t)d_ptr | (uintptr_t)d_best | (uintptr_t)d_median | (uintptr_t)d_out_row;
     if (!ctx || !d_desc || !d_n || !d_ptr || !d_best || (nobs > 0 && !d_obs) || (d_out_row && !d_out_desc) ||
-        cap < 0 || cap >= (1 << 19) || nkeyframes < 0 || nobs < 0 || nsets < 0 || nout < 0 || (long long)nkeyframes * (long long)cap >= (1ll << 31) ||
-        (align4 & 3) || (((uintptr_t)d_desc | (uintptr_t)d_out_desc) & 15)) {      // descriptor rows are read and written as two 16-byte words
+        !rows_in_range(cap) || nkeyframes < 0 || nobs < 0 || nsets < 0 || nout < 0 || !fits_31_bits(nkeyframes, cap) ||
+        !all_aligned<4>(d_n, d_obs, d_ptr, d_best, d_median, d_out_row) || !all_aligned<16>(d_desc, d_out_desc)) {      // descriptor rows are read and written as two 16-byte words
         set_error("sslam_distinctive_descriptors_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
     if (nsets == 0) return SSLAM_OK;
@@ -674,16 +684,16 @@ extern "C" int sslam_fuse_search_batch_dev(sslam_ctx* ctx, int kind, int chi2_mo
         const sslam_proj_query* d_queries, int qcap, const uint8_t* d_qdesc, int nqdesc,
         const sslam_fuse_job* d_jobs, int njobs,
         int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_nfound, void* stream) {
-    const uintptr_t align4 = (uintptr_t)d_feats | (uintptr_t)d_uright | (uintptr_t)d_n | (uintptr_t)d_queries | (uintptr_t)d_jobs | (uintptr_t)d_best_idx |
-                             (uintptr_t)d_best_dist | (uintptr_t)d_nfound;
     if (!ctx || (kind != 0 && kind != 1) || (chi2_mode != 0 && chi2_mode != 1) || (chi2_mode == 1 && (kind != 0 || !inv_level_sigma2 || nlevels < 1 || nlevels > 64)) ||
         !d_feats || !d_desc || !d_n || !bounds || !d_queries || !d_qdesc || !d_jobs || !d_best_idx || !d_best_dist || !d_nfound ||
-        cap < 0 || cap >= (1 << 19) || qcap < 0 || nkeyframes < 0 || njobs < 0 || nqdesc < 0 || (long long)njobs * (long long)qcap >= (1ll << 31) ||
-        (align4 & 3) || (((uintptr_t)d_desc | (uintptr_t)d_qdesc) & 15)) {      // descriptor rows are read as two 16-byte words
+        !rows_in_range(cap) || qcap < 0 || nkeyframes < 0 || njobs < 0 || nqdesc < 0 || !fits_31_bits(njobs, qcap) ||
+        !all_aligned<4>(d_feats, d_uright, d_n, d_queries, d_jobs, d_best_idx, d_best_dist, d_nfound) || !all_aligned<16>(d_desc, d_qdesc)) {      // descriptor rows are read as two 16-byte words
         set_error("sslam_fuse_search_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
-    const FuseBatchPlan P = fuse_batch_plan(cap, qcap, njobs);      // match_plan.h: the keyframe's geometry in LDS or in global memory, by the row capacity alone
-    if (P.grid >= (1ull << 31)) { set_error("sslam_fuse_search_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID; }
+    const BatchPlan P = batch_plan(FUSE_BATCH_ROW_BYTES, cap);      // match_plan.h: the keyframe's geometry in LDS or in global memory, by the row capacity alone
+    const unsigned chunks = fuse_batch_chunks(qcap);
+    const unsigned long long grid = fuse_batch_grid(njobs, qcap);      // one workgroup per (job, chunk of queries), job-major
+    if (grid >= (1ull << 31)) { set_error("sslam_fuse_search_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID; }
     if (njobs == 0) return SSLAM_OK;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
@@ -692,28 +702,13 @@ extern "C" int sslam_fuse_search_batch_dev(sslam_ctx* ctx, int kind, int chi2_mo
     A.chi2 = chi2_mode; A.feats = d_feats; A.desc = d_desc; A.uright = d_uright; A.n = d_n; A.cap = cap; A.nkeyframes = nkeyframes;
     A.minX = bounds[0]; A.maxX = bounds[1]; A.minY = bounds[2]; A.maxY = bounds[3];
     A.nlevels = chi2_mode ? nlevels : 0;
-    A.q = d_queries; A.qcap = qcap; A.qdesc = d_qdesc; A.nqdesc = nqdesc; A.jobs = d_jobs; A.chunks = P.chunks;
+    A.q = d_queries; A.qcap = qcap; A.qdesc = d_qdesc; A.nqdesc = nqdesc; A.jobs = d_jobs; A.chunks = chunks;
     A.bestIdx = d_best_idx; A.bestDist = d_best_dist; A.nfound = d_nfound;
     for (int i = 0; i < 64; ++i) A.invSigma2[i] = (chi2_mode && i < nlevels) ? inv_level_sigma2[i] : 0.f;
-    const dim3 grid((unsigned)P.grid), block(P.threads);
-    switch (P.form) {
-    case FuseBatchForm::Lds: {
-        int rc;
-        if ((rc = allow_dynamic_lds(kind == 0 ? (const void*)k_fuse_search_batch<0, true> : (const void*)k_fuse_search_batch<1, true>, P.ldsBytes))) return rc;
-        SSLAM_HIP(hipMemsetAsync(d_nfound, 0, sizeof(int32_t) * (size_t)njobs, st));      // every workgroup ADDS its chunk's count; a skipped job's chunk 0 stores -1
-        sslam::ProfScope _ps(ctx, "k_fuse_search_batch", st);
-        if (kind == 0) hipLaunchKernelGGL((k_fuse_search_batch<0, true>), grid, block, P.ldsBytes, st, A);
-        else hipLaunchKernelGGL((k_fuse_search_batch<1, true>), grid, block, P.ldsBytes, st, A);
-        break;
-    }
-    case FuseBatchForm::Global: {
-        SSLAM_HIP(hipMemsetAsync(d_nfound, 0, sizeof(int32_t) * (size_t)njobs, st));
-        sslam::ProfScope _ps(ctx, "k_fuse_search_batch", st);
-        if (kind == 0) hipLaunchKernelGGL((k_fuse_search_batch<0, false>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((k_fuse_search_batch<1, false>), grid, block, 0, st, A);
-        break;
-    }
-    }
+    SSLAM_HIP(hipMemsetAsync(d_nfound, 0, sizeof(int32_t) * (size_t)njobs, st));      // every workgroup ADDS its chunk's count; a skipped job's chunk 0 stores -1
+    int rc;
+    if ((rc = kind == 0 ? launch_batch(ctx, "k_fuse_search_batch", k_fuse_search_batch<0, true>, k_fuse_search_batch<0, false>, P, (unsigned)grid, st, A)
+                        : launch_batch(ctx, "k_fuse_search_batch", k_fuse_search_batch<1, true>, k_fuse_search_batch<1, false>, P, (unsigned)grid, st, A))) return rc;
     SSLAM_HIP(hipGetLastError());
     return SSLAM_OK;
 }
@@ -784,35 +779,22 @@ extern "C" int sslam_orb_search_for_triangulation_batch_dev(sslam_ctx* ctx,
         const float* scale_factors, const float* level_sigma2, int nlevels,
         int only_stereo, int check_orientation,
         int32_t* d_matches12, int32_t* d_nmatches, void* stream) {
-    const uintptr_t align4 = (uintptr_t)d_kp | (uintptr_t)d_node | (uintptr_t)d_uright | (uintptr_t)d_n | (uintptr_t)d_pairs | (uintptr_t)d_matches12 | (uintptr_t)d_nmatches;
     if (!ctx || !d_kp || !d_desc || !d_node || !d_n || !d_pairs || !d_matches12 || !d_nmatches || !scale_factors || !level_sigma2 ||
-        cap < 0 || cap >= (1 << 19) || nkeyframes < 0 || npairs < 0 || nlevels < 1 || nlevels > 64 || (long long)npairs * (long long)cap >= (1ll << 31) ||
-        (align4 & 3) || ((uintptr_t)d_desc & 15)) {      // descriptor rows are read as two 16-byte words
+        !rows_in_range(cap) || nkeyframes < 0 || npairs < 0 || nlevels < 1 || nlevels > 64 || !fits_31_bits(npairs, cap) ||
+        !all_aligned<4>(d_kp, d_node, d_uright, d_n, d_pairs, d_matches12, d_nmatches) || !all_aligned<16>(d_desc)) {      // descriptor rows are read as two 16-byte words
         set_error("sslam_orb_search_for_triangulation_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
     if (npairs == 0) return SSLAM_OK;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
-    const TriBatchPlan P = tri_batch_plan(cap, npairs);      // match_plan.h: keyframe 2 in LDS or in global memory, by the row capacity alone
+    const BatchPlan P = batch_plan(TRI_BATCH_ROW_BYTES, cap);      // match_plan.h: keyframe 2 in LDS or in global memory, by the row capacity alone
     TriBatchArgs A;
     A.kp = d_kp; A.desc = d_desc; A.node = d_node; A.isFree = d_free; A.uright = d_uright; A.n = d_n; A.cap = cap; A.nkeyframes = nkeyframes;
     A.pairs = d_pairs; A.nlevels = nlevels; A.onlyStereo = only_stereo; A.checkOri = check_orientation; A.m12 = d_matches12; A.nmatches = d_nmatches;
     for (int i = 0; i < 64; ++i) { A.scale2[i] = i < nlevels ? scale_factors[i] : 0.f; A.sigma2_2[i] = i < nlevels ? level_sigma2[i] : 0.f; }
-    switch (P.form) {
-    case TriBatchForm::Lds: {
-        int rc;
-        if ((rc = allow_dynamic_lds((const void*)k_tri_search_batch<true>, P.ldsBytes))) return rc;
-        sslam::ProfScope _ps(ctx, "k_tri_search_batch", st);
-        hipLaunchKernelGGL(k_tri_search_batch<true>, dim3(P.grid), dim3(P.threads), P.ldsBytes, st, A);
-        break;
-    }
-    case TriBatchForm::Global: {
-        sslam::ProfScope _ps(ctx, "k_tri_search_batch", st);
-        hipLaunchKernelGGL(k_tri_search_batch<false>, dim3(P.grid), dim3(P.threads), 0, st, A);
-        break;
-    }
-    }
+    int rc;
+    if ((rc = launch_batch(ctx, "k_tri_search_batch", k_tri_search_batch<true>, k_tri_search_batch<false>, P, (unsigned)npairs, st, A))) return rc;      // one workgroup per pair
     SSLAM_HIP(hipGetLastError());
     return SSLAM_OK;
 }
@@ -898,9 +880,8 @@ extern "C" int sslam_bow_transform(sslam_ctx* ctx, const sslam_vocab* vocab, con
 // ---- the descent for B frames that are already on the device (the batch extractors' descriptor buffer), asynchronous: one launch, no scratch
 extern "C" int sslam_bow_transform_batch_dev(sslam_ctx* ctx, const sslam_vocab* vocab, const uint8_t* d_desc, const int32_t* d_n, int cap, int nframes,
                                              int levelsup, int32_t* d_word, double* d_weight, int32_t* d_node, void* stream) {
-    const uintptr_t align4 = (uintptr_t)d_n | (uintptr_t)d_word | (uintptr_t)d_node;
-    if (!ctx || !vocab || vocab->ctx != ctx || !d_desc || !d_n || !d_node || cap < 0 || nframes < 0 || levelsup < 0 || (long long)nframes * (long long)cap >= (1ll << 31) ||
-        ((uintptr_t)d_desc & 15) || (align4 & 3) || ((uintptr_t)d_weight & 7)) {
+    if (!ctx || !vocab || vocab->ctx != ctx || !d_desc || !d_n || !d_node || cap < 0 || nframes < 0 || levelsup < 0 || !fits_31_bits(nframes, cap) ||
+        !all_aligned<16>(d_desc) || !all_aligned<4>(d_n, d_word, d_node) || !all_aligned<8>(d_weight)) {
         set_error("sslam_bow_transform_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
     const int rows = nframes * cap;
@@ -921,11 +902,10 @@ extern "C" int sslam_orb_search_by_bow_batch_dev(sslam_ctx* ctx,
         const sslam_keypoint* d_f_kp, const uint8_t* d_f_desc, const int32_t* d_f_node, const int32_t* d_nf, int cap, int nframes,
         const int32_t* d_pair_kf, const int32_t* d_pair_f, int npairs,
         float nnratio, int check_orientation, int32_t* d_assigned, int32_t* d_nmatches, void* stream) {
-    const uintptr_t align4 = (uintptr_t)d_kf_kp | (uintptr_t)d_kf_node | (uintptr_t)d_nkf | (uintptr_t)d_f_kp | (uintptr_t)d_f_node | (uintptr_t)d_nf | (uintptr_t)d_pair_kf |
-                             (uintptr_t)d_pair_f | (uintptr_t)d_assigned | (uintptr_t)d_nmatches;
-    const uintptr_t align16 = (uintptr_t)d_kf_desc | (uintptr_t)d_f_desc;      // descriptor rows are read as two 16-byte words
     if (!ctx || !d_kf_kp || !d_kf_desc || !d_kf_node || !d_kf_valid || !d_nkf || !d_f_kp || !d_f_desc || !d_f_node || !d_nf || !d_assigned || !d_nmatches ||
-        kfcap < 0 || kfcap >= (1 << 19) || cap < 0 || cap >= (1 << 19) || nkeyframes < 0 || nframes < 0 || npairs < 0 || (align4 & 3) || (align16 & 15) ||
+        !rows_in_range(kfcap) || !rows_in_range(cap) || nkeyframes < 0 || nframes < 0 || npairs < 0 ||
+        !all_aligned<4>(d_kf_kp, d_kf_node, d_nkf, d_f_kp, d_f_node, d_nf, d_pair_kf, d_pair_f, d_assigned, d_nmatches) ||
+        !all_aligned<16>(d_kf_desc, d_f_desc) ||      // descriptor rows are read as two 16-byte words
         (!d_pair_kf && nkeyframes != npairs) || (!d_pair_f && nframes != npairs)) {
         set_error("sslam_orb_search_by_bow_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
@@ -933,25 +913,13 @@ extern "C" int sslam_orb_search_by_bow_batch_dev(sslam_ctx* ctx,
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
-    const BowBatchPlan P = bow_batch_plan(cap, npairs);      // match_plan.h: the frame side in LDS or in global memory, by the row capacity alone
+    const BatchPlan P = batch_plan(BOW_BATCH_ROW_BYTES, cap);      // match_plan.h: the frame side in LDS or in global memory, by the row capacity alone
     BowBatchArgs A;
     A.kpKF = d_kf_kp; A.dKF = d_kf_desc; A.nodeKF = d_kf_node; A.validKF = d_kf_valid; A.nKF = d_nkf; A.kfcap = kfcap; A.nkeyframes = nkeyframes;
     A.kpF = d_f_kp; A.dF = d_f_desc; A.nodeF = d_f_node; A.nF = d_nf; A.cap = cap; A.nframes = nframes;
     A.pairKF = d_pair_kf; A.pairF = d_pair_f; A.nnratio = nnratio; A.checkOri = check_orientation; A.assigned = d_assigned; A.nmatches = d_nmatches;
-    switch (P.form) {
-    case BowBatchForm::Lds: {
-        int rc;
-        if ((rc = allow_dynamic_lds((const void*)k_search_bow_batch<true>, P.ldsBytes))) return rc;
-        sslam::ProfScope _ps(ctx, "k_search_bow_batch", st);
-        hipLaunchKernelGGL(k_search_bow_batch<true>, dim3(P.grid), dim3(P.threads), P.ldsBytes, st, A);
-        break;
-    }
-    case BowBatchForm::Global: {
-        sslam::ProfScope _ps(ctx, "k_search_bow_batch", st);
-        hipLaunchKernelGGL(k_search_bow_batch<false>, dim3(P.grid), dim3(P.threads), 0, st, A);
-        break;
-    }
-    }
+    int rc;
+    if ((rc = launch_batch(ctx, "k_search_bow_batch", k_search_bow_batch<true>, k_search_bow_batch<false>, P, (unsigned)npairs, st, A))) return rc;      // one workgroup per pair
     SSLAM_HIP(hipGetLastError());
     return SSLAM_OK;
 }

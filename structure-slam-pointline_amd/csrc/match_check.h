@@ -1,8 +1,9 @@
-// The argument check of the CSR lists that matcher entry points take (match.hip): vocabulary nodes, observation sets, children.  Host code and no
-// HIP in here: tests/sim/host_checks.cpp compiles it with a plain host compiler under the sanitizers and supplies its own set_error.
+// The argument checks that matcher entry points share (match.hip): the CSR lists of vocabulary nodes, observation sets and children, and the
+// alignment and size rules of device-resident batches.  Host code and no HIP in here: tests/sim/host_checks.cpp compiles it with a plain host compiler under the sanitizers and supplies its own set_error.
 #pragma once
 #include <cstdint>
 #include "../../include/sslam_frontend.h"
+#include "match_plan.h"
 
 namespace sslam {
 
@@ -17,5 +18,15 @@ inline int check_csr(const char* fn, const char* what, const int32_t* ptr, int n
     if (idx) for (int i = 0; i < ptr[nnodes]; ++i) if (idx[i] < 0 || idx[i] >= limit) { set_error("%s: %s index out of range", fn, what); return SSLAM_ERR_INVALID; }
     return SSLAM_OK;
 }
+
+// Every one of these pointers is a multiple of N bytes (a power of two); a null pointer is aligned -- whether it may be null is the caller's rule.
+template <unsigned N, class... Ptr> inline bool all_aligned(const Ptr*... p) {
+    static_assert(N && !(N & (N - 1)), "a power of two");
+    return ((((uintptr_t)p) | ... | (uintptr_t)0) & (N - 1)) == 0;
+}
+// A row capacity whose indices fit the packed reduction keys (match_plan.h: MAX_ROWS); 0 is in range, an entry point that needs rows says so itself.
+inline bool rows_in_range(int cap) { return cap >= 0 && cap < MAX_ROWS; }
+// slots * cap rows (or jobs * queries) are indexed with a signed 32-bit int on the device
+inline bool fits_31_bits(int slots, int cap) { return (long long)slots * (long long)cap < (1ll << 31); }
 
 }  // namespace sslam

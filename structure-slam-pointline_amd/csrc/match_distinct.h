@@ -31,7 +31,7 @@ __device__ __forceinline__ int distinct_row(const DistinctArgs& A, int idx) {
     const int kf = A.obs[idx].kf, row = A.obs[idx].row;
     if ((unsigned)kf >= (unsigned)A.nkeyframes) return -1;
     if (A.bad && A.bad[kf]) return -1;
-    const int n = min(max(A.n[kf], 0), A.cap);
+    const int n = slot_count(A.n, kf, A.cap);
     return (unsigned)row < (unsigned)n ? kf * A.cap + row : -1;
 }
 // THE compaction: position of this lane's entry among the admissible entries of the wave's 64, in entry order (ballot + prefix popcount), and their number.

@@ -101,12 +101,12 @@ __global__ __launch_bounds__(64) void k_fuse_search(FuseArgs A) {
 }
 
 // ------------------------------------------------------------------ Fuse / SearchBySim3 candidate search of a batch (sslam_fuse_search_batch_dev)
-// The same search for jobs (keyframe slot, block of queries) on one device-resident pool of keyframe slots.  One workgroup of FUSE_BATCH_WAVES waves
+// The same search for jobs (keyframe slot, block of queries) on one device-resident pool of keyframe slots.  One workgroup of BATCH_WAVES waves
 // per (job, chunk of FUSE_BATCH_CHUNK queries), the grid flattened job-major (match_plan.h).  Where k_fuse_search recomputes every feature's grid cell
 // for every (query, feature) pair and reads 28 or 68 bytes of a row to test 12, the workgroup stages the keyframe's GEOMETRY once, as four arrays of
 // cap words in dynamic LDS (FUSE_BATCH_ROW_BYTES per row): x, y, uright, octave of a keypoint, pt_x, pt_y, angle, octave of a keyline.  A keypoint in
 // no grid cell is staged with x = NaN: every window test rejects it, which is what the single kernel's first gate does.  Consecutive lanes read
-// consecutive words of one array: no bank conflicts.  Wave w takes the chunk's queries w, w + FUSE_BATCH_WAVES, .. in turn and scans the rows
+// consecutive words of one array: no bank conflicts.  Wave w takes the chunk's queries w, w + BATCH_WAVES, .. in turn and scans the rows
 // lane-parallel; only a row that passed every gate -- a handful of a thousand under a window of 3 x scale -- has its cell computed and its 32-byte
 // descriptor read, from global memory.  fuse_key and wave_min_u64 reduce as in the single kernel.
 // d_nfound: the host zeroes it ahead of the launch; every workgroup adds the candidates of its chunk with ONE agent-scope atomic (none where it found
@@ -126,11 +126,11 @@ struct FuseBatchArgs {
 };
 // kLds: the keyframe's geometry in dynamic LDS; otherwise the scan reads the caller's buffers, with the single kernel's grid gate per row
 template <int kind, bool kLds>
-__global__ __launch_bounds__(64 * FUSE_BATCH_WAVES) void k_fuse_search_batch(FuseBatchArgs A) {
+__global__ __launch_bounds__(64 * BATCH_WAVES) void k_fuse_search_batch(FuseBatchArgs A) {
     extern __shared__ __align__(16) unsigned fsl[];
     __shared__ float invS[64];
     __shared__ int total;
-    constexpr int NT = 64 * FUSE_BATCH_WAVES;
+    constexpr int NT = 64 * BATCH_WAVES;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned j = blockIdx.x / A.chunks, chunk = blockIdx.x - j * A.chunks;
     const sslam_fuse_job J = A.jobs[j];
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(64 * FUSE_BATCH_WAVES) void k_fuse_search_batch(Fus
     }
     const int q0 = (int)chunk * FUSE_BATCH_CHUNK, q1 = min(nq, q0 + FUSE_BATCH_CHUNK);
     if (q0 >= nq) return;                                        // d_nfound[j] keeps the host's 0 where the job has no query
-    const int n = min(max(A.n[J.kf], 0), A.cap);
+    const int n = min(max(A.n[J.kf], 0), A.cap);      // slot_count (common.h), written out: through the helper the capacity is loaded ahead of the count and the LDS forms schedule differently
     const size_t r = (size_t)J.kf * (size_t)A.cap;
     const sslam_keypoint* kps = (const sslam_keypoint*)A.feats + r;
     const sslam_keyline* kls = (const sslam_keyline*)A.feats + r;
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(64 * FUSE_BATCH_WAVES) void k_fuse_search_batch(Fus
     __syncthreads();
     // the scan: no workgroup barrier in here
     int found = 0;
-    for (int iq = q0 + wave; iq < q1; iq += FUSE_BATCH_WAVES) {
+    for (int iq = q0 + wave; iq < q1; iq += BATCH_WAVES) {
         const sslam_proj_query Q = qs[iq];
         unsigned long long b = ~0ull;
         if (Q.valid) {
@@ -292,8 +292,8 @@ __global__ __launch_bounds__(64) void k_tri_search(TriArgs A) {
 
 // ------------------------------------------------------------------ SearchForTriangulation of a batch (sslam_orb_search_for_triangulation_batch_dev)
 // The same matcher on per-feature NODE IDS instead of CSR lists, for pairs of keyframe slots of one device-resident pool: no sort, no scratch, no
-// traffic between workgroups.  One workgroup of TRI_BATCH_WAVES waves per pair (match_plan.h).  The queries do not interact, so there is no chain and
-// no ownership of nodes: wave w takes the keyframe-1 rows [64 (w + k TRI_BATCH_WAVES), +64), k = 0, 1, .., one row per lane, ballots the rows that
+// traffic between workgroups.  One workgroup of BATCH_WAVES waves per pair (match_plan.h).  The queries do not interact, so there is no chain and
+// no ownership of nodes: wave w takes the keyframe-1 rows [64 (w + k BATCH_WAVES), +64), k = 0, 1, .., one row per lane, ballots the rows that
 // take part (tri_side_ok, node id >= 0) and serves them in bit order; for each it scans the keyframe-2 rows lane-parallel for rows of that node and
 // reduces tri_key over tri_candidate.  The position in the key is the keyframe-2 row index: inside a node the list FeatureVector::addFeature builds is
 // in ascending feature index, so the later list entry is the higher row.  The lane that loaded a row writes its match (or -1) once, behind the
@@ -311,20 +311,20 @@ constexpr unsigned TRI_PACK_FREE = 0x100u, TRI_PACK_STEREO = 0x200u;      // bes
 // kLds: keyframe 2 of the pair in dynamic LDS -- descriptors [2 cap] uint4, node ids [cap], x [cap], y [cap], octave | free | stereo [cap]
 // (TRI_BATCH_ROW_BYTES per row); otherwise the scan reads the caller's buffers
 template <bool kLds>
-__global__ __launch_bounds__(64 * TRI_BATCH_WAVES) void k_tri_search_batch(TriBatchArgs A) {
+__global__ __launch_bounds__(64 * BATCH_WAVES) void k_tri_search_batch(TriBatchArgs A) {
     extern __shared__ __align__(16) unsigned trl[];
     __shared__ float scale2[64], sigma2_2[64];
     __shared__ int hist[HISTO_LENGTH];
     __shared__ int keep[3];
     __shared__ int total;
-    constexpr int NT = 64 * TRI_BATCH_WAVES;
+    constexpr int NT = 64 * BATCH_WAVES;
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const sslam_tri_pair P = A.pairs[p];
     if (P.kf1 < 0 || P.kf1 >= A.nkeyframes || P.kf2 < 0 || P.kf2 >= A.nkeyframes) {      // (uniform over the workgroup, ahead of every barrier)
         if (tid == 0) A.nmatches[p] = 0;
         return;
     }
-    const int n1 = min(max(A.n[P.kf1], 0), A.cap), n2 = min(max(A.n[P.kf2], 0), A.cap);
+    const int n1 = slot_count(A.n, P.kf1, A.cap), n2 = slot_count(A.n, P.kf2, A.cap);
     const size_t r1 = (size_t)P.kf1 * (size_t)A.cap, r2 = (size_t)P.kf2 * (size_t)A.cap;
     const sslam_keypoint* kp1 = A.kp + r1; const uint8_t* d1 = A.desc + r1 * 32; const int* node1 = A.node + r1;
     const uint8_t* free1 = A.isFree ? A.isFree + r1 : nullptr; const float* ur1 = A.uright ? A.uright + r1 : nullptr;
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(64 * TRI_BATCH_WAVES) void k_tri_search_batch(TriBa
     if (A.checkOri) {
         for (int i = tid; i < n1; i += NT) {
             const int m = out[i];
-            if (m >= 0) atomicAdd(&hist[min(max(rot_bin(kp1[i].angle, kp2[m].angle), 0), HISTO_LENGTH - 1)], 1);      // angles of [0, 360) never need the clamp; the histogram index stays in range whatever a row holds
+            if (m >= 0) atomicAdd(&hist[rot_hist_bin(kp1[i].angle, kp2[m].angle)], 1);
         }
         __syncthreads();
         if (tid == 0) three_maxima(hist, keep[0], keep[1], keep[2]);
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(64 * TRI_BATCH_WAVES) void k_tri_search_batch(TriBa
     for (int i = tid; i < n1; i += NT) {
         const int m = out[i];
         if (m < 0) continue;
-        if (A.checkOri && !rot_kept(min(max(rot_bin(kp1[i].angle, kp2[m].angle), 0), HISTO_LENGTH - 1), keep[0], keep[1], keep[2])) { out[i] = -1; continue; }
+        if (A.checkOri && !rot_kept(rot_hist_bin(kp1[i].angle, kp2[m].angle), keep[0], keep[1], keep[2])) { out[i] = -1; continue; }
         ++cnt;
     }
     cnt = wave_sum(cnt);
@@ -424,7 +424,7 @@ __global__ __launch_bounds__(256) void k_bow_transform(const uint8_t* __restrict
     if (i >= (unsigned)n) return;
     if (counts) {
         const unsigned f = i / (unsigned)cap;
-        if ((int)(i - f * (unsigned)cap) >= min(max(counts[f], 0), cap)) return;
+        if ((int)(i - f * (unsigned)cap) >= slot_count(counts, f, cap)) return;
     }
     const uint4 q0 = ((const uint4*)(feat + (size_t)i * 32))[0], q1 = ((const uint4*)(feat + (size_t)i * 32))[1];
     int node = 0, level = 0, nid = 0;

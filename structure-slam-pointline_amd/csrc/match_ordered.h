@@ -817,7 +817,7 @@ __device__ __forceinline__ ProjTopArgs proj_batch_frame(const ProjBatchArgs& B, 
     ProjTopArgs T;
     T.A = B.A;
     ProjArgs& A = T.A;
-    A.n = min(max(B.n[f], 0), B.cap); A.nq = min(max(B.nq[f], 0), B.qcap);
+    A.n = slot_count(B.n, f, B.cap); A.nq = slot_count(B.nq, f, B.qcap);
     A.feats = (const uint8_t*)B.A.feats + r * (B.A.kind == 0 ? sizeof(sslam_keypoint) : sizeof(sslam_keyline));
     A.desc = B.A.desc + r * 32;
     A.uright = B.A.uright ? B.A.uright + r : nullptr;
@@ -900,7 +900,7 @@ __global__ __launch_bounds__(64) void k_search_bow(BowArgs A) {
 
 // ---------------------------------------------------------------- SearchByBoW of a batch (sslam_orb_search_by_bow_batch_dev)
 // The same matcher on per-feature NODE IDS instead of CSR lists, for pairs of device-resident frames: no sort, no scratch, no traffic between
-// workgroups.  One workgroup of BOW_BATCH_WAVES waves per pair (match_plan.h); wave w owns the nodes with node % BOW_BATCH_WAVES == w, so
+// workgroups.  One workgroup of BATCH_WAVES waves per pair (match_plan.h); wave w owns the nodes with node % BATCH_WAVES == w, so
 // every frame row -- it has one node -- is read and written as "taken" by one wave only, and the waves never wait for each other while they walk.
 // A wave walks the keyframe rows in ascending index, 64 node ids per ballot, and takes the rows that are valid and of a node it owns in
 // bit order; for each it scans the frame side for rows of that node that are still free, with the frame index in the reduction key: inside a
@@ -918,19 +918,19 @@ struct BowBatchArgs {
 // kLds: the frame side in dynamic LDS -- descriptors [2 cap] uint4, node ids [cap], live assignment [cap] (BOW_BATCH_ROW_BYTES per row);
 // otherwise descriptors and node ids in the caller's buffers and the live assignment in the pair's output rows
 template <bool kLds>
-__global__ __launch_bounds__(64 * BOW_BATCH_WAVES) void k_search_bow_batch(BowBatchArgs A) {
+__global__ __launch_bounds__(64 * BATCH_WAVES) void k_search_bow_batch(BowBatchArgs A) {
     extern __shared__ __align__(16) unsigned bwl[];
     __shared__ int hist[HISTO_LENGTH];
     __shared__ int keep[3];
     __shared__ int total;
-    constexpr int NT = 64 * BOW_BATCH_WAVES;
+    constexpr int NT = 64 * BATCH_WAVES;
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int k = A.pairKF ? A.pairKF[p] : p, f = A.pairF ? A.pairF[p] : p;
     if (k < 0 || k >= A.nkeyframes || f < 0 || f >= A.nframes) {      // (uniform over the workgroup, ahead of every barrier)
         if (tid == 0) A.nmatches[p] = 0;
         return;
     }
-    const int nkf = min(max(A.nKF[k], 0), A.kfcap), nf = min(max(A.nF[f], 0), A.cap);
+    const int nkf = slot_count(A.nKF, k, A.kfcap), nf = slot_count(A.nF, f, A.cap);
     const size_t rk = (size_t)k * (size_t)A.kfcap, rf = (size_t)f * (size_t)A.cap;
     const sslam_keypoint* kpKF = A.kpKF + rk; const uint8_t* dKF = A.dKF + rk * 32; const int* nodeKF = A.nodeKF + rk; const uint8_t* validKF = A.validKF + rk;
     const sslam_keypoint* kpF = A.kpF + rf;
@@ -953,7 +953,7 @@ __global__ __launch_bounds__(64 * BOW_BATCH_WAVES) void k_search_bow_batch(BowBa
     for (int i0 = 0; i0 < nkf; i0 += 64) {
         const int i = i0 + lane;
         int nd = -1; bool own = false;
-        if (i < nkf) { nd = nodeKF[i]; own = nd >= 0 && validKF[i] != 0 && (nd % BOW_BATCH_WAVES) == wave; }
+        if (i < nkf) { nd = nodeKF[i]; own = nd >= 0 && validKF[i] != 0 && (nd % BATCH_WAVES) == wave; }
         unsigned long long todo = __ballot(own);
         while (todo) {
             const int bit = __ffsll((long long)todo) - 1;
@@ -983,7 +983,7 @@ __global__ __launch_bounds__(64 * BOW_BATCH_WAVES) void k_search_bow_batch(BowBa
     if (A.checkOri) {
         for (int j = tid; j < nf; j += NT) {
             const int a = asg[j];
-            if (a >= 0) atomicAdd(&hist[min(max(rot_bin(kpKF[a].angle, kpF[j].angle), 0), HISTO_LENGTH - 1)], 1);      // angles of [0, 360) never need the clamp; the histogram index stays in range whatever a row holds
+            if (a >= 0) atomicAdd(&hist[rot_hist_bin(kpKF[a].angle, kpF[j].angle)], 1);
         }
         __syncthreads();
         if (tid == 0) three_maxima(hist, keep[0], keep[1], keep[2]);
@@ -992,7 +992,7 @@ __global__ __launch_bounds__(64 * BOW_BATCH_WAVES) void k_search_bow_batch(BowBa
     int cnt = 0;
     for (int j = tid; j < nf; j += NT) {
         int a = asg[j];
-        if (a >= 0 && A.checkOri && !rot_kept(min(max(rot_bin(kpKF[a].angle, kpF[j].angle), 0), HISTO_LENGTH - 1), keep[0], keep[1], keep[2])) a = -1;
+        if (a >= 0 && A.checkOri && !rot_kept(rot_hist_bin(kpKF[a].angle, kpF[j].angle), keep[0], keep[1], keep[2])) a = -1;
         cnt += a >= 0;
         out[j] = a;
     }

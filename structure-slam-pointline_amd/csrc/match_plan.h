@@ -1,7 +1,7 @@
 // Host-side plans of the matcher entry points (match.hip): which kernel a call launches for its sizes, the sizes that follow from
 // that choice (LDS bytes, capacities, grid), and how a staged call lays out its scratch arena.  Pure functions of integers and no HIP
-// in here: tests/sim/match_plan_dump.cpp compiles this header with a plain host compiler and tests/test_match_plan_cpu.py checks both
-// sides of every boundary.  A size rule lives here and nowhere else; the kernels are chosen by arguments alone (no environment).
+// in here: tests/sim/match_plan_dump.cpp compiles this header with a plain host compiler and tests/test_match_plan_cpu.py and the
+// tests/test_*_batch_plan_cpu.py check both sides of every boundary.  A size rule lives here and nowhere else; the kernels are chosen by arguments alone (no environment).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -16,6 +16,13 @@ struct ArenaLayout {
     size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
     size_t size() const { return off; }
 };
+
+// -------------------------------------------------------------- rows of a frame or slot
+// A row index takes ROW_INDEX_BITS bits of a packed reduction key, so a frame or a slot holds fewer than MAX_ROWS rows.  The keys that depend on it:
+// fuse_key / fuse_key_idx (match_independent.h), the knn-2 and SearchForInitialization keys (match_knn.h, match_ordered.h), and through them every
+// frame that sslam_frame_upload admits.
+constexpr int ROW_INDEX_BITS = 19;
+constexpr int MAX_ROWS = 1 << ROW_INDEX_BITS;
 
 // -------------------------------------------------------------- knn-2 of a batch (sslam_hamming_knn2_batch_dev)
 // k_knn2_mfma packs the train tile into 7 bits of its reduction key: 128 tiles of 32 rows, 4096 rows per frame; beyond that xor + popcount
@@ -152,101 +159,52 @@ inline ProjBatchArena proj_batch_arena(int cap, int qcap, int slice, int projK) 
     return a;
 }
 
-// -------------------------------------------------------------- SearchByBoW of a batch (sslam_orb_search_by_bow_batch_dev)
-// One workgroup of BOW_BATCH_WAVES waves per (keyframe slot, frame slot) pair -- k_search_bow_batch; wave w owns the vocabulary nodes with
-// node % BOW_BATCH_WAVES == w.  The form follows the FRAME side's row capacity alone (every pair of a launch runs the same kernel):
-//   Lds     the frame side of the pair sits in the workgroup's LDS: 32 bytes of descriptor, the node id and the live assignment per row,
-//           BOW_BATCH_ROW_BYTES * cap bytes in all, while that is at most BOW_BATCH_LDS_MAX (64 KB: two pairs per compute unit at the bound, three
-//           at 1000 rows); more than DYNAMIC_LDS_DEFAULT_MAX needs the per-kernel opt-in
-//   Global  beyond that: the same kernel reads descriptors and node ids from the caller's buffers and keeps the live assignment in d_assigned
-// No scratch: every byte of a pair's state is in its workgroup's LDS or in the pair's own output rows.
-constexpr int BOW_BATCH_WAVES = 8;
+// -------------------------------------------------------------- rows in LDS or in global memory (the SearchByBoW, SearchForTriangulation and Fuse batches)
+// One workgroup of BATCH_WAVES waves per unit of work, and one rule for where the rows it scans sit.  The form follows the row capacity alone
+// (every workgroup of a launch runs the same kernel):
+//   Lds     the scanned side sits in the workgroup's LDS, rowBytes per row of the capacity, while rowBytes * cap is at most BATCH_LDS_MAX (64 KB: two
+//           workgroups per compute unit at the bound); more than DYNAMIC_LDS_DEFAULT_MAX needs the per-kernel opt-in
+//   Global  beyond that: the same kernel template reads the caller's buffers, with no dynamic LDS
+// No scratch: a workgroup's state is in its LDS, its registers and its own output rows.  What a row holds, and the grid, are the matcher's own (below).
+constexpr int BATCH_WAVES = 8;
+constexpr size_t BATCH_LDS_MAX = 64 * 1024;
+enum class BatchForm { Lds, Global };
+struct BatchPlan {
+    BatchForm form;
+    size_t ldsBytes;          // dynamic LDS per workgroup (0: Global)
+    int ldsOptIn;             // ldsBytes is more than a launch may ask for without hipFuncSetAttribute
+    unsigned threads;         // workgroup size
+};
+inline BatchPlan batch_plan(int rowBytes, int cap) {
+    BatchPlan P{};
+    const size_t lds = (size_t)rowBytes * (size_t)cap;
+    P.form = lds <= BATCH_LDS_MAX ? BatchForm::Lds : BatchForm::Global;
+    P.ldsBytes = P.form == BatchForm::Lds ? lds : 0;
+    P.ldsOptIn = P.ldsBytes > DYNAMIC_LDS_DEFAULT_MAX ? 1 : 0;
+    P.threads = 64u * BATCH_WAVES;
+    return P;
+}
+
+// SearchByBoW of a batch (sslam_orb_search_by_bow_batch_dev, k_search_bow_batch): one workgroup per (keyframe slot, frame slot) pair, grid = npairs;
+// wave w owns the vocabulary nodes with node % BATCH_WAVES == w.  The FRAME side's capacity decides; a row is 32 bytes of descriptor, the node id and
+// the live assignment (three pairs per compute unit at 1000 rows).  The Global form keeps the live assignment in d_assigned.
 constexpr int BOW_BATCH_ROW_BYTES = 40;
-constexpr size_t BOW_BATCH_LDS_MAX = 64 * 1024;
-enum class BowBatchForm { Lds, Global };
-struct BowBatchPlan {
-    BowBatchForm form;
-    size_t ldsBytes;          // dynamic LDS per workgroup (0: Global)
-    int ldsOptIn;             // ldsBytes is more than a launch may ask for without hipFuncSetAttribute
-    unsigned threads;         // workgroup size
-    unsigned grid;            // workgroups: one per pair
-};
-inline BowBatchPlan bow_batch_plan(int cap, int npairs) {
-    BowBatchPlan P{};
-    const size_t lds = (size_t)BOW_BATCH_ROW_BYTES * (size_t)cap;
-    P.form = lds <= BOW_BATCH_LDS_MAX ? BowBatchForm::Lds : BowBatchForm::Global;
-    P.ldsBytes = P.form == BowBatchForm::Lds ? lds : 0;
-    P.ldsOptIn = P.ldsBytes > DYNAMIC_LDS_DEFAULT_MAX ? 1 : 0;
-    P.threads = 64u * BOW_BATCH_WAVES;
-    P.grid = (unsigned)npairs;
-    return P;
-}
 
-// -------------------------------------------------------------- SearchForTriangulation of a batch (sslam_orb_search_for_triangulation_batch_dev)
-// One workgroup of TRI_BATCH_WAVES waves per pair of keyframe slots -- k_tri_search_batch; the waves share the keyframe-1 rows in turns of 64 (the
-// queries do not interact).  The form follows the row capacity alone (every pair of a launch runs the same kernel):
-//   Lds     keyframe 2 of the pair sits in the workgroup's LDS: 32 bytes of descriptor, the node id, x, y and octave | free | stereo in one word per
-//           row, TRI_BATCH_ROW_BYTES * cap bytes in all, while that is at most TRI_BATCH_LDS_MAX (64 KB, the SearchByBoW batch's bound: two pairs per
-//           compute unit at the bound, three at 1000 rows); more than DYNAMIC_LDS_DEFAULT_MAX needs the per-kernel opt-in
-//   Global  beyond that: the same kernel scans the caller's buffers
-// No scratch: a pair's state is in its workgroup's LDS, its registers and the pair's own output rows.
-constexpr int TRI_BATCH_WAVES = 8;
+// SearchForTriangulation of a batch (sslam_orb_search_for_triangulation_batch_dev, k_tri_search_batch): one workgroup per pair of keyframe slots,
+// grid = npairs; the waves share the keyframe-1 rows in turns of 64 (the queries do not interact).  KEYFRAME 2 is staged; a row is 32 bytes of
+// descriptor, the node id, x, y and octave | free | stereo in one word (three pairs per compute unit at 1000 rows).
 constexpr int TRI_BATCH_ROW_BYTES = 48;
-constexpr size_t TRI_BATCH_LDS_MAX = 64 * 1024;
-enum class TriBatchForm { Lds, Global };
-struct TriBatchPlan {
-    TriBatchForm form;
-    size_t ldsBytes;          // dynamic LDS per workgroup (0: Global)
-    int ldsOptIn;             // ldsBytes is more than a launch may ask for without hipFuncSetAttribute
-    unsigned threads;         // workgroup size
-    unsigned grid;            // workgroups: one per pair
-};
-inline TriBatchPlan tri_batch_plan(int cap, int npairs) {
-    TriBatchPlan P{};
-    const size_t lds = (size_t)TRI_BATCH_ROW_BYTES * (size_t)cap;
-    P.form = lds <= TRI_BATCH_LDS_MAX ? TriBatchForm::Lds : TriBatchForm::Global;
-    P.ldsBytes = P.form == TriBatchForm::Lds ? lds : 0;
-    P.ldsOptIn = P.ldsBytes > DYNAMIC_LDS_DEFAULT_MAX ? 1 : 0;
-    P.threads = 64u * TRI_BATCH_WAVES;
-    P.grid = (unsigned)npairs;
-    return P;
-}
 
-// -------------------------------------------------------------- Fuse / SearchBySim3 candidate search of a batch (sslam_fuse_search_batch_dev)
-// One workgroup of FUSE_BATCH_WAVES waves per (job, chunk of FUSE_BATCH_CHUNK queries) -- k_fuse_search_batch; the grid is flattened to one dimension,
-// job-major: workgroup g serves chunk g % chunks of job g / chunks.  chunks = ceil(qcap / FUSE_BATCH_CHUNK), and 1 where qcap is 0: chunk 0 of a job
-// is the one that reports a skipped job, so it exists for every job.  The form follows the row capacity alone (every job of a launch runs the same
-// kernel), the grid follows njobs and qcap alone:
-//   Lds     the keyframe's GEOMETRY sits in the workgroup's LDS as four arrays of cap words (x, y, uright, octave resp. pt_x, pt_y, angle, octave):
-//           FUSE_BATCH_ROW_BYTES * cap bytes, while that is at most FUSE_BATCH_LDS_MAX (64 KB: cap <= 4096; two workgroups per compute unit at the
-//           bound; at 1000 rows the 32 wave slots admit four and the LDS is no limit); more than DYNAMIC_LDS_DEFAULT_MAX (cap > 3072) needs the per-kernel opt-in.  Descriptors are never staged: a
-//           window admits a handful of rows, and only those rows' descriptors are read
-//   Global  beyond that: the same kernel scans the caller's buffers, with no dynamic LDS
-// No scratch: a job's state is in its workgroups' LDS, their registers and the job's own output rows.
-constexpr int FUSE_BATCH_WAVES = 8;
+// Fuse / SearchBySim3 candidate search of a batch (sslam_fuse_search_batch_dev, k_fuse_search_batch): one workgroup per (job, chunk of FUSE_BATCH_CHUNK
+// queries); the grid is flattened to one dimension, job-major: workgroup g serves chunk g % chunks of job g / chunks, njobs * chunks in all (64 bits:
+// the entry point refuses 2^31 and more).  The keyframe's GEOMETRY is staged, as four arrays of cap words (x, y, uright, octave resp. pt_x, pt_y,
+// angle, octave): cap <= 4096 in LDS, the opt-in above 3072; at 1000 rows the 32 wave slots admit four workgroups and the LDS is no limit.
+// Descriptors are never staged: a window admits a handful of rows, and only those rows' descriptors are read.
 constexpr int FUSE_BATCH_ROW_BYTES = 16;
 constexpr int FUSE_BATCH_CHUNK = 256;
-constexpr size_t FUSE_BATCH_LDS_MAX = 64 * 1024;
-enum class FuseBatchForm { Lds, Global };
-struct FuseBatchPlan {
-    FuseBatchForm form;
-    size_t ldsBytes;          // dynamic LDS per workgroup (0: Global)
-    int ldsOptIn;             // ldsBytes is more than a launch may ask for without hipFuncSetAttribute
-    unsigned threads;         // workgroup size
-    unsigned chunks;          // workgroups per job, at least 1
-    unsigned long long grid;  // workgroups: njobs * chunks (the entry point refuses 2^31 and more)
-};
-inline FuseBatchPlan fuse_batch_plan(int cap, int qcap, int njobs) {
-    FuseBatchPlan P{};
-    const size_t lds = (size_t)FUSE_BATCH_ROW_BYTES * (size_t)cap;
-    P.form = lds <= FUSE_BATCH_LDS_MAX ? FuseBatchForm::Lds : FuseBatchForm::Global;
-    P.ldsBytes = P.form == FuseBatchForm::Lds ? lds : 0;
-    P.ldsOptIn = P.ldsBytes > DYNAMIC_LDS_DEFAULT_MAX ? 1 : 0;
-    P.threads = 64u * FUSE_BATCH_WAVES;
-    P.chunks = (unsigned)std::max(1, (int)(((long long)qcap + FUSE_BATCH_CHUNK - 1) / FUSE_BATCH_CHUNK));
-    P.grid = (unsigned long long)njobs * P.chunks;
-    return P;
-}
+// workgroups per job: ceil(qcap / FUSE_BATCH_CHUNK), and 1 where qcap is 0 -- chunk 0 of a job is the one that reports a skipped job, so it exists for every job
+inline unsigned fuse_batch_chunks(int qcap) { return (unsigned)std::max(1, (int)(((long long)qcap + FUSE_BATCH_CHUNK - 1) / FUSE_BATCH_CHUNK)); }
+inline unsigned long long fuse_batch_grid(int njobs, int qcap) { return (unsigned long long)njobs * fuse_batch_chunks(qcap); }
 
 // -------------------------------------------------------------- ComputeDistinctiveDescriptors of a batch (sslam_distinctive_descriptors_batch_dev)
 // A set's kernel follows its ENTRY count, d_ptr[s + 1] - d_ptr[s], which only the device reads: every call enqueues both kernels.

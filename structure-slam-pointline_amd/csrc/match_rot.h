@@ -14,6 +14,9 @@ __device__ __forceinline__ int rot_bin(float angle1, float angle2) {
     return bin;
 }
 
+// The bin as a histogram index whatever the rows hold: angles of [0, 360) never need the clamp, and a device-resident slot may hold anything.
+__device__ __forceinline__ int rot_hist_bin(float angle1, float angle2) { return min(max(rot_bin(angle1, angle2), 0), HISTO_LENGTH - 1); }
+
 // ComputeThreeMaxima: the first bin wins a tie (strict >); the second and third are dropped (-1) when they hold less than 10 % of the first
 __device__ __forceinline__ void three_maxima(const int* hist, int& ind1, int& ind2, int& ind3) {
     int i1 = -1, i2 = -1, i3 = -1, max1 = 0, max2 = 0, max3 = 0;

@@ -7,7 +7,7 @@ import numpy as np
 import match_cases as mc
 from oracle_lib import KP_DTYPE
 
-W = 8               # waves per pair of k_search_bow_batch (csrc/match_plan.h BOW_BATCH_WAVES): wave w owns the nodes with id % W == w
+W = 8               # waves per pair of k_search_bow_batch (csrc/match_plan.h BATCH_WAVES): wave w owns the nodes with id % W == w
 ROW_BYTES = 40      # LDS bytes per frame row (BOW_BATCH_ROW_BYTES)
 LDS_MAX = 64 * 1024
 LDS_CAP = LDS_MAX // ROW_BYTES          # 1638: the last row capacity whose frame side sits in LDS

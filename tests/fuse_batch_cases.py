@@ -11,10 +11,10 @@ from oracle_lib import KP_DTYPE, KL_DTYPE
 
 PQ_DTYPE = mc.PQ_DTYPE
 JOB_DTYPE = np.dtype([("kf", "<i4"), ("nq", "<i4"), ("qdesc0", "<i4")])      # sslam_fuse_job (frontend.FUSE_JOB_DTYPE)
-W = 8                                   # waves per workgroup of k_fuse_search_batch (csrc/match_plan.h FUSE_BATCH_WAVES)
+W = 8                                   # waves per workgroup of k_fuse_search_batch (csrc/match_plan.h BATCH_WAVES)
 ROW_BYTES = 16                          # LDS bytes per keyframe row (FUSE_BATCH_ROW_BYTES)
 CHUNK = 256                             # queries per workgroup (FUSE_BATCH_CHUNK)
-LDS_MAX = 64 * 1024                     # FUSE_BATCH_LDS_MAX
+LDS_MAX = 64 * 1024                     # BATCH_LDS_MAX
 LDS_DEFAULT = 48 * 1024                 # DYNAMIC_LDS_DEFAULT_MAX
 LDS_CAP = LDS_MAX // ROW_BYTES          # 4096: the last row capacity whose geometry sits in LDS
 PLAIN_CAP = LDS_DEFAULT // ROW_BYTES    # 3072: the last row capacity without the dynamic-LDS opt-in

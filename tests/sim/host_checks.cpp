@@ -1,6 +1,7 @@
 // Host-only checks of the library's host side, built by tests/test_host_checks_cpu.py with a plain host compiler under
 // -fsanitize=address,undefined -DSSLAM_TESTING (no GPU, no HIP: tests/sim/hip_stub stands in for the runtime):
 //   check_csr (csrc/match_check.h)        which CSR lists a call accepts, and that a refused list is never read past what its offsets promise
+//   all_aligned, rows_in_range, fits_31_bits (csrc/match_check.h)   the alignment and size rules of the device-resident batches, on both sides of every bound
 //   StreamOrderedBuf (csrc/common.h)      which runtime calls acquire / mark / release make, in which order
 //   gather_to_root (csrc/group_exchange.h) over the RCCL stand-in (csrc/rccl_standin.h), a thread per rank: the lengths' all-gather and the payload
 //                                         exchange of both group forms, for several rank counts, with and without the root's own bytes through the table
@@ -47,6 +48,29 @@ static int check_csr_cases() {
     CHECK(refused(csr({0, 2, 3}, {0, -1, 2}, 5), "out of range"));
     CHECK(refused(csr({0, 1}, {0}, 0), "out of range"));                      // no row at all to point at
     printf("check_csr ok\n");
+    return 0;
+}
+
+static int check_argument_rules() {
+    alignas(16) static unsigned char block[64];
+    const uint8_t* a = block + 16; const float* f = (const float*)(block + 32); const int32_t* none = nullptr;
+    CHECK(all_aligned<16>(a) && all_aligned<16>(a, f) && all_aligned<4>(a, f, block + 4) && all_aligned<8>(block + 8, f));
+    for (int off : {1, 2, 4, 8}) {                                             // the largest power of two that divides the address decides
+        const uint8_t* m = block + 16 + off;
+        for (int al : {2, 4, 8, 16}) {
+            const bool want = off % al == 0;
+            const bool got = al == 2 ? all_aligned<2>(a, m, f) : al == 4 ? all_aligned<4>(a, m, f) : al == 8 ? all_aligned<8>(a, m, f) : all_aligned<16>(a, m, f);
+            CHECK(got == want);
+        }
+        CHECK(!all_aligned<16>(m) && !all_aligned<16>(f, a, m) && all_aligned<1>(m));      // wherever it stands in the list
+    }
+    CHECK(all_aligned<16>(a, none, f) && all_aligned<4>(none) && all_aligned<16>((const void*)nullptr, a));      // a null pointer is aligned
+    CHECK(!all_aligned<4>(none, block + 17));
+    CHECK(!rows_in_range(-1) && rows_in_range(0) && rows_in_range(MAX_ROWS - 1) && !rows_in_range(MAX_ROWS) && MAX_ROWS == 1 << 19);
+    CHECK(!rows_in_range(INT32_MIN) && !rows_in_range(INT32_MAX));
+    CHECK(fits_31_bits(1, INT32_MAX) && fits_31_bits(INT32_MAX, 1) && !fits_31_bits(1 << 16, 1 << 15) && !fits_31_bits(2, 1 << 30));      // 2^31 - 1 and 2^31
+    CHECK(fits_31_bits((1 << 16) - 1, 1 << 15) && fits_31_bits(0, INT32_MAX) && fits_31_bits(INT32_MAX, 0) && !fits_31_bits(INT32_MAX, INT32_MAX));      // no wrap in 64 bits
+    printf("argument rules ok\n");
     return 0;
 }
 
@@ -142,7 +166,7 @@ static int check_exchange() {
 }
 
 int main() {
-    if (check_csr_cases() || check_stream_ordered_buf() || check_exchange()) return 1;
+    if (check_csr_cases() || check_argument_rules() || check_stream_ordered_buf() || check_exchange()) return 1;
     printf("ok\n");
     return 0;
 }

@@ -1,40 +1,22 @@
-"""The host-side plan of sslam_orb_search_by_bow_batch_dev (csrc/match_plan.h: bow_batch_plan).  The header holds no HIP:
-tests/sim/bow_batch_plan_dump.cpp compiles it with plain g++, once as it is and once with -fsanitize=address,undefined, as a stand-alone program;
+"""The host-side plan of sslam_orb_search_by_bow_batch_dev (csrc/match_plan.h: batch_plan at BOW_BATCH_ROW_BYTES).  The header holds no HIP:
+tests/sim/match_plan_dump.cpp compiles it with plain g++, once as it is and once with -fsanitize=address,undefined, as a stand-alone program;
 nothing is loaded into Python.  Every expected value is worked out here from the documented rule, never read back from the header:
 
   workgroup   one per pair, 8 waves of 64 lanes (wave w owns the nodes with id % 8 == w)
   form        the frame side of a pair in LDS -- 32 bytes of descriptor, 4 of node id, 4 of live assignment per row of the FRAME capacity -- while
               40 * cap <= 64 KB; beyond that the same kernel on global memory, with no dynamic LDS
   opt-in      more than 48 KB of dynamic LDS needs the per-kernel opt-in"""
-import os, subprocess
 import pytest
+import plan_dump
 import bow_batch_cases as bc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 WAVES, ROW, LDS_MAX, LDS_DEFAULT, LDS_CU = 8, 40, 64 * 1024, 48 * 1024, 160 * 1024
 
 
 @pytest.fixture(scope="module")
-def ask(tmp_path_factory):
-    """ask(lines) -> one list of tokens per line; the plain and the sanitised build must answer alike, and the sanitised one must end clean"""
-    d = tmp_path_factory.mktemp("bow_batch_plan")
-    src = os.path.join(HERE, "sim", "bow_batch_plan_dump.cpp")
-    plain, san = str(d / "bow_batch_plan_dump"), str(d / "bow_batch_plan_dump_san")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", src, "-o", plain])
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", san])
-
-    def run(lines):
-        text = "\n".join(lines) + "\n"
-        outs = []
-        for exe in (plain, san):
-            r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
-            assert r.returncode == 0 and r.stderr == "", (exe, r.returncode, r.stderr)
-            outs.append(r.stdout)
-        assert outs[0] == outs[1]
-        rows = [l.split() for l in outs[0].splitlines()]
-        assert len(rows) == len(lines)
-        return rows
-    return run
+def ask():
+    """ask(lines) -> one list of tokens per line; the plain and the sanitised build must answer alike, and the sanitised one must end clean (plan_dump.py)"""
+    return plan_dump.asker("bow_batch")
 
 
 def expect_plan(cap, npairs):

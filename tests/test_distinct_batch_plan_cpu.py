@@ -1,5 +1,5 @@
 """The host-side plan of sslam_distinctive_descriptors_batch_dev (csrc/match_plan.h: distinct_class, distinct_batch_plan).  The header holds no HIP:
-tests/sim/distinct_batch_plan_dump.cpp compiles it with plain g++, once as it is and once with -fsanitize=address,undefined, as a stand-alone program;
+tests/sim/match_plan_dump.cpp compiles it with plain g++, once as it is and once with -fsanitize=address,undefined, as a stand-alone program;
 nothing is loaded into Python.  Every expected value is worked out here from the documented rule, never read back from the header:
 
   class       by the ENTRY count of a set: 0 .. 8 small, 9 .. 64 medium, 65 .. 1024 large, more (or a malformed range, handed in as a negative count) refused
@@ -9,11 +9,10 @@ nothing is loaded into Python.  Every expected value is worked out here from the
   second      k_distinct_large: one wave per workgroup, chunks of 64 sets (lane = set), ceil(nsets / 64) workgroups capped at 1024; 1024 rows of 32
               bytes and their 16-bit entry positions, 34 KB
   launches    both kernels whenever there is a set -- the host never reads d_ptr -- and none without"""
-import os, subprocess
 import pytest
+import plan_dump
 import distinct_batch_cases as dc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SMALL, MEDIUM, LARGE = 8, 64, 1024
 SETS_PER_WAVE, WAVES, GRID_MAX = 8, 4, 2048
 ROW_BYTES, DIST_BYTES = 32 * 64, 2 * 64 * 64
@@ -22,26 +21,9 @@ LDS_CU, LDS_STATIC_MAX = 160 * 1024, 64 * 1024
 
 
 @pytest.fixture(scope="module")
-def ask(tmp_path_factory):
-    """ask(lines) -> one list of tokens per line; the plain and the sanitised build must answer alike, and the sanitised one must end clean"""
-    d = tmp_path_factory.mktemp("distinct_batch_plan")
-    src = os.path.join(HERE, "sim", "distinct_batch_plan_dump.cpp")
-    plain, san = str(d / "distinct_batch_plan_dump"), str(d / "distinct_batch_plan_dump_san")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", src, "-o", plain])
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", san])
-
-    def run(lines):
-        text = "\n".join(lines) + "\n"
-        outs = []
-        for exe in (plain, san):
-            r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
-            assert r.returncode == 0 and r.stderr == "", (exe, r.returncode, r.stderr)
-            outs.append(r.stdout)
-        assert outs[0] == outs[1]
-        rows = [l.split() for l in outs[0].splitlines()]
-        assert len(rows) == len(lines)
-        return rows
-    return run
+def ask():
+    """ask(lines) -> one list of tokens per line; the plain and the sanitised build must answer alike, and the sanitised one must end clean (plan_dump.py)"""
+    return plan_dump.asker("distinct_batch")
 
 
 def expect_plan(nsets):

@@ -1,5 +1,5 @@
-"""The host-side plan of sslam_fuse_search_batch_dev (csrc/match_plan.h: fuse_batch_plan).  The header holds no HIP:
-tests/sim/fuse_batch_plan_dump.cpp compiles it with plain g++, once as it is and once with -fsanitize=address,undefined, as a stand-alone program;
+"""The host-side plan of sslam_fuse_search_batch_dev (csrc/match_plan.h: batch_plan at FUSE_BATCH_ROW_BYTES, fuse_batch_grid).  The header holds no HIP:
+tests/sim/match_plan_dump.cpp compiles it with plain g++, once as it is and once with -fsanitize=address,undefined, as a stand-alone program;
 nothing is loaded into Python.  Every expected value is worked out here from the documented rule, never read back from the header:
 
   workgroup   8 waves of 64 lanes per (job, chunk of 256 queries); the grid is one-dimensional, njobs * ceil(qcap / 256) -- and njobs where qcap is 0,
@@ -7,35 +7,17 @@ nothing is loaded into Python.  Every expected value is worked out here from the
   form        the keyframe's geometry in LDS -- four words per row of the capacity: x, y, uright, octave or pt_x, pt_y, angle, octave -- while
               16 * cap <= 64 KB; beyond that the same kernel on global memory, with no dynamic LDS
   opt-in      more than 48 KB of dynamic LDS needs the per-kernel opt-in"""
-import os, subprocess
 import pytest
+import plan_dump
 import fuse_batch_cases as fc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 WAVES, ROW, CHUNK, LDS_MAX, LDS_DEFAULT, LDS_CU = 8, 16, 256, 64 * 1024, 48 * 1024, 160 * 1024
 
 
 @pytest.fixture(scope="module")
-def ask(tmp_path_factory):
-    """ask(lines) -> one list of tokens per line; the plain and the sanitised build must answer alike, and the sanitised one must end clean"""
-    d = tmp_path_factory.mktemp("fuse_batch_plan")
-    src = os.path.join(HERE, "sim", "fuse_batch_plan_dump.cpp")
-    plain, san = str(d / "fuse_batch_plan_dump"), str(d / "fuse_batch_plan_dump_san")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", src, "-o", plain])
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", san])
-
-    def run(lines):
-        text = "\n".join(lines) + "\n"
-        outs = []
-        for exe in (plain, san):
-            r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
-            assert r.returncode == 0 and r.stderr == "", (exe, r.returncode, r.stderr)
-            outs.append(r.stdout)
-        assert outs[0] == outs[1]
-        rows = [l.split() for l in outs[0].splitlines()]
-        assert len(rows) == len(lines)
-        return rows
-    return run
+def ask():
+    """ask(lines) -> one list of tokens per line; the plain and the sanitised build must answer alike, and the sanitised one must end clean (plan_dump.py)"""
+    return plan_dump.asker("fuse_batch")
 
 
 def expect_plan(cap, qcap, njobs):

@@ -8,38 +8,16 @@ expected value below is worked out here from the documented rule, never read bac
                             64 + ccap * 64 <= 64 KB: LDS batch; else global memory
   projection                n <= 8192: two kernels, the features in the commit's LDS up to 2048 of them; else one wave
   arena                     every block starts on the next multiple of 256 bytes behind the block before it"""
-import os, subprocess
 import pytest
+import plan_dump
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 KP, PQ = 28, 44          # sizeof(sslam_keypoint), sizeof(sslam_proj_query): include/sslam_frontend.h
 
 
 @pytest.fixture(scope="module")
-def dumps(tmp_path_factory):
-    d = tmp_path_factory.mktemp("match_plan")
-    src = os.path.join(HERE, "sim", "match_plan_dump.cpp")
-    plain, san = str(d / "match_plan_dump"), str(d / "match_plan_dump_san")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", src, "-o", plain])
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", san])
-    return plain, san
-
-
-@pytest.fixture(scope="module")
-def ask(dumps):
-    """ask(lines) -> one list of tokens per line; both builds must give the same answer, and the sanitised one must end clean"""
-    def run(lines):
-        text = "\n".join(lines) + "\n"
-        outs = []
-        for exe in dumps:
-            r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
-            assert r.returncode == 0 and r.stderr == "", (exe, r.returncode, r.stderr)
-            outs.append(r.stdout)
-        assert outs[0] == outs[1]
-        rows = [l.split() for l in outs[0].splitlines()]
-        assert len(rows) == len(lines)
-        return rows
-    return run
+def ask():
+    """ask(lines) -> one list of tokens per line; the plain and the sanitised build must answer alike, and the sanitised one must end clean (plan_dump.py)"""
+    return plan_dump.asker()
 
 
 def al(v):

@@ -1,5 +1,5 @@
 """The host-side plan of sslam_search_by_projection_batch_dev (csrc/match_plan.h: proj_batch_plan, proj_batch_slice, proj_batch_arena).  The header holds no
-HIP: tests/sim/proj_batch_plan_dump.cpp compiles it with plain g++, once as it is and once with -fsanitize=address,undefined, as a stand-alone program;
+HIP: tests/sim/match_plan_dump.cpp compiles it with plain g++, once as it is and once with -fsanitize=address,undefined, as a stand-alone program;
 nothing is loaded into Python.  Every expected value is worked out here from the documented rule, never read back from the header:
 
   form        row capacity <= 8192: two kernels (candidates per (frame, query), one committing wave per frame); beyond: the one-wave kernel per frame
@@ -7,10 +7,9 @@ nothing is loaded into Python.  Every expected value is worked out here from the
               more than 48 KB needs the per-kernel opt-in
   scratch     per frame of a slice 8 (cap + qcap) + 8 K qcap + 4 qcap bytes, K = 8
   slice       as many frames as fit 256 MiB, at most 32768 (and the testing library's limit), at most nframes, at least 1"""
-import os, subprocess
 import pytest
+import plan_dump
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 K = 8
 SCRATCH_MAX = 256 << 20
 MAX_SLICE = 32768
@@ -19,26 +18,9 @@ LDS_CU = 160 * 1024
 
 
 @pytest.fixture(scope="module")
-def ask(tmp_path_factory):
-    """ask(lines) -> one list of tokens per line; the plain and the sanitised build must answer alike, and the sanitised one must end clean"""
-    d = tmp_path_factory.mktemp("proj_batch_plan")
-    src = os.path.join(HERE, "sim", "proj_batch_plan_dump.cpp")
-    plain, san = str(d / "proj_batch_plan_dump"), str(d / "proj_batch_plan_dump_san")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", src, "-o", plain])
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", san])
-
-    def run(lines):
-        text = "\n".join(lines) + "\n"
-        outs = []
-        for exe in (plain, san):
-            r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
-            assert r.returncode == 0 and r.stderr == "", (exe, r.returncode, r.stderr)
-            outs.append(r.stdout)
-        assert outs[0] == outs[1]
-        rows = [l.split() for l in outs[0].splitlines()]
-        assert len(rows) == len(lines)
-        return rows
-    return run
+def ask():
+    """ask(lines) -> one list of tokens per line; the plain and the sanitised build must answer alike, and the sanitised one must end clean (plan_dump.py)"""
+    return plan_dump.asker("proj_batch")
 
 
 def frame_bytes(cap, qcap):

@@ -10,9 +10,9 @@ import bow_batch_cases as bc
 import rot_cases
 from oracle_lib import KP_DTYPE
 
-W = 8                                   # waves per pair of k_tri_search_batch (csrc/match_plan.h TRI_BATCH_WAVES)
+W = 8                                   # waves per pair of k_tri_search_batch (csrc/match_plan.h BATCH_WAVES)
 ROW_BYTES = 48                          # LDS bytes per keyframe-2 row (TRI_BATCH_ROW_BYTES)
-LDS_MAX = 64 * 1024                     # TRI_BATCH_LDS_MAX
+LDS_MAX = 64 * 1024                     # BATCH_LDS_MAX
 LDS_DEFAULT = 48 * 1024                 # DYNAMIC_LDS_DEFAULT_MAX
 LDS_CAP = LDS_MAX // ROW_BYTES          # 1365: the last row capacity whose keyframe 2 sits in LDS
 PLAIN_CAP = LDS_DEFAULT // ROW_BYTES    # 1024: the last row capacity without the dynamic-LDS opt-in

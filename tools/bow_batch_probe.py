@@ -13,52 +13,23 @@ synchronise; after a warm-up pass, the median of `reps` passes.  (a): wall time 
 sslam_compute_bow and sslam_orb_search_by_bow, which a caller also pays per pair, is done beforehand and NOT timed, so (a) is a lower bound; above
 1024 pairs the loop is timed over 1024 pairs (its cost per pair does not depend on the batch).  --loop-lib: the library (a) runs on, e.g. a build
 of the parent commit (default: the library under test).  Then an untimed pass with sslam_profile_enable for the kernel split of (b)."""
-import argparse, ctypes as C, json, os, sys, time
+import ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 import torch
 import pkg, oracle_lib
 from synth import synth_frame, warp_prev
 from bow_batch_cases import csr_from_nodes
+import batch_probe_common as bp
+from batch_probe_common import big_vocab, med
 
 LEVELSUP, NNRATIO, ORI = 4, 0.7, 1          # Tracking::TrackReferenceKeyFrame: ORBmatcher matcher(0.7, true)
 
 
-def big_vocab(rng, k=10, L=6):
-    """a full k-ary tree of L levels in DBoW2's numbering, level by level: (L, child_ptr, children, node_desc, word_id, weight)"""
-    sizes = [k ** l for l in range(L + 1)]
-    offs = np.concatenate([[0], np.cumsum(sizes)])
-    n = int(offs[-1])
-    desc = np.zeros((n, 32), np.uint8)
-    desc[0] = rng.integers(0, 256, 32, dtype=np.uint8)
-    for l in range(1, L + 1):
-        par = np.repeat(desc[offs[l - 1]:offs[l]], k, axis=0)
-        flips = rng.integers(0, 256, par.shape, dtype=np.uint8)
-        for _ in range(min(l - 1, 2)):                      # flip probability 1/2, 1/4, 1/8, 1/8, ..: children cluster around their parent
-            flips &= rng.integers(0, 256, par.shape, dtype=np.uint8)
-        desc[offs[l]:offs[l + 1]] = par ^ flips
-    nchild = np.zeros(n, np.int64); nchild[:offs[L]] = k
-    ptr = np.concatenate([[0], np.cumsum(nchild)]).astype(np.int32)
-    children = np.arange(1, n, dtype=np.int32)
-    word = np.full(n, -1, np.int32); word[offs[L]:] = np.arange(sizes[L], dtype=np.int32)
-    weight = np.zeros(n, np.float64); weight[offs[L]:] = rng.uniform(0.1, 9.0, sizes[L])
-    return L, ptr, children, desc, word, weight
-
-
-def med(v):
-    return float(np.median(v))
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="64,1024,12288"); ap.add_argument("--reps", type=int, default=10); ap.add_argument("--unique", type=int, default=16)
-    ap.add_argument("--loop-lib", default=None); ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    lines = []
-
-    def say(s):
-        print(s, flush=True); lines.append(s)
+    a = bp.parse_args("--batches", "64,1024,12288", 10, 16)
+    log = bp.Lines(); say = log.say
 
     fe = pkg.frontend(); orc = oracle_lib.Oracle()
     pipeline = pkg._load("sslam_pipeline", os.path.join(pkg.PKG_DIR, "pipeline.py"))
@@ -76,16 +47,12 @@ def main():
     ctx = fe.Context(0)
     voc = fe.Vocabulary(ctx, L, ptr, ch, nd, word, weight)
     # (a)'s library, context and vocabulary
-    LA = C.CDLL(a.loop_lib) if a.loop_lib else fe.lib()
-    LA.sslam_last_error.restype = C.c_char_p
-    hA, vA = C.c_void_p(), C.c_void_p()
+    LA, hA = bp.loop_library(fe, ctx, a, say)
     p_ = fe._p
+    vA = voc.h
     if a.loop_lib:
-        assert LA.sslam_ctx_create(0, C.byref(hA)) == 0
+        vA = C.c_void_p()
         assert LA.sslam_vocab_create(hA, len(ptr) - 1, L, p_(ptr), p_(ch), p_(nd), p_(word), p_(weight), C.byref(vA)) == 0, LA.sslam_last_error()
-    else:
-        hA, vA = ctx.h, voc.h
-    say("(a) runs on %s" % (a.loop_lib or "the library under test"))
     # the CSR lists of every unique pair (what a caller flattens from the two FeatureVectors), untimed; and (a)'s outputs
     outs, argsA = [], []
     for p in pairs:
@@ -120,33 +87,27 @@ def main():
     tU = [up(x) for x in (kkU, kdU, kvU, fkU, fdU)] + [torch.from_numpy(nkU).cuda(), torch.from_numpy(nfU).cuda()]
     st = torch.cuda.Stream()
     report = {}
-    for B in [int(x) for x in a.batches.split(",")]:
+    for B in a.sizes:
         assert B % U == 0
         kkB, kdB, kvB, fkB, fdB = [t.repeat(B // U, 1) for t in tU[:5]]; nkB, nfB = tU[5].repeat(B // U), tU[6].repeat(B // U)
         knB = torch.full((B, cap), -9, dtype=torch.int32, device="cuda"); fnB = torch.full((B, cap), -9, dtype=torch.int32, device="cuda")
         assigned = torch.full((B, cap), -9, dtype=torch.int32, device="cuda"); nmB = torch.full((B,), -9, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
 
-        def run_b():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0 = time.perf_counter()
-            e0.record(st)
+        def enqueue_b():
             ctx.bow_transform_batch_dev(voc, kdB, nkB, cap, B, knB, levelsup=LEVELSUP, stream=st.cuda_stream)
             ctx.bow_transform_batch_dev(voc, fdB, nfB, cap, B, fnB, levelsup=LEVELSUP, stream=st.cuda_stream)
             ctx.search_by_bow_batch_dev(kkB, kdB, knB, kvB, nkB, cap, B, fkB, fdB, fnB, nfB, cap, B, B, assigned, nmB, nnratio=NNRATIO, check_orientation=bool(ORI),
                                         stream=st.cuda_stream)
-            t1 = time.perf_counter()
-            e1.record(st); st.synchronize()
-            return e0.elapsed_time(e1), (time.perf_counter() - t0) * 1e3, (t1 - t0) * 1e3
+
+        run_b = lambda: bp.timed_pass(st, enqueue_b)
 
         nA = min(B, 1024)
         run_a(max(U, 64)); run_b()                               # warm-up: code objects, the loop's arenas and pinned mirrors
         got, gnm = assigned[B - U:].cpu().numpy(), nmB[B - U:].cpu().numpy()      # the LAST pairs of the batch; (a) left pair u's rows in outs[u]
         same = all(np.array_equal(got[u, :nfU[u]], outs[u]) and gnm[u] == int((outs[u] >= 0).sum()) for u in range(U))
-        ta, tb = [], []
-        for _ in range(a.reps):
-            ta.append(run_a(nA)); tb.append(run_b())
-        dev_b, wall_b, enq_b = med([x[0] for x in tb]), med([x[1] for x in tb]), med([x[2] for x in tb])
+        ta, tb = bp.alternate(a.reps, lambda: run_a(nA), run_b)
+        dev_b, wall_b, enq_b = bp.b_medians(tb)
         a_us = med(ta) * 1e3 / nA
         fe.lib().sslam_profile_enable(ctx.h, 1)
         run_b(); split_b = pipeline.profile_drain(fe, ctx)
@@ -162,10 +123,7 @@ def main():
         say("        (b) kernels: " + ", ".join("%s %.3f ms x%d = %.3f us/pair" % (k, v[0], v[1], v[0] * 1e3 / B) for k, v in sorted(split_b.items())))
         del kkB, kdB, kvB, fkB, fdB, knB, fnB, assigned
     voc.close(); ctx.close()
-    say("JSON " + json.dumps(report))
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    log.finish("bow_batch_probe", report, a.out)
 
 
 if __name__ == "__main__":

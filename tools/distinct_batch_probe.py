@@ -15,14 +15,15 @@ k_distinct_batch + k_distinct_large of (b) on the same sets.  THE CONDITION (64 
 more than the spread (max - min) of k_distinctive's own passes.
 --loop-lib: the library (a) runs on, e.g. a build of the parent commit (default: the library under test).  d_best and the table of (b) must equal (a)'s
 for every set, or the probe exits non-zero."""
-import argparse, ctypes as C, json, os, sys, time
+import ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 import torch
 import pkg
 import distinct_batch_cases as dc
-from bow_batch_probe import med
+import batch_probe_common as bp
+from batch_probe_common import med
 
 POINTS, K, N = 2000, 21, 1000
 
@@ -34,36 +35,23 @@ def drain(L, h):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sessions", default="1,64,1024"); ap.add_argument("--reps", type=int, default=10); ap.add_argument("--unique", type=int, default=2)
-    ap.add_argument("--loop-lib", default=None); ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    lines = []
-
-    def say(s):
-        print(s, flush=True); lines.append(s)
+    a = bp.parse_args("--sessions", "1,64,1024", 10, 2)
+    log = bp.Lines(); say = log.say
 
     fe = pkg.frontend()
     ctx = fe.Context(0)
-    LA = C.CDLL(a.loop_lib) if a.loop_lib else fe.lib()
-    LA.sslam_last_error.restype = C.c_char_p
-    hA = C.c_void_p()
-    if a.loop_lib:
-        assert LA.sslam_ctx_create(0, C.byref(hA)) == 0
-    else:
-        hA = ctx.h
     p_ = fe._p
     U = a.unique
     rng = np.random.default_rng(77)
     S = [dc.workload(rng, POINTS, K, N) for _ in range(U)]
     say("session: %d map points with 3..14 observations (%.1f on average) in %d keyframe slots of %d features; %d unique sessions"
         % (POINTS, np.mean([len(s[1]) for s in S]) / POINTS, K, N, U))
-    say("(a) runs on %s" % (a.loop_lib or "the library under test"))
+    LA, hA = bp.loop_library(fe, ctx, a, say)
     dU = torch.from_numpy(np.stack([s[0] for s in S]).reshape(U, -1)).cuda()
     st = torch.cuda.Stream()
     report = {}
     all_equal, condition = True, None
-    for B in [int(x) for x in a.sessions.split(",")]:
+    for B in a.sizes:
         dB = dU.repeat(-(-B // U), 1)[:B].contiguous().view(B * K, N, 32)
         obs = np.concatenate([S[s % U][1] for s in range(B)])
         obs["kf"] += np.repeat(np.arange(B) * K, [len(S[s % U][1]) for s in range(B)]).astype(np.int32)
@@ -90,20 +78,15 @@ def main():
             kept["rows"] = rows
             return (time.perf_counter() - t0) * 1e3
 
-        def run_b():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0 = time.perf_counter()
-            e0.record(st)
+        def enqueue_b():
             ctx.distinctive_descriptors_batch_dev(dB, d_n, N, B * K, d_obs, nobs, d_ptr, ns, best_b, d_median=med_b, d_out_desc=table_b, nout=ns, stream=st.cuda_stream)
-            e1.record(st); st.synchronize()
-            return e0.elapsed_time(e1), (time.perf_counter() - t0) * 1e3
+
+        run_b = lambda: bp.timed_pass(st, enqueue_b)[:2]
 
         run_a(); run_b()                                                    # warm-up; both leave their results behind
         same = bool(np.array_equal(best_b.cpu().numpy(), best_a) and torch.equal(table_a, table_b))
         all_equal = all_equal and same
-        ta, tb = [], []
-        for _ in range(a.reps):
-            ta.append(run_a()); tb.append(run_b())
+        ta, tb = bp.alternate(a.reps, run_a, run_b)
         # the kernels alone: k_distinctive on (a)'s gathered rows, the two new kernels on the same sets
         rows = kept["rows"]
         ka, kb, kb_split = [], [], []
@@ -114,8 +97,7 @@ def main():
         LA.sslam_profile_enable(hA, 0)
         fe.lib().sslam_profile_enable(ctx.h, 1)
         for _ in range(a.reps + 1):
-            ctx.distinctive_descriptors_batch_dev(dB, d_n, N, B * K, d_obs, nobs, d_ptr, ns, best_b, d_median=med_b, d_out_desc=table_b, nout=ns, stream=st.cuda_stream)
-            st.synchronize()
+            enqueue_b(); st.synchronize()
             d = drain(fe.lib(), ctx.h)
             kb.append(d["k_distinct_batch"] + d["k_distinct_large"]); kb_split.append((d["k_distinct_batch"], d["k_distinct_large"]))
         fe.lib().sslam_profile_enable(ctx.h, 0)
@@ -134,13 +116,7 @@ def main():
         del dB, d_obs, d_ptr, d_n, best_b, med_b, table_a, table_b, rows, kept
     say("condition (64 sessions: new kernels' median <= k_distinctive's median + its spread): %s" % condition)
     ctx.close()
-    say("JSON " + json.dumps(report))
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    if not all_equal:
-        print("distinct_batch_probe: (b) differs from (a)", file=sys.stderr)
-        sys.exit(1)
+    log.finish("distinct_batch_probe", report, a.out, all_equal)
 
 
 if __name__ == "__main__":

@@ -15,14 +15,15 @@ keylines (kind 1: LSDmatcher::Fuse).
 warm-up pass, the median of `reps` passes.  (a): wall time of the loop of C calls alone, queries and descriptors in host arrays as a caller of (a) has
 them; above 1024 jobs the loop is timed over 1024 jobs (its cost per job does not depend on the batch).  --loop-lib: the library (a) runs on, e.g. a
 build of the parent commit (default: the library under test).  Every row of every job of (b) must equal (a)'s, or the probe exits non-zero."""
-import argparse, ctypes as C, json, os, sys, time
+import ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 import torch
 import pkg
 import match_cases as mc
-from bow_batch_probe import med
+import batch_probe_common as bp
+from batch_probe_common import med
 
 NEIGH, N, QCAP = 20, 1000, 1024
 SCALE = (np.float32(1.2) ** np.arange(8)).astype(np.float32)
@@ -51,29 +52,16 @@ def session(rng, kind):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sessions", default="1,64,1024"); ap.add_argument("--reps", type=int, default=10); ap.add_argument("--unique", type=int, default=2)
-    ap.add_argument("--loop-lib", default=None); ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    lines = []
-
-    def say(s):
-        print(s, flush=True); lines.append(s)
+    a = bp.parse_args("--sessions", "1,64,1024", 10, 2)
+    log = bp.Lines(); say = log.say
 
     fe = pkg.frontend()
     U, K, J = a.unique, NEIGH + 1, NEIGH + 1
     ctx = fe.Context(0)
-    LA = C.CDLL(a.loop_lib) if a.loop_lib else fe.lib()
-    LA.sslam_last_error.restype = C.c_char_p
-    hA = C.c_void_p()
-    if a.loop_lib:
-        assert LA.sslam_ctx_create(0, C.byref(hA)) == 0
-    else:
-        hA = ctx.h
     p_ = fe._p
     say("session: %d neighbour jobs of 900..%d queries on one descriptor block + 1 reverse job of %d queries; %d keyframe slots of %d features; %d unique sessions"
         % (NEIGH, N, QCAP, K, N, U))
-    say("(a) runs on %s" % (a.loop_lib or "the library under test"))
+    LA, hA = bp.loop_library(fe, ctx, a, say)
     bounds = (C.c_float * 4)(*BOUNDS)
     st = torch.cuda.Stream()
     report = {}
@@ -117,7 +105,7 @@ def main():
         up = lambda x: torch.from_numpy(x.view(np.uint8).reshape(U, -1)).cuda()
         tf, td, tu, tq, tqd = up(fU), up(dU), up(uU), up(qU), up(qdU)
         rows_mode = {}
-        for B in [int(x) for x in a.sessions.split(",")]:
+        for B in a.sizes:
             r = -(-B // U)
             rep = lambda t: t.repeat(r, 1)[:B].contiguous()
             fB, dB, uB, qB, qdB = rep(tf), rep(td), rep(tu), rep(tq), rep(tqd)
@@ -130,15 +118,11 @@ def main():
             nf = torch.full((B * J,), -9, dtype=torch.int32, device="cuda")
             torch.cuda.synchronize()
 
-            def run_b():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0 = time.perf_counter()
-                e0.record(st)
+            def enqueue_b():
                 ctx.fuse_search_batch_dev(kind, chi2, fB, dB, nB, N, B * K, qB, QCAP, qdB, B * (N + QCAP), jB, B * J, bi, bd, nf, d_uright=uB if kind == 0 else None,
                                           inv_level_sigma2=INV_SIGMA2 if chi2 else None, bounds=BOUNDS, stream=st.cuda_stream)
-                t1 = time.perf_counter()
-                e1.record(st); st.synchronize()
-                return e0.elapsed_time(e1), (time.perf_counter() - t0) * 1e3, (t1 - t0) * 1e3
+
+            run_b = lambda: bp.timed_pass(st, enqueue_b)
 
             nA = min(B * J, 1024)
             run_a(len(argsA)); run_b()                               # warm-up; (a) leaves every unique job's rows in outs
@@ -149,10 +133,8 @@ def main():
                     oi, od = outs[(s % U) * J + j][:2]
                     same = same and np.array_equal(gi[s * J + j, :len(oi)], oi) and np.array_equal(gd[s * J + j, :len(od)], od) and gn[s * J + j] == (oi >= 0).sum()
             all_equal = all_equal and same
-            ta, tb = [], []
-            for _ in range(a.reps):
-                ta.append(run_a(nA)); tb.append(run_b())
-            dev_b, wall_b, enq_b = med([x[0] for x in tb]), med([x[1] for x in tb]), med([x[2] for x in tb])
+            ta, tb = bp.alternate(a.reps, lambda: run_a(nA), run_b)
+            dev_b, wall_b, enq_b = bp.b_medians(tb)
             a_us = med(ta) * 1e3 / nA
             rr = dict(kind=kind, chi2=chi2, sessions=B, jobs=B * J, equal_to_the_loop=bool(same), found_per_job=float(gn.mean()), a_jobs_timed=nA, a_us_per_job=a_us, a_all_ms=ta,
                       b_device_ms=dev_b, b_wall_ms=wall_b, b_enqueue_ms=enq_b, b_us_per_job_device=dev_b * 1e3 / (B * J), b_us_per_job_wall=wall_b * 1e3 / (B * J),
@@ -164,13 +146,7 @@ def main():
             del fB, dB, uB, qB, qdB, bi, bd, nf, jB
         for h in handles: LA.sslam_frame_destroy(h)
     ctx.close()
-    say("JSON " + json.dumps(report))
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    if not all_equal:
-        print("fuse_batch_probe: (b) differs from (a)", file=sys.stderr)
-        sys.exit(1)
+    log.finish("fuse_batch_probe", report, a.out, all_equal)
 
 
 if __name__ == "__main__":

@@ -11,32 +11,24 @@ synchronises).  (b): device time between two HIP events on the call's stream, an
 Then, untimed passes with sslam_profile_enable: the kernel split of (b), and the sum of (a)'s kernels.  Last, (b) with the commit layout the plan
 did not choose (the single call's features in LDS, through sslam_testing_proj_batch_tuning) -- which is why the probe runs on
 libsslam_frontend_testing.so, the product's sources plus the hooks of include/sslam_testing.h."""
-import argparse, ctypes as C, json, os, sys, time
+import ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 import torch
 import pkg, oracle_lib
 from synth import synth_frame
 from test_match_gpu import _proj_queries
 from match_cases import flip_bits
+import batch_probe_common as bp
+from batch_probe_common import med
 
 PARAMS = {0: (0.8, 100, 0), 1: (0.9, 100, 1)}          # mode -> nnratio, th_dist, check_orientation
 
 
-def med(v):
-    return float(np.median(v))
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="1024,6144"); ap.add_argument("--reps", type=int, default=5); ap.add_argument("--unique", type=int, default=16)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    lines = []
-
-    def say(s):
-        print(s, flush=True); lines.append(s)
+    a = bp.parse_args("--batches", "1024,6144", 5, 16, loop_lib=False)
+    log = bp.Lines(); say = log.say
 
     fe = pkg.frontend(); orc = oracle_lib.Oracle()
     pipeline = pkg._load("sslam_pipeline", os.path.join(pkg.PKG_DIR, "pipeline.py"))
@@ -79,29 +71,23 @@ def main():
                     if rc: raise RuntimeError(L.sslam_last_error())
                 return (time.perf_counter() - t0) * 1e3
 
-            for B in [int(x) for x in a.batches.split(",")]:
+            for B in a.sizes:
                 assert B % U == 0
                 kpB, dB, occB, qB, qdB = [t.repeat(B // U, 1) for t in tU[:5]]; nB = tU[5].repeat(B // U)
                 assigned = torch.full((B, cap), -9, dtype=torch.int32, device="cuda"); nmB = torch.zeros(B, dtype=torch.int32, device="cuda")
                 torch.cuda.synchronize()
 
-                def run_b():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    t0 = time.perf_counter()
-                    e0.record(st)
+                def enqueue_b():
                     ctx.search_by_projection_batch_dev(0, mode, kpB, dB, nB, cap, B, qB, qdB, nB, qcap, assigned, nmB, d_occupied=occB, nnratio=ratio, th_dist=th,
                                                        check_orientation=ori, stream=st.cuda_stream)
-                    t1 = time.perf_counter()
-                    e1.record(st); st.synchronize()
-                    return e0.elapsed_time(e1), (time.perf_counter() - t0) * 1e3, (t1 - t0) * 1e3
+
+                run_b = lambda: bp.timed_pass(st, enqueue_b)
 
                 run_a(B); run_b()                                   # warm-up: code objects, the arena, the pinned mirrors
                 got = assigned[:U].cpu().numpy()
                 same = all(np.array_equal(got[u, :nU[u]], outs[u]) for u in range(U)) and bool((nmB.cpu().numpy() >= 0).all())      # (a) left frame u's rows in outs[u]
-                ta, tb = [], []
-                for _ in range(a.reps):
-                    ta.append(run_a(B)); tb.append(run_b())
-                dev_b, wall_b, enq_b = med([x[0] for x in tb]), med([x[1] for x in tb]), med([x[2] for x in tb])
+                ta, tb = bp.alternate(a.reps, lambda: run_a(B), run_b)
+                dev_b, wall_b, enq_b = bp.b_medians(tb)
                 wall_a = med(ta)
                 # kernel split, untimed passes
                 L.sslam_profile_enable(ctx.h, 1)
@@ -129,10 +115,7 @@ def main():
                 del kpB, dB, occB, qB, qdB, assigned
         for h in handles: h.close()
         ctx.close()
-    say("JSON " + json.dumps(report))
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    log.finish("proj_batch_probe", report, a.out)
 
 
 if __name__ == "__main__":

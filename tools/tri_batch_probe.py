@@ -6,7 +6,7 @@ had before it (a): one synchronous sslam_orb_search_for_triangulation call per p
 
 Inputs: `unique` synthetic 640x480 frames of up to 1000 ORB keypoints (the CPU oracle's extraction) as keyframe 2, the same scenes moved by
 synth.warp_prev as keyframe 1, 90 % of the keypoints of either free, monocular; F12 and the epipole are match_cases.tri_F12 / TRI_EPIPOLE (the motion
-of warp_prev); pair p of a batch is unique pair p % unique.  The vocabulary is tools/bow_batch_probe.py's k = 10, L = 6 tree, levelsup = 4: a
+of warp_prev); pair p of a batch is unique pair p % unique.  The vocabulary is tools/batch_probe_common.py's k = 10, L = 6 tree, levelsup = 4: a
 feature's node is one of the 100 nodes of level 2.  only_stereo 0, check_orientation 1.
 (b): device time between two HIP events around the three launches on one side stream, and wall time from the first call to the end of a stream
 synchronise; after a warm-up pass, the median of `reps` passes.  (a): wall time of the loop of C calls alone -- what a caller of (a) also pays per
@@ -14,7 +14,7 @@ pair, bringing the two FeatureVectors to the host and flattening them to CSR lis
 handles are uploaded and the node ids known before the loop): (a) is a lower bound; above 1024 pairs the loop is timed over 1024 pairs (its cost per
 pair does not depend on the batch).  --loop-lib: the library (a) runs on, e.g. a build of the parent commit (default: the library under test).  Every
 pair's result of (b) must equal (a)'s, or the probe exits non-zero.  Then an untimed pass with sslam_profile_enable for the kernel split of (b)."""
-import argparse, ctypes as C, json, os, sys, time
+import ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
@@ -23,20 +23,15 @@ import pkg, oracle_lib
 import match_cases as mc
 from synth import synth_frame, warp_prev
 from bow_batch_cases import csr_from_nodes
-from bow_batch_probe import big_vocab, med
+import batch_probe_common as bp
+from batch_probe_common import big_vocab, med
 
 LEVELSUP, ONLY_STEREO, ORI = 4, 0, 1
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="64,1024,12288"); ap.add_argument("--reps", type=int, default=10); ap.add_argument("--unique", type=int, default=16)
-    ap.add_argument("--loop-lib", default=None); ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    lines = []
-
-    def say(s):
-        print(s, flush=True); lines.append(s)
+    a = bp.parse_args("--batches", "64,1024,12288", 10, 16)
+    log = bp.Lines(); say = log.say
 
     fe = pkg.frontend(); orc = oracle_lib.Oracle()
     pipeline = pkg._load("sslam_pipeline", os.path.join(pkg.PKG_DIR, "pipeline.py"))
@@ -56,15 +51,8 @@ def main():
     ctx = fe.Context(0)
     voc = fe.Vocabulary(ctx, L, ptr, ch, nd, word, weight)
     # (a)'s library and context
-    LA = C.CDLL(a.loop_lib) if a.loop_lib else fe.lib()
-    LA.sslam_last_error.restype = C.c_char_p
-    hA = C.c_void_p()
+    LA, hA = bp.loop_library(fe, ctx, a, say)
     p_ = fe._p
-    if a.loop_lib:
-        assert LA.sslam_ctx_create(0, C.byref(hA)) == 0
-    else:
-        hA = ctx.h
-    say("(a) runs on %s" % (a.loop_lib or "the library under test"))
     say("(a) does NOT count the caller's side of the single call: the two FeatureVectors brought to the host and flattened to CSR lists per pair, and the descents")
     # frame handles, CSR lists (what a caller flattens from the two FeatureVectors) and outputs of every unique pair, untimed
     outs, argsA, handles = [], [], []
@@ -99,7 +87,7 @@ def main():
     st = torch.cuda.Stream()
     report = {}
     all_equal = True
-    for B in [int(x) for x in a.batches.split(",")]:
+    for B in a.sizes:
         assert B % U == 0
         r = B // U
         half = lambda t: torch.cat([t[0].repeat(r, 1), t[1].repeat(r, 1)])          # [2B, ...]: B keyframe-1 slots, then B keyframe-2 slots
@@ -110,27 +98,21 @@ def main():
         m12 = torch.full((B, cap), -9, dtype=torch.int32, device="cuda"); nmB = torch.full((B,), -9, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
 
-        def run_b():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0 = time.perf_counter()
-            e0.record(st)
+        def enqueue_b():
             ctx.bow_transform_batch_dev(voc, dB, nB, cap, B, nodeB, levelsup=LEVELSUP, stream=st.cuda_stream)
             ctx.bow_transform_batch_dev(voc, dB[B:], nB[B:], cap, B, nodeB[B:], levelsup=LEVELSUP, stream=st.cuda_stream)
             ctx.search_for_triangulation_batch_dev(kpB, dB, nodeB, nB, cap, 2 * B, prB, B, sc, sg, m12, nmB, d_free=frB, only_stereo=bool(ONLY_STEREO),
                                                    check_orientation=bool(ORI), stream=st.cuda_stream)
-            t1 = time.perf_counter()
-            e1.record(st); st.synchronize()
-            return e0.elapsed_time(e1), (time.perf_counter() - t0) * 1e3, (t1 - t0) * 1e3
+
+        run_b = lambda: bp.timed_pass(st, enqueue_b)
 
         nA = min(B, 1024)
         run_a(max(U, 64)); run_b()                               # warm-up: code objects, the loop's arena
         got, gnm = m12.cpu().numpy(), nmB.cpu().numpy()          # EVERY pair of the batch; (a) left unique pair u's rows in outs[u]
         same = all(np.array_equal(got[p, :nU[0, p % U]], outs[p % U][0]) and gnm[p] == outs[p % U][1].value for p in range(B))
         all_equal = all_equal and same
-        ta, tb = [], []
-        for _ in range(a.reps):
-            ta.append(run_a(nA)); tb.append(run_b())
-        dev_b, wall_b, enq_b = med([x[0] for x in tb]), med([x[1] for x in tb]), med([x[2] for x in tb])
+        ta, tb = bp.alternate(a.reps, lambda: run_a(nA), run_b)
+        dev_b, wall_b, enq_b = bp.b_medians(tb)
         a_us = med(ta) * 1e3 / nA
         fe.lib().sslam_profile_enable(ctx.h, 1)
         run_b(); split_b = pipeline.profile_drain(fe, ctx)
@@ -147,13 +129,7 @@ def main():
         del kpB, dB, frB, nodeB, m12, prB
     for h in handles: LA.sslam_frame_destroy(h)
     voc.close(); ctx.close()
-    say("JSON " + json.dumps(report))
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    if not all_equal:
-        print("tri_batch_probe: (b) differs from (a)", file=sys.stderr)
-        sys.exit(1)
+    log.finish("tri_batch_probe", report, a.out, all_equal)
 
 
 if __name__ == "__main__":
