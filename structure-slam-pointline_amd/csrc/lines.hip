@@ -327,11 +327,17 @@ static LinesKnobs lines_knobs() {
 }
 
 // Whether a batch of `nframes` runs the sequential core in its guest form (lsd_regions.h): a co-running branch was announced (sslam_lines_set_core_event) and the batch is
-// at least two rounds of the persistent grid of 18 (16 for smaller batches) workgroups per compute unit.  18: two SIMDs of a compute unit hold five core waves and keep 32
-// registers free, two hold four and keep 128 -- since k_fast_cells needs 29 registers (round 6, call AQ) its waves fit into either, and the core's fifth wave on half of the
-// SIMDs pays: 151.3 -> 149.3 ms per step (with the 51-register FAST: 153.2).  17 / 19 / 20 per compute unit: 150.8 / 149.4 / 150.0.
+// at least two rounds of the persistent grid of 20 (16 for smaller batches) workgroups per compute unit.
+// What a compute unit holds beside the core is decided by registers AND by LDS, which gfx950 hands out in granules of 1 280 B (tools/lds_granule_probe.hip).  A core
+// workgroup takes 94 VGPRs and four granules (5 120 B, lsd_regions.h), a k_fast_cells wave 32 VGPRs and four granules at 640 x 480 (orb.hip):
+//   20 per compute unit: five core waves on every SIMD (480 of 512 VGPRs), one FAST wave beside them; 100 KB of the 160 KB of LDS for the core, room for twelve FAST waves;
+//   18 per compute unit: two SIMDs hold five core waves, two hold four and keep 128 registers: ten FAST waves by registers, fourteen by LDS.
+// Before the LDS budgets (core 5 648 B = five granules, FAST 7 290 B = six) 18 left six FAST waves and was the optimum (17 / 19 / 20: 150.8 / 149.4 / 150.0 ms per step against
+// 149.3).  With them it is not: ten FAST waves beside 18 core workgroups slow the core more (92 -> 96 ms) than they speed up FAST (76.4 -> 74.3), 151.4 ms per step; 20 with the
+// FAST waves the registers then leave gives 148.5.  Also measured, no better: k_lsd_regions<false, 6> (80 VGPRs) on the grid at 20 / 22 / 24 per compute unit -- the core
+// drops to 90 / 85 / 79 ms, FAST beside it stays at 76 - 77 ms whatever its slot count, and the step at 148 - 149 ms (profiles/guest_grid_lds_budgets.txt).
 static bool lines_guest_form(const sslam_lines* L, int nframes, const LinesKnobs& K, int* grid_out) {
-    int grid = 18 * L->ctx->num_cus;
+    int grid = 20 * L->ctx->num_cus;
     if (2 * grid > nframes) grid = 16 * L->ctx->num_cus;
     if (K.persist) grid = K.persist;
     if (grid_out) *grid_out = grid;
@@ -360,8 +366,8 @@ enum class CoreForm {
 constexpr int CL_MAXFRAMES = 64;
 
 // Which form a call takes.  Lone waves below 1 024 frames: at most one wave per SIMD is resident, so the instantiation that spills nothing costs no occupancy.  A caller that
-// announced a branch running beside the core (sslam_lines_set_core_event: the bench step's point branch waits for that event) gets the guest form: 16 - 18 persistent workgroups
-// per compute unit of the four-wave instantiation, a third of the registers free for the other branch's waves.  Otherwise up to 16 frames per compute unit (four waves per SIMD
+// announced a branch running beside the core (sslam_lines_set_core_event: the bench step's point branch waits for that event) gets the guest form: 16 - 20 persistent workgroups
+// per compute unit of the four-wave instantiation (lines_guest_form says what that leaves for the other branch's waves).  Otherwise up to 16 frames per compute unit (four waves per SIMD
 // anyway; BASELINE configs[3]: 3 072 frames) take the spill-free instantiation, larger batches the six-wave one.  grid: the guest form's grid.
 static CoreForm lines_core_form(const sslam_lines* L, const LsdPlan& P, int nframes, const LinesKnobs& K, int* grid) {
     if (K.cluster && nframes <= CL_MAXFRAMES && P.sw <= TorusGlobal::XMASK + 1 && P.sh <= TorusGlobal::YMASK + 1)
@@ -493,8 +499,8 @@ static int lines_core_cluster(const LinesCall& c, const LinesKnobs& K, bool stre
 // The sequential core in the form lines_core_form chose, between the core gate / event of the caller
 static int lines_core(const LinesCall& c, const LinesKnobs& K, CoreForm form, int grid, SideJoin& side, size_t* nfaStageOff) {
     sslam_lines* L = c.L; const LsdPlan& P = c.P; const int nframes = c.nframes; hipStream_t st = c.st;
-    static_assert(sizeof(unsigned) * (QCAP + 4) <= 48 * 1024, "k_lsd_regions: the region queue must fit the default dynamic LDS limit (SSLAM_LSD_QCAP)");
-    const size_t lds = sizeof(unsigned) * (QCAP + 4);      // + the sink slot behind the queue (region_grow_w)
+    static_assert(LSD_CORE_LDS <= 48 * 1024, "k_lsd_regions: the region queue must fit the default dynamic LDS limit (SSLAM_LSD_QCAP)");
+    const size_t lds = LSD_CORE_LDS;      // queue, fp64 addends, seed cos / sin: four allocation granules of 1 280 B (lsd_regions.h)
     if (L->coreWait) SSLAM_HIP(hipStreamWaitEvent(st, L->coreWait, 0));      // (sslam_lines_set_core_gate: another extractor's core has the wave slots until then)
     if (L->coreEvent) SSLAM_HIP(hipEventRecord(L->coreEvent, st));
     {

@@ -615,7 +615,7 @@ __device__ bool rect_refine(const LsdPlan& P, const float4 sd, int& n, double& r
 
 // One persistent single-wave workgroup per frame: the flsd() main loop replayed in order.
 template <bool LAT>
-__device__ __forceinline__ void lsd_regions_body(uint8_t* __restrict__ ws, const LsdPlan& P, int b, unsigned* __restrict__ dynLds, double* __restrict__ red, float4* __restrict__ seedStash) {
+__device__ __forceinline__ void lsd_regions_body(uint8_t* __restrict__ ws, const LsdPlan& P, int b, unsigned* __restrict__ dynLds, double* __restrict__ red, float2* __restrict__ seedCs) {
     const int lane = threadIdx.x & 63;
     uint8_t* base = ws + (size_t)b * P.frameBytes;
     Planes pl; pl.T = (float*)(base + P.offT); pl.Cs = (const float2*)(base + P.offCs); pl.S = (const int*)(base + P.offS); pl.tW = P.tW; pl.cW = P.cW;
@@ -636,18 +636,22 @@ __device__ __forceinline__ void lsd_regions_body(uint8_t* __restrict__ ws, const
         const int tiSeed = have ? pl.ti(idx) : 0;
         // One gather per chunk of 64 seed candidates: T is the candidate's level-line angle while it is unused.  What a region start
         // needs from its seed -- coordinates, the angle, cos and sin of it (two fp64 evaluations that the whole wave used to execute for ONE
-        // seed, after a dependent load of the angle) -- is computed here for all 64 candidates at once and parked in LDS.
+        // seed, after a dependent load of the angle) -- is computed here for all 64 candidates at once.  cos and sin are parked in LDS; the angle and
+        // the coordinates stay in their lanes' registers and are fetched with a v_readlane (the seed's lane is wave-uniform): 512 B of LDS instead of
+        // 1 024, which is what brings the workgroup from five LDS allocation granules to four (LSD_CORE_LDS below).
         const float a0 = have ? pl.ldT(tiSeed) : NOTDEF_F;
         unsigned long long unM = __ballot(t_free(a0));        // candidates of this chunk that are still unused (wave-uniform, kept up to date below)
         if (!unM) continue;
         {
             const double ar = (double)a0 * DEG2RAD;
-            seedStash[lane] = make_float4(a0, (float)cos(ar), (float)sin(ar), __int_as_float((int)idx));
+            seedCs[lane] = make_float2((float)cos(ar), (float)sin(ar));
         }
         while (unM) {
             const int first = __ffsll((long long)unM) - 1;
             unM &= unM - 1;                                   // the seed itself is consumed whatever happens
-            const float4 sd = seedStash[first];               // wave-uniform address: one broadcast read
+            const float2 cs = seedCs[first];                  // wave-uniform address: one broadcast read
+            const float4 sd = make_float4(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(a0), first)), cs.x, cs.y,
+                                          __int_as_float(__builtin_amdgcn_readlane((int)idx, first)));
             double regAngle;
             long long t0 = SSLAM_CLK();
             const int sxy = __float_as_int(sd.w), sx = sxy & 0xFFFF, sy = sxy >> 16;
@@ -698,21 +702,30 @@ __device__ __forceinline__ void lsd_regions_body(uint8_t* __restrict__ ws, const
 }
 
 // MW = waves per SIMD the register allocator leaves room for:
-//   6  (80 VGPRs, 11 dwords spilled): every wave slot the register file has -- the fastest form when the core has the chip to itself (77.8 ms per 12 288 frames; 5 and 4: 86 / 85)
-//   4  (97 VGPRs, nothing spilled), launched as a PERSISTENT grid of 16 - 18 workgroups per compute unit (lines.hip, lines_guest_form) that claim frames dynamically: a third of every SIMD's registers
+//   6  (80 VGPRs, 8 dwords spilled): every wave slot the register file has -- the fastest form when the core has the chip to itself (77.8 ms per 12 288 frames; 5 and 4: 86 / 85)
+//   4  (94 VGPRs, nothing spilled), launched as a PERSISTENT grid of 16 - 20 workgroups per compute unit (lines.hip, lines_guest_form) that claim frames dynamically: a third of every SIMD's registers
 //      stays free, so the kernels of another branch (the point branch of the bench step) are co-resident from the first millisecond instead of waiting for core waves to
 //      retire -- lines.hip picks it when the caller announced such a branch (sslam_lines_set_core_event); profiles/r06c_*: 160.5 ms per step against 167.5
+// The workgroup's LDS, one dynamic block: the region queue (first QCAP points), the addends of the ordered fp64 sums, cos / sin of the chunk's seed candidates.
+// 3 072 + 1 536 + 512 = 5 120 B = four allocation granules: gfx950 hands out LDS in steps of 1 280 B (tools/lds_granule_probe.hip: 32 single-wave workgroups per
+// compute unit are resident up to 5 120 B, 25 from 5 184 B, 21 from 6 464 B), and with 2 560 B static + 4 * (QCAP + 4) dynamic = 5 648 B the kernel held five.
+// region_grow_w stores to queue slot QCAP when the queue is full (the sink that spares the common case a branch): that is the first word of `red`, which is
+// dead while a region grows -- ordered_sums_add writes and consumes it within one call.
+constexpr int LSD_CORE_RED_WORDS = 3 * 64 * 2, LSD_CORE_CS_WORDS = 64 * 2;
+constexpr size_t LSD_CORE_LDS = sizeof(unsigned) * (QCAP + LSD_CORE_RED_WORDS + LSD_CORE_CS_WORDS);
+static_assert(QCAP % 4 == 0, "k_lsd_regions: the fp64 addends behind the queue must be 16-byte aligned");
+
 template <bool LAT, int MW>
 __global__ __launch_bounds__(64, MW) void k_lsd_regions(uint8_t* __restrict__ ws, LsdPlan P, const double* __restrict__ lgam, int nframes) {
-    extern __shared__ __align__(16) unsigned dynLds[];           // region queue (first QCAP points)
-    __shared__ double red[3 * 64];                                 // addends of the ordered fp64 sums
-    __shared__ float4 seedStash[64];                               // per seed candidate of the current chunk: angle, cos, sin, x | y << 16
+    extern __shared__ __align__(16) unsigned dynLds[];           // LSD_CORE_LDS bytes
+    double* red = (double*)(dynLds + QCAP);
+    float2* seedCs = (float2*)(dynLds + QCAP + LSD_CORE_RED_WORDS);
     // gridDim.x == nframes: one frame per workgroup.  A smaller grid makes the workgroups persistent: each takes the next unclaimed frame when it
     // has finished one (Misc::claim of frame 0, zeroed by k_zero_misc), and the wave slots the grid does not fill stay free for the other
     // branch's kernels for the whole launch
     int* claim = &((Misc*)(ws + P.offMisc))->claim;
     for (int i = blockIdx.x; i < nframes;) {
-        lsd_regions_body<LAT>(ws, P, xcd_mix_frame(i, nframes), dynLds, red, seedStash);
+        lsd_regions_body<LAT>(ws, P, xcd_mix_frame(i, nframes), dynLds, red, seedCs);
         if (gridDim.x >= (unsigned)nframes) break;
         int nxt = 0;
         if (threadIdx.x == 0) nxt = atomicAdd(claim, 1);

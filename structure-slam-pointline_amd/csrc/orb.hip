@@ -245,9 +245,26 @@ __device__ __forceinline__ int fast_score16(const uint8_t* c, int tp, int minTh)
     return s >= minTh ? s : 0;
 }
 
+// How many survivors of the pre-test (pass A) a cell keeps as a list; an entry is the pixel's index in the cell (i < 4 400 < 2^13, the bound the magic
+// division relies on too) and, from the suppression pass on, its keep-code in bits 13-14.  A condition, not a tuning result: the largest cell of the bench's 64 scenes and
+// their warped predecessors (eight kinds, eight levels, 104 320 cells; numpy replay of pass A, tests/test_guest_budget_gpu.py holds it) has 825 survivors of
+// 1 258 pixels, so 0 % of those cells exceed the cap.  A cell that does -- dense texture, noise -- is still exact: its list is scored and started again whenever the next
+// step's survivors (64 lanes x 4 pixels at most) do not fit, and suppression and emission walk its pixels instead of the list, in the same raster order.
+constexpr int FAST_LIST_CAP = 832;
+
+// Dynamic LDS of k_fast_cells for cells of up to maxW x maxH pixels: the image tile, the score tile and the list.  640 x 480, eight levels (cells of up to
+// 37 x 34): 2 080 + 1 372 + 1 664 = 5 116 B, four allocation granules of 1 280 B (tools/lds_granule_probe.hip); 7 290 B = six with a list entry and a code byte
+// for every pixel.  The score tile's rows are maxW + 1 wide: the zero rim to the right of one row is the zero rim to the left of the next.
+static inline int fast_tile_pitch(int maxW) { return (maxW + 6 + 3 + 7) & ~3; }
+static inline int fast_score_pitch(int maxW) { return maxW + 1; }
+static inline size_t fast_score_bytes(int maxW, int maxH) { return (((size_t)(maxH + 2) * fast_score_pitch(maxW) + 1) + 3) & ~(size_t)3; }
+static inline size_t fast_lds_bytes(int maxW, int maxH) {
+    return (size_t)(maxH + 6) * fast_tile_pitch(maxW) + fast_score_bytes(maxW, maxH) + sizeof(unsigned short) * FAST_LIST_CAP;
+}
+
 // One wave per (cell, frame).  LDS: image tile with 3-px halo (staged with aligned dword loads), score
-// tile with a zero rim (NMS neighbours outside the cell's detection rectangle count as 0, D.1), and a
-// keep-code per pixel.  Candidates leave in raster order, packed (score<<24 | y<<12 | x) with x,y
+// tile with a zero rim (NMS neighbours outside the cell's detection rectangle count as 0, D.1), and the
+// list of pass A's survivors.  Candidates leave in raster order, packed (score<<24 | y<<12 | x) with x,y
 // relative to minBorder (=16), :820-825.  i -> (row, col) uses an exact magic-multiply division.
 __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t* __restrict__ pyr, size_t pyrFrame, Plan P,
                                                    const CellInfo* __restrict__ cells,
@@ -267,8 +284,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t* __restrict__ p
     const LevelInfo& L = P.L[ci.level];
     const int cw = ci.x1 - ci.x0, ch = ci.y1 - ci.y0;
     uint8_t* tile = lds;                                       // (maxCellH+6) x tileP, tileP % 4 == 0
-    uint8_t* sc = tile + (P.maxCellH + 6) * tileP;             // (maxCellH+2) x scP
-    uint8_t* code = sc + (P.maxCellH + 2) * scP;               // maxCellH x maxCellW
+    uint8_t* sc = tile + (P.maxCellH + 6) * tileP;             // (maxCellH+2) x scP + 1, scP = maxCellW + 1 (fast_score_pitch)
     int pitch;
     const uint8_t* img = level_image(P, pyr, pyrFrame, b, ci.level, pitch);
     // stage rows [y0-3, y1+3) from the 4-byte aligned column ax <= x0-3; cells are interior (x0 >= 19, x1 + 3 <= w - 13) and the
@@ -284,7 +300,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t* __restrict__ p
             for (int q = q0; q < ndw; q += 16) ((unsigned*)(tile + ry * tileP))[q] = __builtin_amdgcn_raw_buffer_load_b32(rs, rowOff + 4 * q, 0, 0);
         }
     }
-    for (int i = lane; i < (((ch + 2) * scP + 3) >> 2); i += 64) ((unsigned*)sc)[i] = 0;
+    for (int i = lane; i < (((ch + 2) * scP + 1 + 3) >> 2); i += 64) ((unsigned*)sc)[i] = 0;
     __syncthreads();
     const unsigned magic = ci.magic;      // (1 << 19) / cw + 1: floor(i/cw) == (i*magic)>>19 for i < 4400, cw <= 64
     // pass A: necessary condition for a 9-arc at minTh, four pixels per lane on whole dwords.  Nine contiguous ring positions
@@ -294,16 +310,20 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t* __restrict__ p
     // Bytes are widened to two 16-bit halves per dword and compared with packed i16 arithmetic (sign bit of th -/+ (r - v)).
     // Survivors are compacted in raster order so that the expensive ring evaluation of pass B runs with full lanes on the few
     // pixels that can matter.
-    unsigned short* clist = (unsigned short*)(lds + (((P.maxCellH + 6) * tileP + (P.maxCellH + 2) * scP + P.maxCellH * P.maxCellW + 7) & ~3));
+    unsigned short* clist = (unsigned short*)(sc + (((P.maxCellH + 2) * scP + 1 + 3) & ~3));      // FAST_LIST_CAP entries
     int ncl = 0;
-    {
-        const int T0 = off + 3;                                    // tile column of pixel 0
-        const int gmin = T0 >> 2, ng = ((T0 + cw - 1) >> 2) - gmin + 1;
-        const unsigned gmagic = ci.gmagic;                          // (1 << 19) / ng + 1: ng <= 17, items < 4400
-        const int nitems = ch * ng;
+    bool dense = false;      // more survivors than the list holds (wave-uniform)
+    const int T0 = off + 3;                                        // tile column of pixel 0
+    const int gmin = T0 >> 2, ng = ((T0 + cw - 1) >> 2) - gmin + 1;
+    const unsigned gmagic = ci.gmagic;                              // (1 << 19) / ng + 1: ng <= 17, items < 4400
+    const int nitems = ch * ng;
+    // passes A and B take turns until A has seen every item: once for a cell whose survivors fit the list (every cell of the bench's scenes), else once per list filling
+    for (int it0 = 0;;) {
         const s16x2 th2 = {(short)minTh, (short)minTh};
-        for (int it0 = 0; it0 < nitems; it0 += 64) {
-            const int it = it0 + lane;
+        int la = lane;
+        asm volatile("" : "+v"(la));      // (what pass A derives from the lane is derived in here: hoisted out of the outer loop it would be live across pass B)
+        for (ncl = 0; it0 < nitems; it0 += 64) {
+            const int it = it0 + la;
             unsigned flags = 0;
             int py = 0, g = 0;
             if (it < nitems) {
@@ -339,56 +359,95 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t* __restrict__ p
             }
             const int cntf = __popc(flags);
             const int incl = wave_incl_scan(cntf);
+            const int tot = __builtin_amdgcn_readlane(incl, 63);
+            // the list cannot take this step's survivors (at most 256): score what it holds, start it again and compute the step a second time -- none of its
+            // registers is then live across the scoring, whose sixteen ring values set the kernel's register count
+            if (ncl + tot > FAST_LIST_CAP) { dense = true; break; }
             int pos = ncl + incl - cntf;
             const int ibase = __mul24(py, cw) + 4 * g - T0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) if (flags & (1u << k)) clist[pos++] = (unsigned short)(ibase + k);
-            ncl += __builtin_amdgcn_readlane(incl, 63);
+            ncl += tot;
         }
-    }
-    __syncthreads();
-    for (int j = lane; j < ncl; j += 64) {
-        const int i = clist[j];
-        const int py = (int)(__umul24((unsigned)i, magic) >> 19), px = i - __mul24(py, cw);
-        const int s = fast_score16(tile + __mul24(py + 3, tileP) + (off + px + 3), tileP, minTh);
-        if (s) sc[__mul24(py + 1, scP) + (px + 1)] = (uint8_t)s;        // sc is pre-zeroed
-    }
-    __syncthreads();
-    // NMS + thresholds + emission only visit the compacted list (it is in raster order, and so is what it emits)
-    int cnt20 = 0;
-    for (int j0 = 0; j0 < ncl; j0 += 64) {
-        const int j = j0 + lane;
-        int cde = 0;
-        if (j < ncl) {
+        __syncthreads();
+        // pass B: the FAST score of the listed pixels into the score tile
+        for (int j = lane; j < ncl; j += 64) {
             const int i = clist[j];
             const int py = (int)(__umul24((unsigned)i, magic) >> 19), px = i - __mul24(py, cw);
-            const uint8_t* c = sc + __mul24(py + 1, scP) + (px + 1);
-            // strict maximum of the 3 x 3 neighbourhood: the nine bytes are read together (one LDS round trip; as a chain of && the compiler made it eight dependent ones,
-            // a branch and a wait per neighbour) and "s > every neighbour" is "s > their maximum"
-            const int s = c[0];
-            const int n0 = c[-1], n1 = c[1], n2 = c[-scP - 1], n3 = c[-scP], n4 = c[-scP + 1], n5 = c[scP - 1], n6 = c[scP], n7 = c[scP + 1];
-            const int mx = max(max(max(n0, n1), max(n2, n3)), max(max(n4, n5), max(n6, n7)));
-            cde = (s > mx) ? (s >= iniTh ? 2 : 1) : 0;      // (s > mx >= 0 implies s > 0)
-            code[j] = (uint8_t)cde;
+            const int s = fast_score16(tile + __mul24(py + 3, tileP) + (off + px + 3), tileP, minTh);
+            if (s) sc[__mul24(py + 1, scP) + (px + 1)] = (uint8_t)s;        // sc is pre-zeroed
         }
-        cnt20 += __popcll(__ballot(cde == 2));
+        __syncthreads();
+        if (it0 >= nitems) break;
     }
-    __syncthreads();
-    const int need = cnt20 > 0 ? 2 : 1;      // FAST(iniTh) empty -> FAST(minTh), :809-816
+    // the keep-code of a pixel from the score tile: 0 = suppressed, 1 = a corner at minTh, 2 = a corner at iniTh.
+    // strict maximum of the 3 x 3 neighbourhood: the nine bytes are read together (one LDS round trip; as a chain of && the compiler made it eight dependent ones,
+    // a branch and a wait per neighbour) and "s > every neighbour" is "s > their maximum"
+    auto keep_code = [&](const uint8_t* c) -> int {
+        const int s = c[0];
+        const int n0 = c[-1], n1 = c[1], n2 = c[-scP - 1], n3 = c[-scP], n4 = c[-scP + 1], n5 = c[scP - 1], n6 = c[scP], n7 = c[scP + 1];
+        const int mx = max(max(max(n0, n1), max(n2, n3)), max(max(n4, n5), max(n6, n7)));
+        return (s > mx) ? (s >= iniTh ? 2 : 1) : 0;          // (s > mx >= 0 implies s > 0)
+    };
     unsigned* out = cand + (size_t)b * P.candFrame + ci.candOff;
-    int n = 0;
-    for (int j0 = 0; j0 < ncl; j0 += 64) {
-        const int j = j0 + lane;
-        bool keep = false;
-        if (j < ncl) keep = code[j] >= need;
-        unsigned long long m = __ballot(keep);
-        if (keep) {
-            const int i = clist[j];
-            const int py = (int)(__umul24((unsigned)i, magic) >> 19), px = i - __mul24(py, cw);
-            int s = sc[__mul24(py + 1, scP) + (px + 1)];
-            out[n + mbcnt(m)] = ((unsigned)s << 24) | ((unsigned)(ci.y0 + py - MINB) << 12) | (unsigned)(ci.x0 + px - MINB);
+    int cnt20 = 0, n = 0;
+    if (!dense) {
+        // NMS + thresholds + emission only visit the compacted list (it is in raster order, and so is what it emits)
+        for (int j0 = 0; j0 < ncl; j0 += 64) {
+            const int j = j0 + lane;
+            int cde = 0;
+            if (j < ncl) {
+                const int i = clist[j];
+                const int py = (int)(__umul24((unsigned)i, magic) >> 19), px = i - __mul24(py, cw);
+                cde = keep_code(sc + __mul24(py + 1, scP) + (px + 1));
+                clist[j] = (unsigned short)(i | (cde << 13));
+            }
+            cnt20 += __popcll(__ballot(cde == 2));
         }
-        n += __popcll(m);
+        __syncthreads();
+        const int need = cnt20 > 0 ? 2 : 1;      // FAST(iniTh) empty -> FAST(minTh), :809-816
+        for (int j0 = 0; j0 < ncl; j0 += 64) {
+            const int j = j0 + lane;
+            int e = 0;
+            if (j < ncl) e = clist[j];
+            const bool keep = (e >> 13) >= need;
+            unsigned long long m = __ballot(keep);
+            if (keep) {
+                const int i = e & 0x1FFF;
+                const int py = (int)(__umul24((unsigned)i, magic) >> 19), px = i - __mul24(py, cw);
+                int s = sc[__mul24(py + 1, scP) + (px + 1)];
+                out[n + mbcnt(m)] = ((unsigned)s << 24) | ((unsigned)(ci.y0 + py - MINB) << 12) | (unsigned)(ci.x0 + px - MINB);
+            }
+            n += __popcll(m);
+        }
+    } else {
+        // the list was started again: every pixel of the cell, in raster order.  A pixel that is not a corner has score 0 and keep-code 0, as if it had never been listed
+        const int npx = __mul24(ch, cw);
+        for (int i0 = 0; i0 < npx; i0 += 64) {
+            const int i = i0 + lane;
+            int cde = 0;
+            if (i < npx) {
+                const int py = (int)(__umul24((unsigned)i, magic) >> 19), px = i - __mul24(py, cw);
+                cde = keep_code(sc + __mul24(py + 1, scP) + (px + 1));
+            }
+            cnt20 += __popcll(__ballot(cde == 2));
+        }
+        const int need = cnt20 > 0 ? 2 : 1;
+        for (int i0 = 0; i0 < npx; i0 += 64) {
+            const int i = i0 + lane;
+            bool keep = false;
+            int py = 0, px = 0;
+            if (i < npx) {
+                py = (int)(__umul24((unsigned)i, magic) >> 19); px = i - __mul24(py, cw);
+                keep = keep_code(sc + __mul24(py + 1, scP) + (px + 1)) >= need;
+            }
+            unsigned long long m = __ballot(keep);
+            if (keep) {
+                int s = sc[__mul24(py + 1, scP) + (px + 1)];
+                out[n + mbcnt(m)] = ((unsigned)s << 24) | ((unsigned)(ci.y0 + py - MINB) << 12) | (unsigned)(ci.x0 + px - MINB);
+            }
+            n += __popcll(m);
+        }
     }
     if (lane == 0) cellCount[(size_t)b * P.nCellsFrame + cellId] = n;
 }
@@ -1261,8 +1320,8 @@ static int orb_front(sslam_orb* o, Plan& P, const uint8_t* d_images, int w, int 
     }
     if (o->gateEvent) SSLAM_HIP(hipStreamWaitEvent(st, o->gateEvent, 0));      // sslam_orb_set_gate_event: the pyramid is built ahead, the rest waits (e.g. for the line branch's sequential core)
     if (P.nCellsFrame > 0) {
-        int tileP = (P.maxCellW + 6 + 3 + 7) & ~3, scP = P.maxCellW + 2;
-        size_t lds = (size_t)(P.maxCellH + 6) * tileP + (((size_t)(P.maxCellH + 2) * scP + 3) & ~(size_t)3) + 3 * (size_t)P.maxCellH * P.maxCellW + 32;
+        const int tileP = fast_tile_pitch(P.maxCellW), scP = fast_score_pitch(P.maxCellW);
+        const size_t lds = fast_lds_bytes(P.maxCellW, P.maxCellH);
         dim3 grd(8 * ((P.nCellsFrame + 7) / 8), nframes);
         { sslam::ProfScope _ps(o->ctx, "k_fast_cells", st); hipLaunchKernelGGL(k_fast_cells, grd, dim3(64), lds, st, pyr, P.pyrFrame, P, o->dCells.as<CellInfo>(), o->dCand.as<unsigned>(),
                            o->dCellCount.as<int>(), o->iniTh, o->minTh, tileP, scP); }
