@@ -78,6 +78,30 @@ int sslam_testing_lines_tail(sslam_lines* ln, const uint8_t* gray, int w, int h,
  * product path reads them. */
 int sslam_testing_lines_last_forms(sslam_lines* ln, int32_t out[8]);
 
+/* The line prologue -- k_blur7 + k_lsd_grad or k_lsd_grad_fused, the gradient table behind them, and the counting sort of the seeds as k_lsd_hist + k_lsd_scan +
+ * k_lsd_scatter or k_lsd_hist_sort + k_lsd_scan + k_lsd_scatter_runs: LineSegmentDetectorImpl::flsd up to and including ll_angle (OpenCV imgproc lsd.cpp, reached from
+ * src/ExtractLineSegment.cpp:38-40) -- ALONE, with everything it leaves for region growing copied back, so that a test can compare those kernels with the oracle pixel for
+ * pixel and seed for seed instead of through the segments that come out three stages later.  `nframes` gray images of one size on the host (row pitch `stride`,
+ * `image_stride` bytes from frame to frame).  They are uploaded into the handle's image buffer in the layout the caller chooses: rows `dev_pitch` bytes apart (0: the
+ * 64-byte-aligned pitch sslam_lines_extract and the tail tap use; otherwise >= w), frames dev_pitch * h apart, the first pixel `dev_offset` (0 .. 3) bytes behind the
+ * buffer's 256-byte-aligned start -- the fused kernel takes dword-aligned layouts of its geometry only, so an offset of 1 sends such a frame through k_blur7 + k_lsd_grad.
+ * The choice itself is lines_prologue()'s, unchanged.  The call sets the words of sslam_testing_lines_last_forms to -1, runs lines_prepare, k_zero_misc and lines_prologue()
+ * -- the functions of sslam_lines_extract_batch_dev, nothing else -- which records words 2 (fused gradient) and 3 (tile-sorted runs; stays -1 under
+ * sslam_lines_set_seed_order(1)) as on the product path.  sslam_lines_set_resize_variant / _seed_order / _blur_variant apply as they do there.
+ * Outputs on the host, plane_cap pixels per frame (SSLAM_ERR_CAPACITY if the scaled image sw x sh = size_out[0] x size_out[1] holds more; size_out is valid then): with
+ * npx = sw * sh, t_out[nframes][npx] = the T plane (level-line angle in degrees, -1024 where undefined), s_out[nframes][npx] = S (|g|^2), cs_out[nframes][npx][2] = Cs
+ * (cos, sin), order_out[nframes][npx] = the seed list (x | y << 16), misc_out[nframes][2] = Misc::maxS, Misc::nDefined.  The T, S, Cs and seed list regions of every frame
+ * are filled with the byte 0xA5 after lines_prepare and before the first launch and copied back whole: a T pixel no kernel wrote, and every seed slot at or past nDefined,
+ * still hold it.  UNSPECIFIED, because the kernels write them for defined pixels only: S and Cs where T is -1024 (S is written everywhere under seed order 1, where the host
+ * sorts all pixels: there it is |g|^2 for x < sw - 1, y < sh - 1).  The handle must have been created by THIS library (lines_prepare uploads the library's __constant__
+ * tables once per handle); a sslam_lines_extract on it afterwards is an ordinary call. */
+int sslam_testing_lines_prologue(sslam_lines* ln, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, size_t dev_pitch, int dev_offset,
+                                 size_t plane_cap, int32_t size_out[2], float* t_out, int32_t* s_out, float* cs_out, uint32_t* order_out, int32_t* misc_out);
+/* The handle's gradient table as k_grad_table left it: tab_out[1021 * 1021][4], entry (gy + 510) * 1021 + (gx + 510) = {angle in degrees or -1024, cos, sin, the bits of
+ * gx^2 + gy^2} for every 2 x 2 gradient of an 8-bit image, and *smin_out = k_grad_smin's smallest |g|^2 of a defined pixel.  Built first (as the first plan of the handle
+ * would) if the handle has none. */
+int sslam_testing_lines_grad_table(sslam_lines* ln, float* tab_out, int32_t* smin_out);
+
 /* The ORB tail -- k_octree (DistributeOctTree, src/ORBextractor.cc:539-763) and k_describe (IC_Angle, the 7x7 blur, computeOrbDescriptor and the KeyPoint fill, :77-147,
  * :835-847, :1085-1101) -- on FAST candidates the CALLER supplies in place of k_fast_cells', so that a test can drive the two kernels at their own edges.  `nframes` gray
  * images of one size on the host (row pitch `stride`, `image_stride` bytes from frame to frame), uploaded the way sslam_orb_extract uploads its frame;

@@ -78,6 +78,19 @@ struct LsdTrace {
 };
 static_assert(sizeof(LsdTrace) == 64 * sizeof(int), "LsdTrace is 64 ints");
 
+// ll_angle's per-pixel expressions, ONE copy for the detector and for the exports orc_lsd_prologue / orc_lsd_grad_table: the gradient magnitude |g| / 2 of the 2 x 2
+// differences (gx, gy), whether it is above the threshold, and then the level-line angle in DEGREES (fast_atan2's value; ll_angle stores it times DEG_TO_RADS)
+struct LlPixel { double norm; bool defined; float deg; };
+static inline bool ll_defined(int s, double threshold, double& norm) { norm = std::sqrt(s / 4.0); return !(norm <= threshold); }      // s = gx * gx + gy * gy
+static inline LlPixel ll_pixel(int gx, int gy, double threshold) {
+    LlPixel q;
+    q.defined = ll_defined(gx * gx + gy * gy, threshold, q.norm);
+    q.deg = q.defined ? fast_atan2(float(gx), float(-gy)) : float(NOTDEF);
+    return q;
+}
+// the direction region_grow adds to its sums for a pixel it accepts, from the angle ll_angle stored for it (radians): decision D5
+static inline void grow_direction(double angle, float& c, float& s) { c = cr_cosf(float(angle)); s = cr_sinf(float(angle)); }
+
 struct Lsd {
     LsdTrace* tr = nullptr;               // orc_lsd_trace
     std::vector<int>* segCand = nullptr;  // per emitted segment, the ordinal of its candidate rectangle (regions past refine, seed order)
@@ -110,11 +123,12 @@ struct Lsd {
             for (int x = 0; x < w - 1; ++x) {
                 int DA = r1[x + 1] - r0[x], BC = r0[x + 1] - r1[x];
                 int gx = DA + BC, gy = DA - BC;
-                double norm = std::sqrt((gx * gx + gy * gy) / 4.0);
+                const LlPixel q = ll_pixel(gx, gy, threshold);
+                const double norm = q.norm;
                 modgrad[(size_t)y * w + x] = norm;
-                if (norm <= threshold) angles[(size_t)y * w + x] = NOTDEF;
+                if (!q.defined) angles[(size_t)y * w + x] = NOTDEF;
                 else {
-                    angles[(size_t)y * w + x] = fast_atan2(float(gx), float(-gy)) * DEG_TO_RADS;
+                    angles[(size_t)y * w + x] = q.deg * DEG_TO_RADS;
                     if (norm > max_grad) max_grad = norm;
                 }
             }
@@ -169,8 +183,9 @@ struct Lsd {
                         is_used = 1;
                         RegionPoint rp; rp.x = xx; rp.y = yy; rp.modgrad = modgrad[(size_t)yy * w + xx]; rp.angle = angle;
                         reg.push_back(rp);
-                        sumdx += cr_cosf(float(angle));       // D5
-                        sumdy += cr_sinf(float(angle));
+                        float dc, ds; grow_direction(angle, dc, ds);       // D5
+                        sumdx += dc;
+                        sumdy += ds;
                         reg_angle = fast_atan2(sumdy, sumdx) * DEG_TO_RADS;
                     }
                 }
@@ -403,11 +418,10 @@ struct Lsd {
         return leave(log_nfa);
     }
 
-    // LineSegmentDetectorImpl::flsd
-    void detect(const Img8& image, std::vector<Seg4f>& lines) {
-        lines.clear();
-        const double prec = M_PI * ANG_TH / 180, p = ANG_TH / 180;
-        const double rho = QUANT / std::sin(prec);
+    double rho() const { return QUANT / std::sin(M_PI * ANG_TH / 180); }          // ll_angle's threshold on |g| / 2
+
+    // flsd up to and including ll_angle: blur, 0.8x, gradient planes and the ordered seed list (detect() and orc_lsd_prologue)
+    void prologue(const Img8& image) {
         const double sigma = SIGMA_SCALE / SCALE;
         const double sprec = 3;
         const unsigned hk = (unsigned)(std::ceil(sigma * std::sqrt(2 * sprec * std::log(10.0))));
@@ -415,7 +429,14 @@ struct Lsd {
         // D7; its alternative (orc_set_lsd_resize(1), error bar only): plain INTER_LINEAR, the 11-bit fixed-point resize of the ORB pyramid, with the same output size
         scaled = g_lsdResize == 1 ? resize_linear_8u(g, cv_round(g.w * SCALE), cv_round(g.h * SCALE)) : resize_linear_exact_8u(g, SCALE, SCALE);
         w = scaled.w; h = scaled.h;
-        ll_angle(rho);
+        ll_angle(rho());
+    }
+
+    // LineSegmentDetectorImpl::flsd
+    void detect(const Img8& image, std::vector<Seg4f>& lines) {
+        lines.clear();
+        const double prec = M_PI * ANG_TH / 180, p = ANG_TH / 180;
+        prologue(image);
         LOG_NT = 5 * (std::log10(double(w)) + std::log10(double(h))) / 2 + std::log10(11.0);
         const size_t min_reg_size = size_t(-LOG_NT / std::log10(p));
         used.assign((size_t)w * h, 0);
@@ -529,6 +550,64 @@ extern "C" int orc_lsd_trace(const uint8_t* gray, int w, int h, size_t stride, i
         if (cand_out) cand_out[i] = sc[i];
     }
     return n;
+}
+// What flsd leaves for region growing (Lsd::prologue), under orc_set_lsd_resize / orc_set_lsd_seed_sort as every other entry.  size_out[2] = scaled width and height; with
+// planes to fill (any of them may be null; a first call with all null asks for the size): per scaled pixel deg_out = the level-line angle in degrees (fast_atan2's value
+// before `* DEG_TO_RADS`; -1024 where undefined: also the last row and column), s_out = gx * gx + gy * gy (0 in the last row and column), cs_out = the (cos, sin) pair
+// region_grow adds for the pixel (0, 0 where undefined); order_out = the seed list restricted to DEFINED pixels in the order ll_angle leaves it, as y * sw + x;
+// stat_out[2] = the largest |g|^2 of a defined pixel (0: none) and the defined count (= the return value).
+extern "C" int orc_lsd_prologue(const uint8_t* gray, int w, int h, size_t stride, int32_t* size_out, float* deg_out, int32_t* s_out, float* cs_out, int32_t* order_out,
+                                int32_t* stat_out) {
+    Img8 im(w, h);
+    for (int y = 0; y < h; ++y) std::memcpy(im.row(y), gray + (size_t)y * stride, (size_t)w);
+    Lsd lsd;
+    lsd.prologue(im);
+    const int sw = lsd.w, sh = lsd.h;
+    if (size_out) { size_out[0] = sw; size_out[1] = sh; }
+    const double rho = lsd.rho();
+    int maxS = 0;
+    for (int y = 0; y < sh; ++y)
+        for (int x = 0; x < sw; ++x) {
+            const size_t i = (size_t)y * sw + x;
+            float deg = float(NOTDEF), c = 0.f, sn = 0.f; int s = 0;
+            if (y < sh - 1 && x < sw - 1) {          // ll_angle's own loop bounds and differences
+                const uint8_t* r0 = lsd.scaled.row(y); const uint8_t* r1 = lsd.scaled.row(y + 1);
+                const int DA = r1[x + 1] - r0[x], BC = r0[x + 1] - r1[x];
+                const int gx = DA + BC, gy = DA - BC;
+                s = gx * gx + gy * gy;
+                const LlPixel q = ll_pixel(gx, gy, rho);
+                if (q.defined != (lsd.angles[i] != NOTDEF) || (q.defined && lsd.angles[i] != q.deg * DEG_TO_RADS)) return -1;      // (the export describes the detector's planes)
+                if (q.defined) { deg = q.deg; grow_direction(lsd.angles[i], c, sn); if (s > maxS) maxS = s; }
+            } else if (lsd.angles[i] != NOTDEF) return -1;
+            if (deg_out) deg_out[i] = deg;
+            if (s_out) s_out[i] = s;
+            if (cs_out) { cs_out[2 * i] = c; cs_out[2 * i + 1] = sn; }
+        }
+    int n = 0;
+    for (const int idx : lsd.order)
+        if (lsd.angles[idx] != NOTDEF) { if (order_out) order_out[n] = idx; ++n; }
+    if (stat_out) { stat_out[0] = maxS; stat_out[1] = n; }
+    return n;
+}
+// ll_pixel and grow_direction over every gradient an 8-bit image can give: tab_out[(gy + 510) * 1021 + (gx + 510)][4] = angle in degrees (-1024: undefined), cos, sin (0 where
+// undefined) and gx * gx + gy * gy as an integer's bit pattern; *smin_out = the smallest defined |g|^2 as a threshold: the smallest INTEGER s the defined test accepts (the
+// test is monotone in s, so "defined" is "s >= *smin_out"; the smallest s a gradient can actually take may lie above it, a sum of two squares)
+extern "C" int orc_lsd_grad_table(float* tab_out, int32_t* smin_out) {
+    const double rho = Lsd().rho();
+    int smin = 0; double nrm;
+    while (!ll_defined(smin, rho, nrm)) ++smin;
+    for (int gy = -510; gy <= 510; ++gy)
+        for (int gx = -510; gx <= 510; ++gx) {
+            const LlPixel q = ll_pixel(gx, gy, rho);
+            const int32_t s = gx * gx + gy * gy;
+            float c = 0.f, sn = 0.f;
+            if (q.defined) grow_direction(q.deg * DEG_TO_RADS, c, sn);
+            if (q.defined != (s >= smin)) return -1;
+            float* o = tab_out + 4 * ((size_t)(gy + 510) * 1021 + (size_t)(gx + 510));
+            o[0] = q.deg; o[1] = c; o[2] = sn; std::memcpy(o + 3, &s, sizeof(s));
+        }
+    if (smin_out) *smin_out = smin;
+    return 0;
 }
 extern "C" double orc_log_gamma(double x) { return log_gamma(x); }
 extern "C" int orc_sobel3(const uint8_t* src, int w, int h, int16_t* gx, int16_t* gy) {

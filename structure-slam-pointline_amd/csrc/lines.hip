@@ -118,6 +118,27 @@ static std::vector<int> taps_340(int n, double sigma) {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// ll_angle's threshold on |g| / 2: it depends on LSD's constants alone, so the gradient table below is built once per handle, whatever the image size
+constexpr double LSD_ANG_TH = 22.5, LSD_QUANT = 2.0;
+static double lsd_rho() { return LSD_QUANT / std::sin(kPI * LSD_ANG_TH / 180); }
+
+// gradient -> {angle, cos, sin, |g|^2} table, and the smallest defined |g|^2 behind it, unless the handle has them (lines_build_plan; in the testing library
+// sslam_testing_lines_grad_table reads them back)
+static int lines_grad_table(sslam_lines* L) {
+    if (L->dGtab.p) return SSLAM_OK;
+    int rc;
+    const double rho = lsd_rho();
+    if ((rc = L->dGtab.ensure(sizeof(float4) * ((size_t)GT * GT + 1)))) return rc;
+    int* dSmin = (int*)(L->dGtab.as<float4>() + (size_t)GT * GT);
+    const int big = 0x7FFFFFFF;
+    SSLAM_HIP(hipMemcpy(dSmin, &big, sizeof(int), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_grad_table, dim3((GT * GT + 255) / 256), dim3(256), 0, L->ctx->stream, L->dGtab.as<float4>(), rho);
+    hipLaunchKernelGGL(k_grad_smin, dim3((2 * 510 * 510 + 256) / 256), dim3(256), 0, L->ctx->stream, dSmin, rho);
+    SSLAM_HIP(hipStreamSynchronize(L->ctx->stream));
+    SSLAM_HIP(hipMemcpy(&L->sMin, dSmin, sizeof(int), hipMemcpyDeviceToHost));
+    return SSLAM_OK;
+}
+
 // The plan is built in a local and assigned on success.  A size that is refused (the checks up to the first upload touch nothing of the handle) leaves the previous plan, its
 // workspace and the last batch's results as they were: the next call at the previous size runs on the plan it was built for.  From the first upload on the handle holds no
 // plan (planW = planH = 0) until the new one is complete, so a failure in between makes the next call build again.
@@ -135,9 +156,9 @@ static int lines_build_plan(sslam_lines* L, int w, int h) {
     P.tileRows = std::min(64, std::max(1, TILE_PX / P.sw));
     P.nTiles = (P.sh + P.tileRows - 1) / P.tileRows;
     if (P.tileRows * P.nXB > MAX_TSEG) { set_error("image %dx%d: too many segments per counting-sort tile", w, h); return SSLAM_ERR_UNSUPPORTED; }
-    const double ANG_TH = 22.5, QUANT = 2.0, SIGMA_SCALE = 0.6;
+    const double ANG_TH = LSD_ANG_TH, SIGMA_SCALE = 0.6;
     P.prec = kPI * ANG_TH / 180; P.p = ANG_TH / 180;
-    P.rho = QUANT / std::sin(P.prec);
+    P.rho = lsd_rho();
     P.logNT = 5 * (std::log10((double)P.sw) + std::log10((double)P.sh)) / 2 + std::log10(11.0);
     P.minRegSize = (int)(size_t)(-P.logNT / std::log10(P.p));
     const double sigma = SIGMA_SCALE / SCALE;
@@ -211,16 +232,7 @@ static int lines_build_plan(sslam_lines* L, int w, int h) {
     P.offKl = take(sizeof(sslam_keyline) * MAX_SEG);
     P.offLbdDir = take(sizeof(float2) * MAX_SEG);            // (cos, sin) of every output line's direction: k_keylines -> k_lbd
     P.frameBytes = align_up(off, 4096);
-    if (!L->dGtab.p) {   // gradient -> {angle, cos, sin, |g|^2} table (rho depends only on LSD constants), and the smallest defined |g|^2 behind it
-        if ((rc = L->dGtab.ensure(sizeof(float4) * ((size_t)GT * GT + 1)))) return rc;
-        int* dSmin = (int*)(L->dGtab.as<float4>() + (size_t)GT * GT);
-        const int big = 0x7FFFFFFF;
-        SSLAM_HIP(hipMemcpy(dSmin, &big, sizeof(int), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_grad_table, dim3((GT * GT + 255) / 256), dim3(256), 0, L->ctx->stream, L->dGtab.as<float4>(), P.rho);
-        hipLaunchKernelGGL(k_grad_smin, dim3((2 * 510 * 510 + 256) / 256), dim3(256), 0, L->ctx->stream, dSmin, P.rho);
-        SSLAM_HIP(hipStreamSynchronize(L->ctx->stream));
-        SSLAM_HIP(hipMemcpy(&L->sMin, dSmin, sizeof(int), hipMemcpyDeviceToHost));
-    }
+    if ((rc = lines_grad_table(L))) return rc;
     P.sMin = L->sMin;
     {   // log-gamma table for nfa(): arguments are integers in [1, npx+2]
         const int nl = P.npx + 4;
@@ -421,6 +433,9 @@ static void lines_blur_sobel(const LinesCall& c, hipStream_t s) {
 
 // The prologue: blur(7, 0.75) -> 0.8x -> gradient, then the seeds in order.  The fused blur + gradient kernel where the plan admits it (lines_build_plan) and the tile-sorted
 // runs where a sorted entry's packing fits (scaled image up to 2048 x 2048); k_blur7 + k_lsd_grad and k_lsd_hist + k_lsd_scatter for every other geometry.
+// What it leaves per frame -- the T, S and Cs planes, Misc::maxS / nDefined and the ordered seed list at offOrder -- is read back by the testing library's
+// sslam_testing_lines_prologue (below; include/sslam_testing.h), which runs lines_prepare, k_zero_misc and this function and nothing else: tests/test_lsd_head_gpu.py
+// compares every pixel and every seed with the oracle.
 static int lines_prologue(const LinesCall& c) {
     sslam_lines* L = c.L; const LsdPlan& P = c.P; hipStream_t st = c.st;
     const int* taps = L->dTaps.as<int>();
@@ -805,6 +820,71 @@ extern "C" int sslam_testing_lines_tail(sslam_lines* L, const uint8_t* gray, int
         for (int b = 0; b < nframes; ++b)
             SSLAM_HIP(hipMemcpyAsync(lbd_dir_out + (size_t)b * cap * 2, c.ws + (size_t)b * P.frameBytes + P.offLbdDir, sizeof(float2) * (size_t)cap, hipMemcpyDeviceToHost, st));
     SSLAM_HIP(hipStreamSynchronize(st));
+    return SSLAM_OK;
+}
+
+// The line prologue alone (include/sslam_testing.h): the upload in the layout the caller chooses, the preparation of sslam_lines_extract_batch_dev (lines_prepare),
+// k_zero_misc and lines_prologue() -- the product path's own function -- then the planes, the seed list and the two scalars of every frame copied back.
+extern "C" int sslam_testing_lines_prologue(sslam_lines* L, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, size_t dev_pitch,
+                                            int dev_offset, size_t plane_cap, int32_t* size_out, float* t_out, int32_t* s_out, float* cs_out, uint32_t* order_out,
+                                            int32_t* misc_out) {
+    if (!L || !gray || !size_out || !t_out || !s_out || !cs_out || !order_out || !misc_out || w <= 0 || h <= 0 || nframes <= 0 || stride < (size_t)w ||
+        (dev_pitch != 0 && dev_pitch < (size_t)w) || dev_offset < 0 || dev_offset > 3) {
+        set_error("sslam_testing_lines_prologue: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (nframes > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w) { set_error("sslam_testing_lines_prologue: the frames overlap"); return SSLAM_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
+    for (int& f : L->lastForms) f = -1;
+    SSLAM_HIP(hipSetDevice(L->ctx->device));
+    hipStream_t st = L->ctx->stream;
+    int rc;
+    const size_t dpitch = dev_pitch ? dev_pitch : (((size_t)w + 63) & ~(size_t)63), dframe = dpitch * h;
+    if ((rc = L->dImg.ensure((size_t)dev_offset + dframe * nframes + 64))) return rc;      // (64: the offset and a dword read that starts inside the last row stay in the buffer)
+    L->lastN = -1;      // (the buffers of the last sslam_lines_extract are overwritten)
+    uint8_t* dimg = L->dImg.as<uint8_t>() + dev_offset;
+    for (int b = 0; b < nframes; ++b)
+        SSLAM_HIP(hipMemcpy2DAsync(dimg + (size_t)b * dframe, dpitch, gray + (size_t)b * image_stride, stride, w, h, hipMemcpyHostToDevice, st));
+    if ((rc = lines_prepare(L, w, h, nframes, st))) return rc;
+    const LsdPlan& P = L->plan;
+    size_out[0] = P.sw; size_out[1] = P.sh;
+    const size_t npx = (size_t)P.npx;
+    if (npx > plane_cap) { (void)hipStreamSynchronize(st); set_error("sslam_testing_lines_prologue: %d x %d scaled pixels per frame, the output planes hold %zu", P.sw, P.sh, plane_cap); return SSLAM_ERR_CAPACITY; }
+    const LinesCall c{L, P, dimg, dpitch, dframe, nframes, st, L->dWs.as<uint8_t>()};
+    for (int b = 0; b < nframes; ++b) {      // what a kernel does not write still holds 0xA5 afterwards
+        uint8_t* base = c.ws + (size_t)b * P.frameBytes;
+        SSLAM_HIP(hipMemsetAsync(base + P.offT, 0xA5, sizeof(float) * npx, st));
+        SSLAM_HIP(hipMemsetAsync(base + P.offS, 0xA5, sizeof(int) * npx, st));
+        SSLAM_HIP(hipMemsetAsync(base + P.offCs, 0xA5, sizeof(float2) * npx, st));
+        SSLAM_HIP(hipMemsetAsync(base + P.offOrder, 0xA5, sizeof(unsigned) * npx, st));
+    }
+    hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c.ws, P);
+    if ((rc = lines_prologue(c))) return rc;
+    SSLAM_HIP(hipGetLastError());
+    L->lastFrames = nframes;
+    std::vector<Misc> hm((size_t)nframes);      // (alive until the stream is idle)
+    for (int b = 0; b < nframes; ++b) {
+        const uint8_t* base = c.ws + (size_t)b * P.frameBytes;
+        SSLAM_HIP(hipMemcpyAsync(t_out + (size_t)b * npx, base + P.offT, sizeof(float) * npx, hipMemcpyDeviceToHost, st));
+        SSLAM_HIP(hipMemcpyAsync(s_out + (size_t)b * npx, base + P.offS, sizeof(int) * npx, hipMemcpyDeviceToHost, st));
+        SSLAM_HIP(hipMemcpyAsync(cs_out + (size_t)b * npx * 2, base + P.offCs, sizeof(float2) * npx, hipMemcpyDeviceToHost, st));
+        SSLAM_HIP(hipMemcpyAsync(order_out + (size_t)b * npx, base + P.offOrder, sizeof(unsigned) * npx, hipMemcpyDeviceToHost, st));
+        SSLAM_HIP(hipMemcpyAsync(&hm[b], base + P.offMisc, sizeof(Misc), hipMemcpyDeviceToHost, st));
+    }
+    SSLAM_HIP(hipStreamSynchronize(st));
+    for (int b = 0; b < nframes; ++b) { misc_out[2 * b] = hm[b].maxS; misc_out[2 * b + 1] = hm[b].nDefined; }
+    return SSLAM_OK;
+}
+
+// the handle's gradient table (k_grad_table) and the smallest defined |g|^2 behind it (k_grad_smin), built first if the handle has none
+extern "C" int sslam_testing_lines_grad_table(sslam_lines* L, float* tab_out, int32_t* smin_out) {
+    if (!L || !tab_out || !smin_out) { set_error("sslam_testing_lines_grad_table: invalid arguments"); return SSLAM_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
+    SSLAM_HIP(hipSetDevice(L->ctx->device));
+    int rc;
+    if ((rc = lines_grad_table(L))) return rc;
+    SSLAM_HIP(hipStreamSynchronize(L->ctx->stream));
+    SSLAM_HIP(hipMemcpy(tab_out, L->dGtab.p, sizeof(float4) * (size_t)GT * GT, hipMemcpyDeviceToHost));
+    SSLAM_HIP(hipMemcpy(smin_out, L->dGtab.as<float4>() + (size_t)GT * GT, sizeof(int), hipMemcpyDeviceToHost));
     return SSLAM_OK;
 }
 

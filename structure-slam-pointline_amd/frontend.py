@@ -747,6 +747,75 @@ class LineExtractor:
             self.h = C.c_void_p()
 
 
+class LinePrologue:
+    """A sslam_lines handle of the TESTING library (lines_prepare uploads that library's constant tables once per handle) with the two taps of the line prologue,
+    sslam_testing_lines_prologue and sslam_testing_lines_grad_table (include/sslam_testing.h), and sslam_lines_extract on the same handle."""
+
+    def __init__(self, ctx, max_lines=40):
+        self.T = testing_lib()
+        self.T.sslam_testing_lines_prologue.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_size_t] + [C.c_void_p] * 6
+        self.T.sslam_testing_lines_grad_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.h = C.c_void_p()
+        self._chk(self.T.sslam_lines_create(ctx.h, int(max_lines), C.byref(self.h)))
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise SslamError("%s: %s" % (self.T.sslam_status_str(rc).decode(), self.T.sslam_last_error().decode()), rc)
+
+    def __enter__(self): return self
+
+    def __exit__(self, *a): self.close()
+
+    def __call__(self, images, dev_pitch=0, dev_offset=0):
+        """images [n, h, w] uint8 (any strides with contiguous rows) -> list of n dicts(sw, sh, T [sh, sw] float32, S [sh, sw] int32, Cs [sh, sw, 2] float32,
+        order [sw * sh] uint32 as x | y << 16, max_s, n_defined): the planes and the seed list copied back WHOLE (0xA5 where no kernel wrote)"""
+        images = np.asarray(images, np.uint8)
+        n, h, w = images.shape
+        assert images.strides[2] == 1
+        sw, sh = int(round(w * 0.8)), int(round(h * 0.8))
+        cap = (sw + 1) * (sh + 1)          # (the library's own rounding decides: size_out)
+        size = np.zeros(2, np.int32); T = np.zeros((n, cap), np.float32); S = np.zeros((n, cap), np.int32); Cs = np.zeros((n, cap, 2), np.float32)
+        order = np.zeros((n, cap), np.uint32); misc = np.zeros((n, 2), np.int32)
+        self._chk(self.T.sslam_testing_lines_prologue(self.h, images.ctypes.data, w, h, images.strides[1], images.strides[0], n, int(dev_pitch), int(dev_offset), cap,
+                                                      size.ctypes.data, T.ctypes.data, S.ctypes.data, Cs.ctypes.data, order.ctypes.data, misc.ctypes.data))
+        assert (int(size[0]), int(size[1])) == (sw, sh), (size, sw, sh)
+        npx = sw * sh          # (a frame's arrays are npx long in the library's layout: frame b starts at b * npx)
+        T, S, Cs, order = (a.reshape(-1)[:n * npx * k].reshape((n, npx) + ((2,) if k == 2 else ())) for a, k in ((T, 1), (S, 1), (Cs, 2), (order, 1)))
+        return [dict(sw=sw, sh=sh, T=T[b].reshape(sh, sw), S=S[b].reshape(sh, sw), Cs=Cs[b].reshape(sh, sw, 2), order=order[b], max_s=int(misc[b, 0]),
+                     n_defined=int(misc[b, 1])) for b in range(n)]
+
+    def grad_table(self):
+        """-> (k_grad_table's table [1021, 1021, 4] float32 indexed [gy + 510, gx + 510], k_grad_smin's smallest defined |g|^2)"""
+        tab = np.zeros((1021, 1021, 4), np.float32); smin = C.c_int32(0)
+        self._chk(self.T.sslam_testing_lines_grad_table(self.h, tab.ctypes.data, C.addressof(smin)))
+        return tab, smin.value
+
+    def last_forms(self):
+        """words 2 and 3 of sslam_testing_lines_last_forms as (fused_grad, sort_runs): True / False, None where the call did not get there"""
+        o = (C.c_int32 * 8)()
+        self._chk(self.T.sslam_testing_lines_last_forms(self.h, o))
+        return tuple(bool(v) if v >= 0 else None for v in (o[2], o[3]))
+
+    def set_resize_variant(self, variant): self._chk(self.T.sslam_lines_set_resize_variant(self.h, int(variant)))
+
+    def set_seed_order(self, variant): self._chk(self.T.sslam_lines_set_seed_order(self.h, int(variant)))
+
+    def extract(self, gray, cap=8192):
+        """sslam_lines_extract on this handle -> (keylines, LBD rows, line equations, the segments before the top-N)"""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        h, w = gray.shape
+        kl = np.zeros(cap, KL_DTYPE); ld = np.zeros((cap, 32), np.uint8); fn = np.zeros((cap, 3), np.float64); n = C.c_int(0)
+        self._chk(self.T.sslam_lines_extract(self.h, _p(gray), w, h, C.c_size_t(gray.strides[0]), _p(kl), _p(ld), _p(fn), cap, C.byref(n)))
+        seg = np.zeros((20000, 4), np.float32); m = C.c_int(0)
+        self._chk(self.T.sslam_lines_debug_segments(self.h, 0, _p(seg), len(seg), C.byref(m)))
+        return kl[:n.value].copy(), ld[:n.value].copy(), fn[:n.value].copy(), seg[:m.value].copy()
+
+    def close(self):
+        if self.h:
+            self.T.sslam_lines_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 # ---- multi-GPU batch mode (include/sslam_frontend.h: sslam_group_*, record stream) ------------------------------------------------
 class FrontendParams(C.Structure):
     _fields_ = [("nfeatures", C.c_int32), ("scale_factor", C.c_float), ("nlevels", C.c_int32), ("ini_th_fast", C.c_int32),

@@ -385,7 +385,39 @@ def _orc_line_methods():
         assert 0 <= n <= cap
         return {k: int(v) for k, v in zip(LSD_TRACE, tr)}, seg[:n].copy(), cand[:n].copy()
 
-    for f in (lines_extract, lsd_scaled, lines_tail, lbd_from_keylines, lsd_trace):
+    def set_lsd_resize(self, v):
+        """0: decision D7 (INTER_LINEAR_EXACT); 1: INTER_LINEAR.  Process-global; returns the previous value."""
+        return int(self.L.orc_set_lsd_resize(int(v)))
+
+    def set_lsd_seed_sort(self, v):
+        """0: decision D2 (raster order inside a bin); 1: upstream's std::sort.  Process-global; returns the previous value."""
+        return int(self.L.orc_set_lsd_seed_sort(int(v)))
+
+    def lsd_prologue(self, gray):
+        """orc_lsd_prologue: what the detector leaves for region growing, under the resize / seed sort variants in force -> dict(sw, sh, deg [sh, sw] float32 (-1024 where
+        undefined), S [sh, sw] int32, cs [sh, sw, 2] float32, order = the defined pixels in seed order as y * sw + x, max_s, n_defined)"""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        h, w = gray.shape
+        self.L.orc_lsd_prologue.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t] + [C.c_void_p] * 6
+        size = np.zeros(2, np.int32); st = np.zeros(2, np.int32)
+        n = self.L.orc_lsd_prologue(_p(gray), w, h, gray.strides[0], _p(size), None, None, None, None, _p(st))
+        assert n >= 0, "orc_lsd_prologue: the export disagrees with the detector's planes"
+        sw, sh = int(size[0]), int(size[1])
+        deg = np.zeros((sh, sw), np.float32); S = np.zeros((sh, sw), np.int32); cs = np.zeros((sh, sw, 2), np.float32); order = np.zeros(max(n, 1), np.int32)
+        assert self.L.orc_lsd_prologue(_p(gray), w, h, gray.strides[0], _p(size), _p(deg), _p(S), _p(cs), _p(order), _p(st)) == n == st[1]
+        out = dict(sw=sw, sh=sh, deg=deg, S=S, cs=cs, order=order[:n].copy(), max_s=int(st[0]), n_defined=n)
+        for a in (deg, S, cs, out["order"]): a.setflags(write=False)
+        return out
+
+    def lsd_grad_table(self):
+        """orc_lsd_grad_table -> (table [1021, 1021, 4] float32: angle in degrees or -1024, cos, sin, the bits of gx^2 + gy^2; indexed [gy + 510, gx + 510]), the smallest
+        integer |g|^2 the defined test accepts"""
+        tab = np.zeros((1021, 1021, 4), np.float32); smin = C.c_int32(0)
+        self.L.orc_lsd_grad_table.argtypes = [C.c_void_p, C.c_void_p]
+        assert self.L.orc_lsd_grad_table(_p(tab), C.byref(smin)) == 0
+        return tab, smin.value
+
+    for f in (lines_extract, lsd_scaled, lines_tail, lbd_from_keylines, lsd_trace, set_lsd_resize, set_lsd_seed_sort, lsd_prologue, lsd_grad_table):
         setattr(Oracle, f.__name__, f)
 
 
