@@ -477,7 +477,7 @@ int sslam_orb_search_by_bow(sslam_ctx* ctx, const sslam_keypoint* kf_kp, const u
                             const int32_t* node_kf_ptr, const int32_t* node_f_ptr, int nnodes,
                             const int32_t* kf_idx, const int32_t* f_idx, float nnratio, int check_orientation,
                             int32_t* assigned_out, int* nmatches_out);
-/* The same matcher (src/ORBmatcher.cc:159-291, the KeyFrame -> Frame overload only) for `npairs` pairs of device-resident frames,
+/* The same matcher (src/ORBmatcher.cc:159-291, the KeyFrame -> Frame overload; sslam_orb_search_by_bow_keyframes_batch_dev is the KeyFrame -> KeyFrame one) for `npairs` pairs of device-resident frames,
  * asynchronously, from per-feature node ids instead of CSR lists: the batch form of Tracking::TrackReferenceKeyFrame (src/Tracking.cc:1009-1020,
  * one reference keyframe per session) and of Tracking::Relocalization (src/Tracking.cc:1964-1996, one frame against K candidate keyframes).
  * Keyframe slot k owns rows [k*kfcap, k*kfcap + d_nkf[k]) of d_kf_kp, d_kf_desc (32 bytes per row), d_kf_node and d_kf_valid
@@ -510,6 +510,40 @@ int sslam_orb_search_by_bow_keyframes(sslam_ctx* ctx, const sslam_keypoint* kf1_
                                       const int32_t* node_kf1_ptr, const int32_t* node_kf2_ptr, int nnodes,
                                       const int32_t* kf1_idx, const int32_t* kf2_idx, float nnratio, int check_orientation,
                                       int32_t* matches12_out, int* nmatches_out);
+/* The same matcher (src/ORBmatcher.cc:525-658) for `npairs` pairs of device-resident keyframes, asynchronously, from per-feature node ids instead of
+ * CSR lists: the first matcher of LoopClosing::ComputeSim3 (src/LoopClosing.cc:256-285: the current keyframe against every consistent candidate,
+ * ORBmatcher(0.75, true), `nmatches < 20` discards the candidate), for callers that keep many sessions' keyframes on the device.  With it every
+ * public matcher of ORBmatcher and LSDmatcher has a batch form: the two matchers behind this one in ComputeSim3 are sslam_fuse_search_batch_dev
+ * (SearchBySim3, :328) and mode 1 of sslam_search_by_projection_batch_dev (:380).
+ * The pool is sslam_orb_search_for_triangulation_batch_dev's: keyframe slot k owns rows [k*cap, k*cap + d_n[k]) of d_kp (mvKeysUn), d_desc (32 bytes
+ * per row), d_node (what sslam_bow_transform_batch_dev writes to d_node; an id below 0 is in no node) and d_valid (= GetMapPoint(i) && !isBad();
+ * NULL: every row is valid).  A count below 0 is read as 0, one above cap as cap; nothing at or past a count is read.
+ * d_pairs holds npairs x 2 int32: pair p is (kf1, kf2) = (d_pairs[2p], d_pairs[2p+1]), kf1 is pKF1 (the side the result is indexed by), kf2 is pKF2
+ * (the candidates).  kf1 == kf2 is legal and computed like any other pair; a slot may appear in any number of pairs.  A pair with a slot outside
+ * [0, nkeyframes) is skipped: d_nmatches[p] = 0 and nothing else of the pair is written.
+ * Pair p yields exactly what sslam_orb_search_by_bow_keyframes returns for the two FeatureVectors FeatureVector::addFeature(node[i], i) builds in
+ * feature order from the two node arrays.  d_matches12[p*cap + i1], i1 < n[kf1], = the keyframe-2 row whose map point goes into vpMatches12[i1], or
+ * -1, after the rotation pruning; d_nmatches[p] = the count after the pruning.  d_matches21[p*cap + i2], i2 < n[kf2], = the keyframe-1 row that
+ * holds keyframe-2 row i2, or -1: the inverse of the pair's d_matches12 rows after the pruning (the reference's vbMatched2 with its owner).  It is a
+ * required output, and where keyframe 2 does not fit the LDS it is also where the call keeps its live state, which is why there is no scratch.  Rows
+ * at or past a count are not touched in either array.
+ * Unlike the KeyFrame -> Frame batch above: the result is indexed by keyframe 1; keyframe 2 has validity flags, and an invalid or already taken
+ * keyframe-2 row is skipped before its distance is looked at (:577-583), so it is neither best nor second best; the distance gate is strict,
+ * bestDist1 < TH_LOW (:601); the ratio test is (float)bestDist1 < nnratio * (float)bestDist2 with bestDist2 = 256 when there is no second (:603);
+ * the rotation bin is that of kp1.angle - kp2.angle (:610), one histogram entry per matched keyframe-1 row.
+ * WHY ONE CALL IS EXACT for any pair list: the reference function writes nothing but its own output vector and its local vbMatched2, so the K
+ * candidates of one current keyframe are K independent pairs.  (sslam_orb_search_for_triangulation_batch_dev is different: its free flags change
+ * between the neighbours of one keyframe, so it needs one call per round.)
+ * Every pointer is a device pointer; d_desc is 16-byte aligned, the typed buffers 4-byte aligned.  One launch on `stream` (NULL: the context's
+ * stream), no scratch, no synchronise, no host memory read or written; independent of every other call on the context.  SSLAM_ERR_INVALID (nothing
+ * enqueued): a NULL ctx, d_kp, d_desc, d_node, d_n, d_pairs, d_matches12, d_matches21 or d_nmatches, a misaligned buffer, a negative cap, nkeyframes
+ * or npairs, cap >= 2^19, npairs * cap >= 2^31.  npairs == 0 is SSLAM_OK and enqueues nothing. */
+int sslam_orb_search_by_bow_keyframes_batch_dev(sslam_ctx* ctx,
+                                                const sslam_keypoint* d_kp, const uint8_t* d_desc, const int32_t* d_node, const uint8_t* d_valid,
+                                                const int32_t* d_n, int cap, int nkeyframes,
+                                                const int32_t* d_pairs, int npairs,
+                                                float nnratio, int check_orientation,
+                                                int32_t* d_matches12, int32_t* d_matches21, int32_t* d_nmatches, void* stream);
 
 /* LSDmatcher::SerachForInitialize(InitialFrame,CurrentFrame,LineMatches),
  * src/LSDmatcher.cpp:257-284 = knn2 + Frame::lineDescriptorMAD (src/Frame.cc:190-215)

@@ -923,3 +923,31 @@ extern "C" int sslam_orb_search_by_bow_batch_dev(sslam_ctx* ctx,
     SSLAM_HIP(hipGetLastError());
     return SSLAM_OK;
 }
+
+// ---- SearchByBoW between pairs of keyframe slots that are already on the device (src/ORBmatcher.cc:525-658, the first matcher of LoopClosing::ComputeSim3),
+// from per-feature node ids (sslam_bow_transform_batch_dev), asynchronous.  The reference function writes its own output vector and its local vbMatched2
+// alone, so any pair list is exact in one launch.
+extern "C" int sslam_orb_search_by_bow_keyframes_batch_dev(sslam_ctx* ctx,
+        const sslam_keypoint* d_kp, const uint8_t* d_desc, const int32_t* d_node, const uint8_t* d_valid,
+        const int32_t* d_n, int cap, int nkeyframes,
+        const int32_t* d_pairs, int npairs,
+        float nnratio, int check_orientation,
+        int32_t* d_matches12, int32_t* d_matches21, int32_t* d_nmatches, void* stream) {
+    if (!ctx || !d_kp || !d_desc || !d_node || !d_n || !d_pairs || !d_matches12 || !d_matches21 || !d_nmatches ||
+        !rows_in_range(cap) || nkeyframes < 0 || npairs < 0 || !fits_31_bits(npairs, cap) ||
+        !all_aligned<4>(d_kp, d_node, d_n, d_pairs, d_matches12, d_matches21, d_nmatches) || !all_aligned<16>(d_desc)) {      // descriptor rows are read as two 16-byte words
+        set_error("sslam_orb_search_by_bow_keyframes_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (npairs == 0) return SSLAM_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    SSLAM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    const BatchPlan P = batch_plan(BOW_BATCH_ROW_BYTES, cap);      // match_plan.h: keyframe 2 in LDS or in global memory, by the row capacity alone
+    BowKfBatchArgs A;
+    A.kp = d_kp; A.desc = d_desc; A.node = d_node; A.valid = d_valid; A.n = d_n; A.cap = cap; A.nkeyframes = nkeyframes;
+    A.pairs = d_pairs; A.nnratio = nnratio; A.checkOri = check_orientation; A.m12 = d_matches12; A.m21 = d_matches21; A.nmatches = d_nmatches;
+    int rc;
+    if ((rc = launch_batch(ctx, "k_search_bow_kf_batch", k_search_bow_kf_batch<true>, k_search_bow_kf_batch<false>, P, (unsigned)npairs, st, A))) return rc;      // one workgroup per pair
+    SSLAM_HIP(hipGetLastError());
+    return SSLAM_OK;
+}

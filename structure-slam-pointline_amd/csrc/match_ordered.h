@@ -1,5 +1,5 @@
 // Order-dependent matchers (an accepted match changes what later queries may take): SearchForInitialization, the
-// projection-window family (two-kernel form and one-wave form), SearchByBoW.
+// projection-window family (two-kernel form and one-wave form), SearchByBoW (KeyFrame -> Frame and KeyFrame -> KeyFrame).
 // Part of match.hip (included there, inside its anonymous namespace: one translation unit).  Not a standalone header.
 #pragma once
 
@@ -995,6 +995,115 @@ __global__ __launch_bounds__(64 * BATCH_WAVES) void k_search_bow_batch(BowBatchA
         if (a >= 0 && A.checkOri && !rot_kept(rot_hist_bin(kpKF[a].angle, kpF[j].angle), keep[0], keep[1], keep[2])) a = -1;
         cnt += a >= 0;
         out[j] = a;
+    }
+    cnt = wave_sum(cnt);
+    if (lane == 0 && cnt) atomicAdd(&total, cnt);
+    __syncthreads();
+    if (tid == 0) A.nmatches[p] = total;
+}
+
+// ---------------------------------------------------------------- SearchByBoW(KeyFrame*, KeyFrame*) of a batch (sslam_orb_search_by_bow_keyframes_batch_dev)
+// src/ORBmatcher.cc:525-658 for pairs of slots of ONE device-resident keyframe pool, on per-feature node ids.  The walk is k_search_bow_batch's: one
+// workgroup of BATCH_WAVES waves per pair, wave w owns the nodes with node % BATCH_WAVES == w, walks the keyframe-1 rows in ascending index, 64 node
+// ids per ballot, and takes the valid rows of a node it owns in bit order; a keyframe-2 row has one node, so its state word is written and read by
+// one wave only and the waves never wait for each other.  What differs from the KeyFrame -> Frame matcher:
+//   - keyframe 2 has validity flags: a row that is invalid or already taken is skipped BEFORE its distance is looked at (:577-583), so it is neither
+//     best nor second best.  One state word per keyframe-2 row says both: BOW_KF_INVALID, BOW_KF_FREE, or the keyframe-1 row that owns it;
+//   - the distance gate is strict, bestDist1 < TH_LOW (:601); the ratio test reads bestDist2 = 256 when there is no second (:603);
+//   - the result is indexed by keyframe 1, and the rotation bin is that of kp1.angle - kp2.angle (:610).
+// After the one barrier behind the walk the workgroup fills the rotation histogram, prunes, counts and writes both directions.  The state words are a
+// one-to-one map, so walking the owned keyframe-2 rows visits every matched keyframe-1 row exactly once: the histogram holds the reference's per-row
+// entries, and the bin is recomputed from the owner and the two angles.
+// Every loop is bounded by a clamped count, a ballot's set bits or a constant: bytes past a count are never read, node ids and validity flags included.
+struct BowKfBatchArgs {
+    const sslam_keypoint* kp; const uint8_t* desc; const int* node; const uint8_t* valid; const int* n; int cap, nkeyframes;      // valid null: every row
+    const int* pairs;              // (kf1, kf2) per pair
+    float nnratio; int checkOri;
+    int* m12; int* m21; int* nmatches;
+};
+constexpr int BOW_KF_FREE = -1, BOW_KF_INVALID = -2;      // a state word >= 0 is the owning keyframe-1 row
+// kLds: keyframe 2 in dynamic LDS -- descriptors [2 cap] uint4, node ids [cap], state words [cap] (BOW_BATCH_ROW_BYTES per row); otherwise descriptors
+// and node ids in the caller's buffers and the state words in the pair's d_matches21 rows
+template <bool kLds>
+__global__ __launch_bounds__(64 * BATCH_WAVES) void k_search_bow_kf_batch(BowKfBatchArgs A) {
+    extern __shared__ __align__(16) unsigned bkl[];
+    __shared__ int hist[HISTO_LENGTH];
+    __shared__ int keep[3];
+    __shared__ int total;
+    constexpr int NT = 64 * BATCH_WAVES;
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int k1 = A.pairs[2 * (size_t)p], k2 = A.pairs[2 * (size_t)p + 1];
+    if (k1 < 0 || k1 >= A.nkeyframes || k2 < 0 || k2 >= A.nkeyframes) {      // (uniform over the workgroup, ahead of every barrier)
+        if (tid == 0) A.nmatches[p] = 0;
+        return;
+    }
+    const int n1 = slot_count(A.n, k1, A.cap), n2 = slot_count(A.n, k2, A.cap);
+    const size_t r1 = (size_t)k1 * (size_t)A.cap, r2 = (size_t)k2 * (size_t)A.cap;
+    const sslam_keypoint* kp1 = A.kp + r1; const uint8_t* d1 = A.desc + r1 * 32; const int* node1 = A.node + r1;
+    const sslam_keypoint* kp2 = A.kp + r2; const int* node2 = A.node + r2;
+    const uint8_t* valid1 = A.valid ? A.valid + r1 : nullptr; const uint8_t* valid2 = A.valid ? A.valid + r2 : nullptr;
+    int* out12 = A.m12 + (size_t)p * (size_t)A.cap; int* out21 = A.m21 + (size_t)p * (size_t)A.cap;
+    const uint4* fdesc; const int* fnode; int* state;
+    if (kLds) {
+        uint4* ld = (uint4*)bkl; int* ln = (int*)(ld + 2 * (size_t)A.cap); int* ls = ln + A.cap;
+        const uint4* gd = (const uint4*)(A.desc + r2 * 32);
+        for (int j = tid; j < 2 * n2; j += NT) ld[j] = gd[j];
+        for (int j = tid; j < n2; j += NT) ln[j] = node2[j];
+        fdesc = ld; fnode = ln; state = ls;
+    } else {
+        fdesc = (const uint4*)(A.desc + r2 * 32); fnode = node2; state = out21;
+    }
+    for (int j = tid; j < n2; j += NT) state[j] = (!valid2 || valid2[j] != 0) ? BOW_KF_FREE : BOW_KF_INVALID;
+    for (int i = tid; i < n1; i += NT) out12[i] = -1;
+    if (tid < HISTO_LENGTH) hist[tid] = 0;
+    if (tid == 0) total = 0;
+    __syncthreads();
+    // the walk: no workgroup barrier in here (the waves' trip counts differ); a state word is written and read by one wave only
+    for (int i0 = 0; i0 < n1; i0 += 64) {
+        const int i = i0 + lane;
+        int nd = -1; bool own = false;
+        if (i < n1) { nd = node1[i]; own = nd >= 0 && (!valid1 || valid1[i] != 0) && (nd % BATCH_WAVES) == wave; }
+        unsigned long long todo = __ballot(own);
+        while (todo) {
+            const int bit = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int i1 = i0 + bit;
+            const int nodeId = __builtin_amdgcn_readlane(nd, bit);
+            const uint4 q0 = ((const uint4*)(d1 + (size_t)i1 * 32))[0], q1 = ((const uint4*)(d1 + (size_t)i1 * 32))[1];
+            unsigned long long b = ~0ull, s = ~0ull;
+            for (int j = lane; j < n2; j += 64) {
+                if (fnode[j] != nodeId) continue;
+                if (__hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != BOW_KF_FREE) continue;      // vbMatched2 || !pMP2 || isBad (:579-583)
+                const unsigned long long kk = ((unsigned long long)hamming256(q0, q1, fdesc[2 * j], fdesc[2 * j + 1]) << 32) | (unsigned)j;
+                if (kk < b) { s = b; b = kk; } else if (kk < s) s = kk;
+            }
+            const unsigned long long best = wave_min_u64(b);
+            const unsigned long long second = wave_min_u64(b == best ? s : b);
+            int bestDist1 = 256, bestDist2 = 256, bestIdx2 = -1;
+            if (best != ~0ull) { bestDist1 = (int)(best >> 32); bestIdx2 = (int)(unsigned)best; }
+            if (second != ~0ull) bestDist2 = (int)(second >> 32);
+            if (bestIdx2 >= 0 && bestDist1 < TH_LOW && (float)bestDist1 < __fmul_rn(A.nnratio, (float)bestDist2)) {
+                if (lane == 0) __hip_atomic_store(&state[bestIdx2], i1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // the wave's next keyframe-1 row of this node must see the row taken
+            }
+        }
+    }
+    __syncthreads();
+    if (A.checkOri) {
+        for (int j = tid; j < n2; j += NT) {
+            const int a = state[j];
+            if (a >= 0) atomicAdd(&hist[rot_hist_bin(kp1[a].angle, kp2[j].angle)], 1);
+        }
+        __syncthreads();
+        if (tid == 0) three_maxima(hist, keep[0], keep[1], keep[2]);
+        __syncthreads();
+    }
+    int cnt = 0;
+    for (int j = tid; j < n2; j += NT) {
+        int a = state[j];
+        if (a >= 0 && A.checkOri && !rot_kept(rot_hist_bin(kp1[a].angle, kp2[j].angle), keep[0], keep[1], keep[2])) a = -1;
+        if (a >= 0) { out12[a] = j; ++cnt; }
+        out21[j] = a >= 0 ? a : -1;
     }
     cnt = wave_sum(cnt);
     if (lane == 0 && cnt) atomicAdd(&total, cnt);

@@ -159,7 +159,7 @@ inline ProjBatchArena proj_batch_arena(int cap, int qcap, int slice, int projK) 
     return a;
 }
 
-// -------------------------------------------------------------- rows in LDS or in global memory (the SearchByBoW, SearchForTriangulation and Fuse batches)
+// -------------------------------------------------------------- rows in LDS or in global memory (the two SearchByBoW batches, the SearchForTriangulation and Fuse batches)
 // One workgroup of BATCH_WAVES waves per unit of work, and one rule for where the rows it scans sit.  The form follows the row capacity alone
 // (every workgroup of a launch runs the same kernel):
 //   Lds     the scanned side sits in the workgroup's LDS, rowBytes per row of the capacity, while rowBytes * cap is at most BATCH_LDS_MAX (64 KB: two
@@ -188,6 +188,9 @@ inline BatchPlan batch_plan(int rowBytes, int cap) {
 // SearchByBoW of a batch (sslam_orb_search_by_bow_batch_dev, k_search_bow_batch): one workgroup per (keyframe slot, frame slot) pair, grid = npairs;
 // wave w owns the vocabulary nodes with node % BATCH_WAVES == w.  The FRAME side's capacity decides; a row is 32 bytes of descriptor, the node id and
 // the live assignment (three pairs per compute unit at 1000 rows).  The Global form keeps the live assignment in d_assigned.
+// SearchByBoW between keyframes of a batch (sslam_orb_search_by_bow_keyframes_batch_dev, k_search_bow_kf_batch) stages the same row and reuses the
+// constant: one workgroup per pair of keyframe slots, grid = npairs, KEYFRAME 2 staged; a row is 32 bytes of descriptor, the node id and one state
+// word (invalid, free, or the owning keyframe-1 row).  The Global form keeps the state words in the pair's d_matches21 rows.
 constexpr int BOW_BATCH_ROW_BYTES = 40;
 
 // SearchForTriangulation of a batch (sslam_orb_search_for_triangulation_batch_dev, k_tri_search_batch): one workgroup per pair of keyframe slots,

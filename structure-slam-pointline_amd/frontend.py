@@ -218,6 +218,16 @@ class Context:
                                                      int(npairs), C.c_float(nnratio), int(bool(check_orientation)), _p(d_assigned), _p(d_nmatches),
                                                      C.c_void_p(stream or 0)))
 
+    def search_by_bow_keyframes_batch_dev(self, d_kp, d_desc, d_node, d_n, cap, nkeyframes, d_pairs, npairs, d_matches12, d_matches21, d_nmatches,
+                                          d_valid=None, nnratio=0.75, check_orientation=True, stream=None):
+        """sslam_orb_search_by_bow_keyframes_batch_dev on device tensors / pointers: pair p matches keyframe slot d_pairs[2p] (pKF1, the side the result
+        is indexed by) against slot d_pairs[2p+1] (pKF2) of the one pool d_kp / d_desc / d_node / d_n [/ d_valid] from the per-feature node ids of
+        bow_transform_batch_dev; d_pairs [npairs, 2] int32, d_matches12 and d_matches21 [npairs, cap] int32, d_nmatches [npairs] int32; enqueues on
+        `stream` (None: the context's) and returns without synchronising"""
+        _chk(lib().sslam_orb_search_by_bow_keyframes_batch_dev(self.h, _p(d_kp), _p(d_desc), _p(d_node), _p(d_valid), _p(d_n), int(cap), int(nkeyframes),
+                                                               _p(d_pairs), int(npairs), C.c_float(nnratio), int(bool(check_orientation)),
+                                                               _p(d_matches12), _p(d_matches21), _p(d_nmatches), C.c_void_p(stream or 0)))
+
     def search_for_triangulation_batch_dev(self, d_kp, d_desc, d_node, d_n, cap, nkeyframes, d_pairs, npairs, scale_factors, level_sigma2,
                                            d_matches12, d_nmatches, d_free=None, d_uright=None, only_stereo=False, check_orientation=True, nlevels=None,
                                            stream=None):
