@@ -176,6 +176,45 @@ int sslam_orb_search_for_initialization_batch_dev(sslam_ctx* ctx,
         int cap, int npairs, float* d_prev_matched, int32_t* d_matches12, int32_t* d_nmatches,
         int window_size, float nnratio, int check_orientation, const float bounds[4], void* stream);
 
+/* The model selection of Initializer::Initialize (src/Initializer.cc:55-118, reached from src/Tracking.cc:366 right behind SearchForInitialization): `iterations` RANSAC
+ * hypotheses, each one homography and one fundamental matrix from eight matches (FindHomography / FindFundamental :155-253, ComputeH21 / ComputeF21 :255-332 on the points of
+ * Normalize :784-830), scored against every match (CheckHomography / CheckFundamental :334-497), the best of each and RH = SH / (SH + SF) (:118).  What follows in the
+ * reference -- ReconstructH / ReconstructF, CheckRT, Triangulate (:499-782, :833 on) -- are poses and map points and stay with the tracker: H21 / F21 and the inlier bits
+ * below are their inputs.  kp1 / kp2 are the UNDISTORTED keypoints (mvKeysUn: sslam_undistort_keypoints_batch_dev); matches12[i] is the keypoint of frame 2 matched to keypoint i
+ * of frame 1 or negative (vnMatches12: sslam_orb_search_for_initialization_batch_dev's d_matches12); a row counts as matched when 0 <= matches12[i] < n2, and the matched rows in
+ * ascending i are the match list (mvMatches12, :67-76).  sigma is mSigma (1.0 in Tracking), iterations mMaxIterations (200).
+ *   sets  NULL: iteration `it` of pair p draws its eight matches as :93-108 do, with randi = hash32(seed, p, it, j) % remaining (csrc/two_view_math.h states hash32; the
+ *         reference's rand() stream is per process and not reproducible per pair).  Otherwise sets[(p * iterations + it) * 8 + j] are indices into the match list and replace
+ *         the draw -- the hook for a caller that wants the reference's own rand() stream.  An iteration with an index outside [0, nmatches) gets zero matrices and the score 0:
+ *         it never wins.  H and F share the sets, as in the reference.
+ *   result, one per pair.  A pair with fewer than 8 matches is skipped: model 0, best_it -1, scores, rh and matrices 0, inlier bytes 0.  (Tracking only initialises from 100
+ *         matches on; the library itself only refuses below 8.)  best_it_h / best_it_f: the first iteration with the highest score above 0 (:196, :246: a strict >), -1 when
+ *         no score exceeded 0 (the matrix is zero then).  A NaN score (a singular H21i: its inverse is the zero matrix) never wins, as in the reference.  rh is the float the
+ *         reference holds (NaN for 0 / 0); model is 1 (H) when rh > 0.40 and 2 (F) otherwise.
+ *   inliers[i], by keypoint 1 like matches12: bit 0 = inlier of the winning H (vbMatchesInliersH), bit 1 = inlier of the winning F; 0 for an unmatched row.  Rows [n1, cap) are
+ *         not written.
+ * What the reference leaves to OpenCV here (cv::SVDecomp, the float matrix product and inverse) is restated by decision D15 of DESIGN.md; everything else is the reference's
+ * arithmetic operation for operation, the score summed in match order.
+ * The batch form uses the layout of sslam_orb_search_for_initialization_batch_dev: pair p owns rows [p*cap, (p+1)*cap) of d_kp1, d_kp2, d_matches12 and d_inliers, counts
+ * d_n1[p], d_n2[p] on the device.  One launch on `stream` (NULL: the context's stream), no scratch, no synchronise, no host memory read or written; every output word has one
+ * writer.  SSLAM_ERR_INVALID (nothing enqueued): a NULL pointer other than d_sets, cap or npairs < 1, iterations < 1, sigma <= 0 or NaN, a pointer that is not 4-byte aligned,
+ * npairs * cap >= 2^31.  SSLAM_ERR_UNSUPPORTED (nothing enqueued): cap > 4096 (the match rows sit in LDS, 16 bytes each).  The single call is pair 0 of the same kernel
+ * (cap = max(n1, n2)) and synchronises. */
+typedef struct sslam_two_view_result {      /* 100 bytes */
+    int32_t nmatches;               /* matched rows the call saw */
+    int32_t model;                  /* 0 = skipped (nmatches < 8), 1 = H (RH > 0.40), 2 = F */
+    int32_t best_it_h, best_it_f;   /* winning iteration, -1 when no score exceeded 0 */
+    float score_h, score_f, rh;     /* SH, SF, SH / (SH + SF) */
+    float H21[9], F21[9];           /* row-major; zeros when best_it is -1 */
+} sslam_two_view_result;
+int sslam_two_view_ransac(sslam_ctx* ctx, const sslam_keypoint* kp1, int n1, const sslam_keypoint* kp2, int n2,
+        const int32_t* matches12, const int32_t* sets /* NULL or [iterations*8] */, int iterations, float sigma, uint32_t seed,
+        sslam_two_view_result* result, uint8_t* inliers /* [n1] */);
+int sslam_two_view_ransac_batch_dev(sslam_ctx* ctx, const sslam_keypoint* d_kp1, const int32_t* d_n1,
+        const sslam_keypoint* d_kp2, const int32_t* d_n2, int cap, int npairs, const int32_t* d_matches12,
+        const int32_t* d_sets /* NULL or [npairs*iterations*8] */, int iterations, float sigma, uint32_t seed,
+        sslam_two_view_result* d_result, uint8_t* d_inliers /* [npairs*cap] */, void* stream);
+
 /* The projection-window matcher family.  The tracker keeps the projection / visibility logic (poses, map
  * points: host state) and hands over one query per map point or map line; the device replays the
  * window search, the best/second-best Hamming selection, the level-consistent ratio test, the

@@ -123,6 +123,14 @@ int sslam_testing_orb_tail(sslam_orb* o, const uint8_t* gray, int w, int h, size
  * rows of at most 2048), the layout tools/proj_batch_probe.py times against the one the plan chooses.  Process-wide; results do not depend on either. */
 int sslam_testing_proj_batch_tuning(int max_slice, int feats_in_lds);
 
+/* sslam_two_view_ransac for one host pair with EVERY hypothesis copied back, so that a wrong hypothesis that does not win is visible: the same kernel with its stores enabled,
+ * run as pair `pair` of a batch (the draw of src/Initializer.cc:93-108 hashes the pair index; the single call is pair 0).  Per iteration it: sets_out[it*8 .. +8) = the eight
+ * indices into the match list, mats_out[it*45 .. +45) = Hn, H21i, H12i, Fn, F21i (row-major, 9 floats each: ComputeH21, :191, :192, ComputeF21, :242), scores_out[it*2 .. +2) =
+ * CheckHomography's and CheckFundamental's score.  All zero for a pair below 8 matches.  result and inliers as sslam_two_view_ransac. */
+int sslam_testing_two_view_hypotheses(sslam_ctx* ctx, const sslam_keypoint* kp1, int n1, const sslam_keypoint* kp2, int n2, const int32_t* matches12, const int32_t* sets,
+                                      int iterations, float sigma, uint32_t seed, int pair, sslam_two_view_result* result, uint8_t* inliers,
+                                      int32_t* sets_out, float* mats_out, float* scores_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,7 +94,7 @@ enum {
     SCR_SFI_STATE = 3,       // sslam_orb_search_for_initialization_batch_dev: per-pair state (SfiArgs::scratch)
     SCR_SFI_STAGE = 4,       // sslam_orb_search_for_initialization: the pair and its results
     SCR_LINE_MATCH = 5,      // sslam_line_match
-    SCR_CALL = 6,            // the arena of search_proj_core, sslam_hamming_knn2_frames, sslam_distinctive_descriptors, sslam_fuse_search, sslam_orb_search_for_triangulation, bow_core
+    SCR_CALL = 6,            // the arena of search_proj_core, sslam_hamming_knn2_frames, sslam_distinctive_descriptors, sslam_fuse_search, sslam_orb_search_for_triangulation, bow_core, sslam_two_view_ransac (two_view.hip)
     SCR_UPLOAD = 7,          // host features that a core with an arena in SCR_CALL reads (sslam_search_by_projection, sslam_bow_transform); the arena of search_by_bow_core
     SCR_COUNT = 8
 };

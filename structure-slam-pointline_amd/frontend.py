@@ -33,6 +33,10 @@ assert FUSE_JOB_DTYPE.itemsize == 12
 OBS_DTYPE = np.dtype([("kf", "<i4"), ("row", "<i4")])      # sslam_observation
 assert OBS_DTYPE.itemsize == 8
 
+TWO_VIEW_RESULT_DTYPE = np.dtype([("nmatches", "<i4"), ("model", "<i4"), ("best_it_h", "<i4"), ("best_it_f", "<i4"), ("score_h", "<f4"), ("score_f", "<f4"),
+                                  ("rh", "<f4"), ("H21", "<f4", (9,)), ("F21", "<f4", (9,))])      # sslam_two_view_result
+assert TWO_VIEW_RESULT_DTYPE.itemsize == 100
+
 _lib = None
 
 PIX_GRAY, PIX_RGB, PIX_BGR, PIX_RGBA, PIX_BGRA = 0, 1, 2, 3, 4      # SSLAM_PIX_* (include/sslam_frontend.h)
@@ -165,6 +169,28 @@ class Context:
                                                        _p(pm), _p(m12), int(window), C.c_float(nnratio),
                                                        int(bool(check_orientation)), b, C.byref(n)))
         return m12, pm, n.value
+
+    def two_view_ransac(self, kp1, kp2, matches12, sets=None, iterations=200, sigma=1.0, seed=0):
+        """Initializer::Initialize's model selection (sslam_two_view_ransac) for one pair: kp1 / kp2 the undistorted keypoints (KP_DTYPE), matches12 [n1] int32, sets None
+        (the library draws) or [iterations, 8] indices into the match list.  Returns (result: a TWO_VIEW_RESULT_DTYPE record, inliers: uint8 [n1])"""
+        kp1 = np.ascontiguousarray(kp1, KP_DTYPE); kp2 = np.ascontiguousarray(kp2, KP_DTYPE)
+        m12 = np.ascontiguousarray(matches12, np.int32)
+        assert len(m12) == len(kp1)
+        if sets is not None:
+            sets = np.ascontiguousarray(sets, np.int32)
+            assert sets.shape == (int(iterations), 8)
+        res = np.zeros(1, TWO_VIEW_RESULT_DTYPE); inl = np.zeros(len(kp1), np.uint8)
+        _chk(lib().sslam_two_view_ransac(self.h, _p(kp1), len(kp1), _p(kp2), len(kp2), _p(m12), _p(sets), int(iterations), C.c_float(sigma), C.c_uint32(seed),
+                                         _p(res), _p(inl)))
+        return res[0], inl
+
+    def two_view_ransac_batch_dev(self, d_kp1, d_n1, d_kp2, d_n2, cap, npairs, d_matches12, d_result, d_inliers, d_sets=None, iterations=200, sigma=1.0, seed=0,
+                                  stream=None):
+        """sslam_two_view_ransac_batch_dev on device tensors / pointers laid out like search_for_initialization_batch_dev's: pair p owns rows [p*cap, (p+1)*cap) of d_kp1,
+        d_kp2, d_matches12 and d_inliers (uint8); d_result receives npairs TWO_VIEW_RESULT_DTYPE records (100 bytes each), d_sets is None or [npairs, iterations, 8] int32;
+        enqueues on `stream` (None: the context's) and returns without synchronising"""
+        _chk(lib().sslam_two_view_ransac_batch_dev(self.h, _p(d_kp1), _p(d_n1), _p(d_kp2), _p(d_n2), int(cap), int(npairs), _p(d_matches12), _p(d_sets), int(iterations),
+                                                   C.c_float(sigma), C.c_uint32(seed), _p(d_result), _p(d_inliers), C.c_void_p(stream or 0)))
 
     def search_by_projection(self, kind, mode, feats, desc, queries, qdesc, occupied=None, uright=None, nnratio=0.8, th_dist=100,
                              check_orientation=True, bounds=(0.0, 640.0, 0.0, 480.0)):
