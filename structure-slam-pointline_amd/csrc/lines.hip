@@ -341,13 +341,15 @@ static LinesKnobs lines_knobs() {
 // Whether a batch of `nframes` runs the sequential core in its guest form (lsd_regions.h): a co-running branch was announced (sslam_lines_set_core_event) and the batch is
 // at least two rounds of the persistent grid of 20 (16 for smaller batches) workgroups per compute unit.
 // What a compute unit holds beside the core is decided by registers AND by LDS, which gfx950 hands out in granules of 1 280 B (tools/lds_granule_probe.hip).  A core
-// workgroup takes 94 VGPRs and four granules (5 120 B, lsd_regions.h), a k_fast_cells wave 32 VGPRs and four granules at 640 x 480 (orb.hip):
-//   20 per compute unit: five core waves on every SIMD (480 of 512 VGPRs), one FAST wave beside them; 100 KB of the 160 KB of LDS for the core, room for twelve FAST waves;
-//   18 per compute unit: two SIMDs hold five core waves, two hold four and keep 128 registers: ten FAST waves by registers, fourteen by LDS.
+// workgroup takes 94 VGPRs and four granules (5 120 B, lsd_regions.h), a k_fast_cells wave -- one per strip of three cells -- 32 VGPRs and eleven granules at 640 x 480 (orb.hip):
+//   20 per compute unit: five core waves on every SIMD (480 of 512 VGPRs), one FAST wave beside them; 100 KB of the 160 KB of LDS for the core, room for four FAST waves;
+//   18 per compute unit: two SIMDs hold five core waves, two hold four and keep 128 registers: ten FAST waves by registers, five by LDS.
 // Before the LDS budgets (core 5 648 B = five granules, FAST 7 290 B = six) 18 left six FAST waves and was the optimum (17 / 19 / 20: 150.8 / 149.4 / 150.0 ms per step against
 // 149.3).  With them it is not: ten FAST waves beside 18 core workgroups slow the core more (92 -> 96 ms) than they speed up FAST (76.4 -> 74.3), 151.4 ms per step; 20 with the
 // FAST waves the registers then leave gives 148.5.  Also measured, no better: k_lsd_regions<false, 6> (80 VGPRs) on the grid at 20 / 22 / 24 per compute unit -- the core
 // drops to 90 / 85 / 79 ms, FAST beside it stays at 76 - 77 ms whatever its slot count, and the step at 148 - 149 ms (profiles/guest_grid_lds_budgets.txt).
+// (Those figures are from k_fast_cells per cell at four granules.  Per strip FAST takes 73.0 ms beside the grid of 20 and the step 146.2 ms; 18 / 19 / 20 per compute unit
+// were run again with it, profiles/fast_strips.txt section 6.)
 static bool lines_guest_form(const sslam_lines* L, int nframes, const LinesKnobs& K, int* grid_out) {
     int grid = 20 * L->ctx->num_cus;
     if (2 * grid > nframes) grid = 16 * L->ctx->num_cus;

@@ -17,10 +17,12 @@
 //     staged in LDS (no blurred image in HBM).
 #include "common.h"
 #include "camera.h"
+#include "fast_strips.h"
 #include <cmath>
 #include <algorithm>
 
 using namespace sslam;
+using sslam_fast::StripInfo; using sslam_fast::FAST_STRIP_K; using sslam_fast::FAST_LIST_CAP; using sslam_fast::FAST_IDX_BITS; using sslam_fast::FAST_DIV_SHIFT;
 
 namespace {
 
@@ -58,6 +60,7 @@ struct Plan {
     // copies it into the frame's pyramid block first (rounds 1-4 always did: 0.6 MB per frame read and written for nothing).
     const uint8_t* img0; size_t img0Stride; int img0Pitch;
     int maxCellW, maxCellH, maxCellsLevel, maxNodeCap;
+    int nStripsFrame, maxStripW;  // k_fast_cells' strip table (fast_strips.h): one wave per strip of up to FAST_STRIP_K cells
     LevelInfo L[MAX_LEVELS];
 };
 
@@ -245,64 +248,79 @@ __device__ __forceinline__ int fast_score16(const uint8_t* c, int tp, int minTh)
     return s >= minTh ? s : 0;
 }
 
-// How many survivors of the pre-test (pass A) a cell keeps as a list; an entry is the pixel's index in the cell (i < 4 400 < 2^13, the bound the magic
-// division relies on too) and, from the suppression pass on, its keep-code in bits 13-14.  A condition, not a tuning result: the largest cell of the bench's 64 scenes and
-// their warped predecessors (eight kinds, eight levels, 104 320 cells; numpy replay of pass A, tests/test_guest_budget_gpu.py holds it) has 825 survivors of
-// 1 258 pixels, so 0 % of those cells exceed the cap.  A cell that does -- dense texture, noise -- is still exact: its list is scored and started again whenever the next
-// step's survivors (64 lanes x 4 pixels at most) do not fit, and suppression and emission walk its pixels instead of the list, in the same raster order.
-constexpr int FAST_LIST_CAP = 832;
-
-// Dynamic LDS of k_fast_cells for cells of up to maxW x maxH pixels: the image tile, the score tile and the list.  640 x 480, eight levels (cells of up to
-// 37 x 34): 2 080 + 1 372 + 1 664 = 5 116 B, four allocation granules of 1 280 B (tools/lds_granule_probe.hip); 7 290 B = six with a list entry and a code byte
-// for every pixel.  The score tile's rows are maxW + 1 wide: the zero rim to the right of one row is the zero rim to the left of the next.
+// One wave takes a STRIP of up to FAST_STRIP_K adjacent cells of a cell row (fast_strips.h): FAST scores depend on the pixel alone, so the strip is staged, pre-tested
+// and scored as one rectangle -- one set-up, no halo between its cells, full lanes in the three loops -- and only suppression at a cell's rim, the iniTh / minTh decision
+// and the output lists are per cell.  The list of pass A's survivors holds FAST_LIST_CAP entries; an entry is the pixel's index in the strip (< 2^13, the bound the magic
+// divisions are proven for too) and, from the suppression pass on, its keep-code in bits 13-14.  A condition, not a tuning result: no strip of the bench's scenes
+// has more survivors (numpy replay of pass A, tests/test_fast_strips_cpu.py).  A strip that does -- dense texture, noise -- is still exact: its list is scored and started
+// again whenever the next step's survivors (64 lanes x 4 pixels at most) do not fit, and suppression and emission walk its pixels instead of the list, in the same raster order.
+//
+// Dynamic LDS for strips of up to maxW x maxH pixels: the image tile, the score tile and the list.  640 x 480, eight levels (strips of up to 111 x 34):
+// 4 960 + 4 036 + 4 992 = 13 988 B, eleven allocation granules of 1 280 B (tools/lds_granule_probe.hip).
 static inline int fast_tile_pitch(int maxW) { return (maxW + 6 + 3 + 7) & ~3; }
-static inline int fast_score_pitch(int maxW) { return maxW + 1; }
-static inline size_t fast_score_bytes(int maxW, int maxH) { return (((size_t)(maxH + 2) * fast_score_pitch(maxW) + 1) + 3) & ~(size_t)3; }
+static inline size_t fast_score_bytes(int maxW, int maxH) { return (((size_t)(maxH + 2) * (maxW + 1) + 1) + 3) & ~(size_t)3; }
 static inline size_t fast_lds_bytes(int maxW, int maxH) {
     return (size_t)(maxH + 6) * fast_tile_pitch(maxW) + fast_score_bytes(maxW, maxH) + sizeof(unsigned short) * FAST_LIST_CAP;
 }
 
-// One wave per (cell, frame).  LDS: image tile with 3-px halo (staged with aligned dword loads), score
-// tile with a zero rim (NMS neighbours outside the cell's detection rectangle count as 0, D.1), and the
-// list of pass A's survivors.  Candidates leave in raster order, packed (score<<24 | y<<12 | x) with x,y
-// relative to minBorder (=16), :820-825.  i -> (row, col) uses an exact magic-multiply division.
+// phase clocks for tools/fast_cycles.py: compiled in with -DSSLAM_FAST_CYCLES only (a variant library, never the product build).  Slots: 0 set-up + staging + zeroing,
+// 1 pass A, 2 pass B, 3 suppression, 4 emission, 5 strips
+#ifdef SSLAM_FAST_CYCLES
+__device__ unsigned long long g_fastCycles[8];
+#define FAST_CLK(k) do { const unsigned long long t_ = __builtin_readcyclecounter(); clk[k] += t_ - tPrev; tPrev = t_; } while (0)
+#else
+#define FAST_CLK(k) do {} while (0)
+#endif
+
+// One wave per (strip, frame).  LDS: image tile with 3-px halo (staged with aligned dword loads), score tile with a zero rim (NMS neighbours outside the cell's
+// detection rectangle count as 0, D.1; between two cells of the strip keep_code masks them), and the list of pass A's survivors.  Candidates leave per cell in raster
+// order, packed (score<<24 | y<<12 | x) with x,y relative to minBorder (=16), :820-825.  i -> (row, col) uses an exact magic-multiply division.
 __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t* __restrict__ pyr, size_t pyrFrame, Plan P,
-                                                   const CellInfo* __restrict__ cells,
+                                                   const StripInfo* __restrict__ strips, const CellInfo* __restrict__ cells,
                                                    unsigned* __restrict__ cand, int* __restrict__ cellCount,
-                                                   int iniTh, int minTh, int tileP, int scP) {
+                                                   int iniTh, int minTh, int tileMaxP) {
     extern __shared__ __align__(16) uint8_t lds[];
-    // Round 4: which cell a workgroup takes follows the dispatch order.  Workgroups are dealt round-robin over the eight XCDs, so with
-    // cellId = blockIdx.x horizontally adjacent cells -- which share their 6-pixel overlap and the 128-byte lines both tiles straddle -- were
+    // Round 4: which strip a workgroup takes follows the dispatch order.  Workgroups are dealt round-robin over the eight XCDs, so with
+    // stripId = blockIdx.x horizontally adjacent strips -- which share their 6-pixel overlap and the 128-byte lines both tiles straddle -- were
     // fetched through eight different L2s (4.34 MB fetched per frame for 0.95 MB of pyramid, PMC).  Now the workgroups of one XCD
-    // (blockIdx.x % 8) walk one contiguous eighth of the frame's cell list, in order; which eighth rotates with the frame so that
-    // every XCD sees every pyramid level (the levels differ in corner density).  gridDim.x = 8 * ceil(nCells / 8).
+    // (blockIdx.x % 8) walk one contiguous eighth of the frame's strip list, in order; which eighth rotates with the frame so that
+    // every XCD sees every pyramid level (the levels differ in corner density).  gridDim.x = 8 * ceil(nStrips / 8).
     const int b = blockIdx.y, per = gridDim.x >> 3;
-    const int cellId = (((blockIdx.x & 7) + b) & 7) * per + (blockIdx.x >> 3);
-    if (cellId >= P.nCellsFrame) return;
+    const int stripId = (((blockIdx.x & 7) + b) & 7) * per + (blockIdx.x >> 3);
+    if (stripId >= P.nStripsFrame) return;
+#ifdef SSLAM_FAST_CYCLES
+    unsigned long long clk[5] = {0, 0, 0, 0, 0}, tPrev = __builtin_readcyclecounter();
+#endif
     const int lane = threadIdx.x;
-    const CellInfo ci = cells[cellId];
-    const LevelInfo& L = P.L[ci.level];
-    const int cw = ci.x1 - ci.x0, ch = ci.y1 - ci.y0;
-    uint8_t* tile = lds;                                       // (maxCellH+6) x tileP, tileP % 4 == 0
-    uint8_t* sc = tile + (P.maxCellH + 6) * tileP;             // (maxCellH+2) x scP + 1, scP = maxCellW + 1 (fast_score_pitch)
+    const StripInfo si = strips[stripId];
+    const int sw = si.x1 - si.x0, ch = si.y1 - si.y0, wc = si.wc;
+    const int scP = sw + 1;                                    // the score tile's rows are sw + 1 wide: the zero rim to the right of one row is the zero rim to the left of the next
+    uint8_t* tile = lds;                                       // (ch+6) x tileP of (maxCellH+6) x tileMaxP (fast_tile_pitch)
+    uint8_t* sc = tile + (P.maxCellH + 6) * tileMaxP;             // (ch+2) x scP + 1 of fast_score_bytes(maxStripW, maxCellH)
     int pitch;
-    const uint8_t* img = level_image(P, pyr, pyrFrame, b, ci.level, pitch);
+    const uint8_t* img = level_image(P, pyr, pyrFrame, b, si.level, pitch);
     // stage rows [y0-3, y1+3) from the 4-byte aligned column ax <= x0-3; cells are interior (x0 >= 19, x1 + 3 <= w - 13) and the
     // row pitch is a multiple of 4, so the aligned dwords stay inside the row
-    const int ax = (ci.x0 - 3) & ~3, off = (ci.x0 - 3) - ax;
-    const int ndw = (off + cw + 6 + 3) >> 2, th = ch + 6;
-    {   // buffer loads: the tile's first byte in a scalar resource descriptor, ONE 32-bit offset register per load (the loop's sixteen loads in flight with 64-bit addresses
-        // set the kernel's register count: 51 -> how many of its waves fit beside the sequential LSD core in its guest form)
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(img + (size_t)(ci.y0 - 3) * pitch + ax), 0, 0x7FFFFFFF, 0x00020000);
-        const int q0 = lane & 15;
-        for (int ry = lane >> 4; ry < th; ry += 4) {
-            const int rowOff = __mul24(ry, pitch);
-            for (int q = q0; q < ndw; q += 16) ((unsigned*)(tile + ry * tileP))[q] = __builtin_amdgcn_raw_buffer_load_b32(rs, rowOff + 4 * q, 0, 0);
+    const int ax = (si.x0 - 3) & ~3, off = (si.x0 - 3) - ax;
+    const int ndw = (off + sw + 6 + 3) >> 2, th = ch + 6;
+    const int tileP = 4 * ndw;                                 // the tile's rows lie back to back: what the loads below write is linear in the lane
+    {   // buffer loads straight into LDS: the tile's first byte in a scalar resource descriptor, ONE 32-bit offset register per load and no data register at all.  The
+        // lanes walk the flattened (row, dword) index in steps of 64 -- every lane carries a dword whatever the strip's width -- and a load writes the 256 bytes behind
+        // its wave-uniform LDS address in lane order, which is that index.  All of a strip's loads are in flight together; the barrier below waits for them.
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(img + (size_t)(si.y0 - 3) * pitch + ax), 0, 0x7FFFFFFF, 0x00020000);
+        const int rstep = (int)((64u * si.smagic) >> FAST_DIV_SHIFT), qstep = 64 - rstep * ndw;      // 64 = rstep * ndw + qstep
+        int ry = (int)(__umul24((unsigned)lane, si.smagic) >> FAST_DIV_SHIFT), q = lane - __mul24(ry, ndw);
+        const int ndwords = th * ndw;
+        for (int base = 0; base < ndwords; base += 64) {
+            if (ry < th) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(tile + 4 * base), 4, __mul24(ry, pitch) + 4 * q, 0, 0, 0);
+            ry += rstep; q += qstep;
+            if (q >= ndw) { q -= ndw; ++ry; }
         }
     }
     for (int i = lane; i < (((ch + 2) * scP + 1 + 3) >> 2); i += 64) ((unsigned*)sc)[i] = 0;
     __syncthreads();
-    const unsigned magic = ci.magic;      // (1 << 19) / cw + 1: floor(i/cw) == (i*magic)>>19 for i < 4400, cw <= 64
+    FAST_CLK(0);
+    const unsigned magic = si.magic;      // (1 << 20) / sw + 1: floor(i/sw) == (i*magic)>>20 for every i the strip has (fast_strips.h: fast_strip_fits)
     // pass A: necessary condition for a 9-arc at minTh, four pixels per lane on whole dwords.  Nine contiguous ring positions
     // always contain two ADJACENT compass points (ring 0/4/8/12 = S/E/N/W at distance 3), i.e. one vertical and one
     // horizontal one, and both must lie on the arc's side of the threshold:
@@ -310,14 +328,14 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t* __restrict__ p
     // Bytes are widened to two 16-bit halves per dword and compared with packed i16 arithmetic (sign bit of th -/+ (r - v)).
     // Survivors are compacted in raster order so that the expensive ring evaluation of pass B runs with full lanes on the few
     // pixels that can matter.
-    unsigned short* clist = (unsigned short*)(sc + (((P.maxCellH + 2) * scP + 1 + 3) & ~3));      // FAST_LIST_CAP entries
+    unsigned short* clist = (unsigned short*)(sc + (((P.maxCellH + 2) * (P.maxStripW + 1) + 1 + 3) & ~3));      // FAST_LIST_CAP entries
     int ncl = 0;
     bool dense = false;      // more survivors than the list holds (wave-uniform)
     const int T0 = off + 3;                                        // tile column of pixel 0
-    const int gmin = T0 >> 2, ng = ((T0 + cw - 1) >> 2) - gmin + 1;
-    const unsigned gmagic = ci.gmagic;                              // (1 << 19) / ng + 1: ng <= 17, items < 4400
+    const int gmin = T0 >> 2, ng = ((T0 + sw - 1) >> 2) - gmin + 1;
+    const unsigned gmagic = si.gmagic;                              // (1 << 20) / ng + 1
     const int nitems = ch * ng;
-    // passes A and B take turns until A has seen every item: once for a cell whose survivors fit the list (every cell of the bench's scenes), else once per list filling
+    // passes A and B take turns until A has seen every item: once for a strip whose survivors fit the list (every strip of the bench's scenes), else once per list filling
     for (int it0 = 0;;) {
         const s16x2 th2 = {(short)minTh, (short)minTh};
         int la = lane;
@@ -327,7 +345,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t* __restrict__ p
             unsigned flags = 0;
             int py = 0, g = 0;
             if (it < nitems) {
-                py = (int)(__umul24((unsigned)it, gmagic) >> 19);
+                py = (int)(__umul24((unsigned)it, gmagic) >> FAST_DIV_SHIFT);
                 g = gmin + (it - __mul24(py, ng));
                 const int rowN = __mul24(py, tileP);               // (24-bit multiplies throughout: v_mul_lo_u32 is quarter rate)
                 const unsigned* rc = (const unsigned*)(tile + rowN + 3 * tileP) + g;
@@ -355,7 +373,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t* __restrict__ p
                 // res bits: 0 -> byte 0, 1 -> byte 1, 16 -> byte 2, 17 -> byte 3
                 flags = (res & 3u) | ((res >> 14) & 12u);
                 const int px0 = 4 * g - T0;                        // pixel of byte 0
-                flags &= (0xFu << max(0, -px0)) & (0xFu >> max(0, px0 + 4 - cw));      // bytes that are pixels of this cell
+                flags &= (0xFu << max(0, -px0)) & (0xFu >> max(0, px0 + 4 - sw));      // bytes that are pixels of this strip
             }
             const int cntf = __popc(flags);
             const int incl = wave_incl_scan(cntf);
@@ -364,92 +382,127 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t* __restrict__ p
             // registers is then live across the scoring, whose sixteen ring values set the kernel's register count
             if (ncl + tot > FAST_LIST_CAP) { dense = true; break; }
             int pos = ncl + incl - cntf;
-            const int ibase = __mul24(py, cw) + 4 * g - T0;
+            const int ibase = __mul24(py, sw) + 4 * g - T0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) if (flags & (1u << k)) clist[pos++] = (unsigned short)(ibase + k);
             ncl += tot;
         }
         __syncthreads();
+        FAST_CLK(1);
         // pass B: the FAST score of the listed pixels into the score tile
         for (int j = lane; j < ncl; j += 64) {
             const int i = clist[j];
-            const int py = (int)(__umul24((unsigned)i, magic) >> 19), px = i - __mul24(py, cw);
+            const int py = (int)(__umul24((unsigned)i, magic) >> FAST_DIV_SHIFT), px = i - __mul24(py, sw);
             const int s = fast_score16(tile + __mul24(py + 3, tileP) + (off + px + 3), tileP, minTh);
             if (s) sc[__mul24(py + 1, scP) + (px + 1)] = (uint8_t)s;        // sc is pre-zeroed
         }
         __syncthreads();
+        FAST_CLK(2);
         if (it0 >= nitems) break;
     }
+    // The strip's cells are wc wide (the last one may be narrower: its last column is the strip's, whose right neighbours are the zero rim): column px is the first of
+    // a cell when px == k * wc, the last when px == k * wc - 1, and belongs to cell k or a later one when px >= k * wc.  All three are compares against scalars, and
+    // what the cells count and emit is worked out on the compare masks in scalar registers.
+    auto first_col = [&](int px) -> bool {
+        bool f = px == 0;
+#pragma unroll
+        for (int k = 1; k < FAST_STRIP_K; ++k) f = f || px == k * wc;
+        return f;
+    };
+    auto last_col = [&](int px) -> bool {
+        bool f = false;
+#pragma unroll
+        for (int k = 1; k < FAST_STRIP_K; ++k) f = f || px == k * wc - 1;
+        return f;
+    };
+    // the lanes (of mask m) whose column lies in cell k
+    auto in_cell = [&](const unsigned long long (&ge)[FAST_STRIP_K], int k) -> unsigned long long {
+        return k == 0 ? (FAST_STRIP_K > 1 ? ~ge[1] : ~0ull) : (k == FAST_STRIP_K - 1 ? ge[k] : ge[k] & ~ge[k + 1]);
+    };
     // the keep-code of a pixel from the score tile: 0 = suppressed, 1 = a corner at minTh, 2 = a corner at iniTh.
     // strict maximum of the 3 x 3 neighbourhood: the nine bytes are read together (one LDS round trip; as a chain of && the compiler made it eight dependent ones,
-    // a branch and a wait per neighbour) and "s > every neighbour" is "s > their maximum"
-    auto keep_code = [&](const uint8_t* c) -> int {
+    // a branch and a wait per neighbour) and "s > every neighbour" is "s > their maximum".  The reference runs FAST per cell (D.1): at a cell's first (last) column the
+    // three neighbours to the left (right) belong to the next cell of the strip and count as 0, as the zero rim does at the strip's own edges.
+    auto keep_code = [&](const uint8_t* c, bool first, bool last) -> int {
         const int s = c[0];
         const int n0 = c[-1], n1 = c[1], n2 = c[-scP - 1], n3 = c[-scP], n4 = c[-scP + 1], n5 = c[scP - 1], n6 = c[scP], n7 = c[scP + 1];
-        const int mx = max(max(max(n0, n1), max(n2, n3)), max(max(n4, n5), max(n6, n7)));
+        const int mxL = first ? 0 : max(max(n0, n2), n5), mxR = last ? 0 : max(max(n1, n4), n7);
+        const int mx = max(max(mxL, mxR), max(n3, n6));
         return (s > mx) ? (s >= iniTh ? 2 : 1) : 0;          // (s > mx >= 0 implies s > 0)
     };
-    unsigned* out = cand + (size_t)b * P.candFrame + ci.candOff;
-    int cnt20 = 0, n = 0;
-    if (!dense) {
-        // NMS + thresholds + emission only visit the compacted list (it is in raster order, and so is what it emits)
-        for (int j0 = 0; j0 < ncl; j0 += 64) {
-            const int j = j0 + lane;
-            int cde = 0;
-            if (j < ncl) {
-                const int i = clist[j];
-                const int py = (int)(__umul24((unsigned)i, magic) >> 19), px = i - __mul24(py, cw);
-                cde = keep_code(sc + __mul24(py + 1, scP) + (px + 1));
-                clist[j] = (unsigned short)(i | (cde << 13));
-            }
-            cnt20 += __popcll(__ballot(cde == 2));
+    // NMS + thresholds + emission visit the compacted list (it is in the strip's raster order; filtered by cell it is in that cell's raster order, and so is what a
+    // cell emits).  When the list was started again they visit every pixel of the strip instead, in the same order: a pixel that is not a corner has score 0 and
+    // keep-code 0, as if it had never been listed.  Per-cell counters and cursors are wave-uniform (scalar registers).
+    const int nvis = dense ? __mul24(ch, sw) : ncl;
+    int cnt20[FAST_STRIP_K], n[FAST_STRIP_K], co[FAST_STRIP_K];
+#pragma unroll
+    for (int k = 0; k < FAST_STRIP_K; ++k) { cnt20[k] = 0; n[k] = 0; co[k] = k < si.nc ? cells[si.cellBeg + k].candOff : 0; }
+    for (int j0 = 0; j0 < nvis; j0 += 64) {
+        const int j = j0 + lane;
+        int cde = 0, px = 0;
+        if (j < nvis) {
+            const int i = dense ? j : (int)clist[j];
+            const int py = (int)(__umul24((unsigned)i, magic) >> FAST_DIV_SHIFT);
+            px = i - __mul24(py, sw);
+            cde = keep_code(sc + __mul24(py + 1, scP) + (px + 1), first_col(px), last_col(px));
+            if (!dense) clist[j] = (unsigned short)(i | (cde << FAST_IDX_BITS));
         }
-        __syncthreads();
-        const int need = cnt20 > 0 ? 2 : 1;      // FAST(iniTh) empty -> FAST(minTh), :809-816
-        for (int j0 = 0; j0 < ncl; j0 += 64) {
-            const int j = j0 + lane;
-            int e = 0;
-            if (j < ncl) e = clist[j];
-            const bool keep = (e >> 13) >= need;
-            unsigned long long m = __ballot(keep);
-            if (keep) {
-                const int i = e & 0x1FFF;
-                const int py = (int)(__umul24((unsigned)i, magic) >> 19), px = i - __mul24(py, cw);
-                int s = sc[__mul24(py + 1, scP) + (px + 1)];
-                out[n + mbcnt(m)] = ((unsigned)s << 24) | ((unsigned)(ci.y0 + py - MINB) << 12) | (unsigned)(ci.x0 + px - MINB);
+        const unsigned long long m2 = __ballot(cde == 2);      // corners at iniTh
+        unsigned long long ge[FAST_STRIP_K] = {};
+#pragma unroll
+        for (int k = 1; k < FAST_STRIP_K; ++k) ge[k] = __ballot(px >= k * wc);
+#pragma unroll
+        for (int k = 0; k < FAST_STRIP_K; ++k) cnt20[k] += __popcll(m2 & in_cell(ge, k));
+    }
+    __syncthreads();
+    FAST_CLK(3);
+    unsigned* out = cand + (size_t)b * P.candFrame;
+    for (int j0 = 0; j0 < nvis; j0 += 64) {
+        const int j = j0 + lane;
+        int cde = 0, py = 0, px = 0;
+        if (j < nvis) {
+            if (dense) {
+                py = (int)(__umul24((unsigned)j, magic) >> FAST_DIV_SHIFT); px = j - __mul24(py, sw);
+                cde = keep_code(sc + __mul24(py + 1, scP) + (px + 1), first_col(px), last_col(px));
+            } else {
+                const int e = clist[j], i = e & ((1 << FAST_IDX_BITS) - 1);
+                cde = e >> FAST_IDX_BITS;
+                py = (int)(__umul24((unsigned)i, magic) >> FAST_DIV_SHIFT); px = i - __mul24(py, sw);
             }
-            n += __popcll(m);
         }
-    } else {
-        // the list was started again: every pixel of the cell, in raster order.  A pixel that is not a corner has score 0 and keep-code 0, as if it had never been listed
-        const int npx = __mul24(ch, cw);
-        for (int i0 = 0; i0 < npx; i0 += 64) {
-            const int i = i0 + lane;
-            int cde = 0;
-            if (i < npx) {
-                const int py = (int)(__umul24((unsigned)i, magic) >> 19), px = i - __mul24(py, cw);
-                cde = keep_code(sc + __mul24(py + 1, scP) + (px + 1));
-            }
-            cnt20 += __popcll(__ballot(cde == 2));
+        const unsigned long long m2 = __ballot(cde == 2), m1 = __ballot(cde >= 1);
+        unsigned long long ge[FAST_STRIP_K] = {};
+#pragma unroll
+        for (int k = 1; k < FAST_STRIP_K; ++k) ge[k] = __ballot(px >= k * wc);
+        int pos = 0;
+        unsigned long long any = 0;
+#pragma unroll
+        for (int k = 0; k < FAST_STRIP_K; ++k) {
+            // FAST(iniTh) empty -> FAST(minTh), :809-816: per cell
+            const unsigned long long m = (cnt20[k] > 0 ? m2 : m1) & in_cell(ge, k);
+            const int at = co[k] + n[k] + mbcnt(m);
+            if (__builtin_amdgcn_inverse_ballot_w64(m)) pos = at;
+            n[k] += __popcll(m);
+            any |= m;
         }
-        const int need = cnt20 > 0 ? 2 : 1;
-        for (int i0 = 0; i0 < npx; i0 += 64) {
-            const int i = i0 + lane;
-            bool keep = false;
-            int py = 0, px = 0;
-            if (i < npx) {
-                py = (int)(__umul24((unsigned)i, magic) >> 19); px = i - __mul24(py, cw);
-                keep = keep_code(sc + __mul24(py + 1, scP) + (px + 1)) >= need;
-            }
-            unsigned long long m = __ballot(keep);
-            if (keep) {
-                int s = sc[__mul24(py + 1, scP) + (px + 1)];
-                out[n + mbcnt(m)] = ((unsigned)s << 24) | ((unsigned)(ci.y0 + py - MINB) << 12) | (unsigned)(ci.x0 + px - MINB);
-            }
-            n += __popcll(m);
+        if (__builtin_amdgcn_inverse_ballot_w64(any)) {
+            const int s = sc[__mul24(py + 1, scP) + (px + 1)];
+            out[pos] = ((unsigned)s << 24) | ((unsigned)(si.y0 + py - MINB) << 12) | (unsigned)(si.x0 + px - MINB);
         }
     }
-    if (lane == 0) cellCount[(size_t)b * P.nCellsFrame + cellId] = n;
+    if (lane < si.nc) {
+        int nk = n[0];
+#pragma unroll
+        for (int k = 1; k < FAST_STRIP_K; ++k) nk = lane == k ? n[k] : nk;
+        cellCount[(size_t)b * P.nCellsFrame + si.cellBeg + lane] = nk;
+    }
+#ifdef SSLAM_FAST_CYCLES
+    FAST_CLK(4);
+    if (lane == 0) {
+        for (int k = 0; k < 5; ++k) atomicAdd(&g_fastCycles[k], clk[k]);
+        atomicAdd(&g_fastCycles[5], 1ull);
+    }
+#endif
 }
 
 // ------------------------------------------------------------------ quadtree
@@ -977,8 +1030,9 @@ struct sslam_orb {
     Plan plan;
     const uint8_t* lastImg0 = nullptr; size_t lastImg0Pitch = 0, lastImg0Stride = 0; bool lastInPlace = false;      // the image of the last call (debug taps of level 0)
     std::vector<CellInfo> cells;
+    std::vector<StripInfo> strips;      // k_fast_cells' work list: the cells in strips of up to FAST_STRIP_K (fast_strips.h)
     std::vector<short> tabs;
-    DevBuf dCells, dTabs, dPyr, dCellCount, dCand, dBufA, dBufB, dSel, dSelCount;
+    DevBuf dCells, dStrips, dTabs, dPyr, dCellCount, dCand, dBufA, dBufB, dSel, dSelCount;
     DevBuf dImg, dKp, dDesc, dCounts;       // single-frame host path staging
     HostPinned hImg, hOut;
     int wsFrames = 0;
@@ -1076,7 +1130,7 @@ static int build_plan(sslam_orb* o, int w, int h) {
                     P.maxCellW = std::max(P.maxCellW, cw); P.maxCellH = std::max(P.maxCellH, chh);
                     {   // as k_fast_cells lays the tile out: tile column of pixel 0 = off + 3, off = (x0 - 3) & 3
                         const int T0 = ((c.x0 - 3) & 3) + 3, gmin = T0 >> 2, ng = ((T0 + cw - 1) >> 2) - gmin + 1;
-                        c.magic = (1u << 19) / (unsigned)cw + 1; c.gmagic = (1u << 19) / (unsigned)ng + 1;
+                        c.magic = (1u << 19) / (unsigned)cw + 1; c.gmagic = (1u << 19) / (unsigned)ng + 1;      // (kept: the cell table stays byte for byte; k_fast_cells reads the strip's)
                     }
                     o->cells.push_back(c);
                 }
@@ -1143,11 +1197,17 @@ static int build_plan(sslam_orb* o, int w, int h) {
     }
     P.pyrFrame = (off + 16 + 255) & ~(size_t)255;      // 16 spare bytes: k_resize reads whole dwords past a row's last pixel
     P.nCellsFrame = (int)o->cells.size();
+    // k_fast_cells' strips: the cell table, candOff and the candidate layout stay what they are -- a strip only says which cells one wave takes together
+    if (!sslam_fast::fast_build_strips(o->cells.data(), (int)o->cells.size(), o->strips)) { set_error("image size %dx%d: a FAST cell is larger than k_fast_cells' index range", w, h); return SSLAM_ERR_UNSUPPORTED; }
+    P.nStripsFrame = (int)o->strips.size();
+    for (const StripInfo& s : o->strips) P.maxStripW = std::max(P.maxStripW, s.x1 - s.x0);
     P.candFrame = std::max(candOff, 1);
     P.selFrame = selOff;
     if (o->dCells.ensure(std::max<size_t>(o->cells.size(), 1) * sizeof(CellInfo)) != SSLAM_OK) return SSLAM_ERR_HIP;
+    if (o->dStrips.ensure(std::max<size_t>(o->strips.size(), 1) * sizeof(StripInfo)) != SSLAM_OK) return SSLAM_ERR_HIP;
     if (o->dTabs.ensure(std::max<size_t>(o->tabs.size(), 1) * sizeof(short)) != SSLAM_OK) return SSLAM_ERR_HIP;
     if (!o->cells.empty()) SSLAM_HIP(hipMemcpy(o->dCells.p, o->cells.data(), o->cells.size() * sizeof(CellInfo), hipMemcpyHostToDevice));
+    if (!o->strips.empty()) SSLAM_HIP(hipMemcpy(o->dStrips.p, o->strips.data(), o->strips.size() * sizeof(StripInfo), hipMemcpyHostToDevice));
     if (!o->tabs.empty()) SSLAM_HIP(hipMemcpy(o->dTabs.p, o->tabs.data(), o->tabs.size() * sizeof(short), hipMemcpyHostToDevice));
     o->planW = w; o->planH = h;
     o->wsFrames = 0;
@@ -1210,7 +1270,7 @@ extern "C" int sslam_orb_destroy(sslam_orb* o) {
     if (!o) return SSLAM_OK;
     (void)hipSetDevice(o->ctx->device);
     (void)hipStreamSynchronize(o->ctx->stream);
-    DevBuf* bufs[] = {&o->dCells, &o->dTabs, &o->dPyr, &o->dCellCount, &o->dCand, &o->dBufA, &o->dBufB, &o->dSel, &o->dSelCount, &o->dImg, &o->dKp, &o->dDesc, &o->dCounts, &o->dToep};
+    DevBuf* bufs[] = {&o->dCells, &o->dStrips, &o->dTabs, &o->dPyr, &o->dCellCount, &o->dCand, &o->dBufA, &o->dBufB, &o->dSel, &o->dSelCount, &o->dImg, &o->dKp, &o->dDesc, &o->dCounts, &o->dToep};
     for (DevBuf* b : bufs) b->release();
     o->hImg.release(); o->hOut.release();
     delete o;
@@ -1320,11 +1380,11 @@ static int orb_front(sslam_orb* o, Plan& P, const uint8_t* d_images, int w, int 
     }
     if (o->gateEvent) SSLAM_HIP(hipStreamWaitEvent(st, o->gateEvent, 0));      // sslam_orb_set_gate_event: the pyramid is built ahead, the rest waits (e.g. for the line branch's sequential core)
     if (P.nCellsFrame > 0) {
-        const int tileP = fast_tile_pitch(P.maxCellW), scP = fast_score_pitch(P.maxCellW);
-        const size_t lds = fast_lds_bytes(P.maxCellW, P.maxCellH);
-        dim3 grd(8 * ((P.nCellsFrame + 7) / 8), nframes);
-        { sslam::ProfScope _ps(o->ctx, "k_fast_cells", st); hipLaunchKernelGGL(k_fast_cells, grd, dim3(64), lds, st, pyr, P.pyrFrame, P, o->dCells.as<CellInfo>(), o->dCand.as<unsigned>(),
-                           o->dCellCount.as<int>(), o->iniTh, o->minTh, tileP, scP); }
+        const int tileP = fast_tile_pitch(P.maxStripW);
+        const size_t lds = fast_lds_bytes(P.maxStripW, P.maxCellH);
+        dim3 grd(8 * ((P.nStripsFrame + 7) / 8), nframes);
+        { sslam::ProfScope _ps(o->ctx, "k_fast_cells", st); hipLaunchKernelGGL(k_fast_cells, grd, dim3(64), lds, st, pyr, P.pyrFrame, P, o->dStrips.as<StripInfo>(), o->dCells.as<CellInfo>(),
+                           o->dCand.as<unsigned>(), o->dCellCount.as<int>(), o->iniTh, o->minTh, tileP); }
     }
     return SSLAM_OK;
 }
@@ -1596,3 +1656,14 @@ extern "C" int sslam_orb_set_camera(sslam_orb* o, const sslam_camera* cam) {
 }
 
 extern "C" sslam_ctx* sslam_orb_context(sslam_orb* o) { return o ? o->ctx : nullptr; }
+
+#ifdef SSLAM_FAST_CYCLES
+// k_fast_cells' phase clocks, summed over every strip of every launch since the last reset (tools/fast_cycles.py; variant builds only): out[0..4] = cycles of
+// set-up + staging + zeroing, pass A, pass B, suppression, emission; out[5] = strips
+extern "C" int sslam_testing_orb_fast_cycles(unsigned long long* out8, int reset) {
+    SSLAM_HIP(hipDeviceSynchronize());
+    if (out8) SSLAM_HIP(hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_fastCycles), sizeof(unsigned long long) * 8));
+    if (reset) { const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; SSLAM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_fastCycles), z, sizeof(z))); }
+    return SSLAM_OK;
+}
+#endif
