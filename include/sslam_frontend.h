@@ -215,6 +215,66 @@ int sslam_two_view_ransac_batch_dev(sslam_ctx* ctx, const sslam_keypoint* d_kp1,
         const int32_t* d_sets /* NULL or [npairs*iterations*8] */, int iterations, float sigma, uint32_t seed,
         sslam_two_view_result* d_result, uint8_t* d_inliers /* [npairs*cap] */, void* stream);
 
+/* Sim3Solver (src/Sim3Solver.cc), the RANSAC of LoopClosing::ComputeSim3 (src/LoopClosing.cc:279-306) between SearchByBoW (:269: sslam_orb_search_by_bow_keyframes_batch_dev) and
+ * SearchBySim3 (:328: sslam_fuse_search_batch_dev, which takes the s, R, t found here): the constructor (:37-112), SetRansacParameters (:114-138) and iterate (:140-207) with
+ * ComputeSim3 (:226-337, Horn's closed form on three drawn correspondences), CheckInliers (:340-364) and Project (:382-403).  What follows in the reference -- OptimizeSim3
+ * (g2o), the KeyFrameDatabase, the bookkeeping of :308-347 -- stays with the caller.
+ * The pool and d_pairs are those of sslam_orb_search_by_bow_keyframes_batch_dev: keyframe slot k owns rows [k*cap, k*cap + d_n[k]) of d_kp (mvKeysUn; only `octave` is read),
+ * d_valid (= GetMapPoint(i) && !isBad(); NULL: every row is valid) and d_x3dc; a count below 0 is read as 0, one above cap as cap; pair p is (kf1, kf2) = (d_pairs[2p],
+ * d_pairs[2p+1]); d_matches12 is that call's output, used where it lies.  d_x3dc[(k*cap + i)*3 .. +3) is the camera-frame position Rcw * Xw + tcw (:94-98) of the map point at
+ * row i of slot k: the caller fills it (poses and map points stay with the tracker) and it is read only for rows that enter a correspondence.  d_K[k*4 .. +4) = fx fy cx cy of
+ * slot k (mK1 / mK2, :105-106); level_sigma2 is HOST memory, mvLevelSigma2 of nlevels entries (one scale pyramid for all slots).
+ *   a correspondence  keyframe-1 row i1 < n[kf1] with 0 <= m = d_matches12[p*cap + i1] < n[kf2], valid[kf1][i1], valid[kf2][m] and both octaves in [0, nlevels).  The list in
+ *         ascending i1 is mvnIndices1; N is its length.  The reference's GetIndexInKeyFrame lookups (:75-79) are the rows themselves: a map point observed at row i of a keyframe
+ *         has index i there.  A caller that knows otherwise (the lookup would give -1 or another row) clears d_valid for that row.
+ *   gates  mvnMaxError is a vector<size_t> (include/Sim3Solver.h:78-79): a correspondence is an inlier when both squared errors are < the INTEGER part of 9.210 * sigma2[octave]
+ *         (13 for sigma2 = 1.44, not 13.26).
+ *   d_state, in/out, one per pair, is the solver object: zero-filled = a new Sim3Solver, and repeated calls resume exactly as repeated iterate(new_iterations, ..) calls do
+ *         (mnIterations and the best hypothesis carry over; after a return best_inliers stays raised).  new_iterations is iterate's nIterations: 5 in LoopClosing (:296),
+ *         max_iterations for find().  probability, min_inliers, max_iterations are SetRansacParameters' (0.99, 20, 300 at :284); max_its = mRansacMaxIts for the pair's N, from a
+ *         table of cap + 1 entries the context keeps and rebuilds (on the host, with libm) only when (probability, min_inliers, max_iterations, cap) change.  iterate returns
+ *         at the first iteration whose count is >= every earlier one (best_inliers included) and > min_inliers; among equal counts the later iteration becomes the best.
+ *         N < min_inliers: nothing is iterated, no_more = 1, max_its = 0 and the in/out words keep their values.  Otherwise no_more = 1 when the call did not return a
+ *         hypothesis and its_done >= max_its afterwards (bNoMore, :203; a return leaves it 0, as :142 does).
+ *         A pair with a slot outside [0, nkeyframes) is skipped: n = 0, no_more = 1, found_it = -1, max_its = n_inliers = 0; its in/out words and d_inliers rows are not written.
+ *   d_inliers[p*cap + i1], i1 < n[kf1]: 1 for an inlier of the returned hypothesis (vbInliers, :195-197), else 0; all 0 when found_it < 0.  Rows at or past the count are not
+ *         touched.
+ *   d_sets  NULL: iteration `it` of pair p draws as :166-177 do with randi = hash32(seed, p, it, j) % remaining (csrc/two_view_math.h states hash32); with N < 3 nothing can
+ *         be drawn and the iteration counts as one with an index out of range.  Otherwise d_sets[(p*max_iterations + it)*3 + j] are indices into the correspondence list by
+ *         ABSOLUTE iteration number (equal indices are legal); a set with an index outside [0, N) makes a hypothesis that never becomes the best and never returns.
+ * What the reference leaves to OpenCV and libm (cv::eigen, atan2 + cv::Rodrigues, the matrix expressions, cv::reduce, cv::pow) is restated by decision D16 of DESIGN.md;
+ * everything else is the reference's arithmetic operation for operation (csrc/sim3_math.h).
+ * One launch on `stream` (NULL: the context's stream) behind at most one upload of the table, no synchronise; every pointer but level_sigma2 is a device pointer; every output
+ * word has one writer.  SSLAM_ERR_INVALID (nothing enqueued): a NULL ctx or pointer other than d_valid and d_sets, a typed buffer that is not 4-byte aligned, cap < 1,
+ * nkeyframes < 0, npairs < 0, nlevels outside 1 .. 64, min_inliers < 1, max_iterations < 1, new_iterations < 1, probability not in (0, 1), npairs * cap or nkeyframes * cap
+ * >= 2^31, with d_sets npairs * max_iterations >= 2^28.  SSLAM_ERR_UNSUPPORTED (nothing enqueued): cap > 3072 (the correspondences sit in LDS, 48 bytes each).  npairs == 0 is
+ * SSLAM_OK and enqueues nothing.  The single call takes one pair from host memory (valid1 and valid2 both NULL or both given), runs it as pair 0 of the same kernel with
+ * cap = max(n1, n2) and synchronises; sets holds max_iterations x 3 indices. */
+typedef struct sslam_sim3_state {      /* 84 bytes, no padding; zero-filled = a new Sim3Solver */
+    int32_t its_done;        /* in/out  mnIterations */
+    int32_t best_inliers;    /* in/out  mnBestInliers */
+    int32_t best_it;         /* in/out  iteration that holds the best, -1 none yet (read as -1 when its_done == 0) */
+    int32_t n;               /* out     N: correspondences the call saw */
+    int32_t max_its;         /* out     mRansacMaxIts after SetRansacParameters; 0 when n < min_inliers */
+    int32_t found_it;        /* out     the iteration iterate() returned at, -1 when it returned empty */
+    int32_t n_inliers;       /* out     nInliers of that return, else 0 */
+    int32_t no_more;         /* out     bNoMore */
+    float s12, R12[9], t12[3];  /* in/out  mBestScale / mBestRotation / mBestTranslation (row-major) */
+} sslam_sim3_state;
+int sslam_sim3_ransac_batch_dev(sslam_ctx* ctx, const sslam_keypoint* d_kp, const float* d_x3dc, const uint8_t* d_valid,
+        const int32_t* d_n, int cap, int nkeyframes, const float* d_K /* [nkeyframes*4] fx fy cx cy */,
+        const float* level_sigma2 /* HOST, nlevels */, int nlevels,
+        const int32_t* d_pairs, int npairs, const int32_t* d_matches12,
+        int fix_scale, double probability, int min_inliers, int max_iterations, int new_iterations,
+        const int32_t* d_sets /* NULL or [npairs*max_iterations*3] */, uint32_t seed,
+        sslam_sim3_state* d_state /* [npairs] in/out */, uint8_t* d_inliers /* [npairs*cap] */, void* stream);
+int sslam_sim3_ransac(sslam_ctx* ctx, const sslam_keypoint* kp1, const float* x3dc1, const uint8_t* valid1, int n1, const float K1[4],
+        const sslam_keypoint* kp2, const float* x3dc2, const uint8_t* valid2, int n2, const float K2[4],
+        const float* level_sigma2, int nlevels, const int32_t* matches12,
+        int fix_scale, double probability, int min_inliers, int max_iterations, int new_iterations,
+        const int32_t* sets /* NULL or [max_iterations*3] */, uint32_t seed,
+        sslam_sim3_state* state /* in/out */, uint8_t* inliers /* [n1] */);
+
 /* The projection-window matcher family.  The tracker keeps the projection / visibility logic (poses, map
  * points: host state) and hands over one query per map point or map line; the device replays the
  * window search, the best/second-best Hamming selection, the level-consistent ratio test, the

@@ -131,6 +131,17 @@ int sslam_testing_two_view_hypotheses(sslam_ctx* ctx, const sslam_keypoint* kp1,
                                       int iterations, float sigma, uint32_t seed, int pair, sslam_two_view_result* result, uint8_t* inliers,
                                       int32_t* sets_out, float* mats_out, float* scores_out);
 
+/* sslam_sim3_ransac for one host pair with EVERY iteration the reference's loop ran copied back, so that a wrong hypothesis that neither becomes the best nor returns is visible:
+ * the same kernel with its stores enabled, run as pair `pair` of a batch (the draw of src/Sim3Solver.cc:166-177 hashes the pair index; the single call is pair 0).  By absolute
+ * iteration it < max_iterations: sets_out[it*3 .. +3) = the three indices into the correspondence list, mats_out[it*13 .. +13) = ms12i, mR12i (row-major), mt12i,
+ * counts_out[it] = mnInliersi (-1 for a set with an index out of range, whose matrices are zero).  Rows of iterations this call did not run -- before its_done, past the
+ * return -- are zero.  state and inliers as sslam_sim3_ransac. */
+int sslam_testing_sim3_hypotheses(sslam_ctx* ctx, const sslam_keypoint* kp1, const float* x3dc1, const uint8_t* valid1, int n1, const float K1[4],
+                                  const sslam_keypoint* kp2, const float* x3dc2, const uint8_t* valid2, int n2, const float K2[4], const float* level_sigma2, int nlevels,
+                                  const int32_t* matches12, int fix_scale, double probability, int min_inliers, int max_iterations, int new_iterations,
+                                  const int32_t* sets, uint32_t seed, int pair, sslam_sim3_state* state, uint8_t* inliers,
+                                  int32_t* sets_out, float* mats_out, int32_t* counts_out);
+
 #ifdef __cplusplus
 }
 #endif

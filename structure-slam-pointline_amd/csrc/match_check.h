@@ -28,5 +28,10 @@ template <unsigned N, class... Ptr> inline bool all_aligned(const Ptr*... p) {
 inline bool rows_in_range(int cap) { return cap >= 0 && cap < MAX_ROWS; }
 // slots * cap rows (or jobs * queries) are indexed with a signed 32-bit int on the device
 inline bool fits_31_bits(int slots, int cap) { return (long long)slots * (long long)cap < (1ll << 31); }
+// The parameters sslam_sim3_ransac and sslam_sim3_ransac_batch_dev share (sim3.hip): the host table of level_sigma2 (nlevels in 1 .. 64), SetRansacParameters' arguments and
+// iterate's nIterations.  probability lies strictly inside (0, 1): log(1 - probability) has to be finite and negative; a NaN fails both comparisons.
+inline bool sim3_params_ok(const float* level_sigma2, int nlevels, double probability, int min_inliers, int max_iterations, int new_iterations) {
+    return level_sigma2 && nlevels >= 1 && nlevels <= 64 && probability > 0.0 && probability < 1.0 && min_inliers >= 1 && max_iterations >= 1 && new_iterations >= 1;
+}
 
 }  // namespace sslam

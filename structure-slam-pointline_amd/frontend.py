@@ -37,6 +37,10 @@ TWO_VIEW_RESULT_DTYPE = np.dtype([("nmatches", "<i4"), ("model", "<i4"), ("best_
                                   ("rh", "<f4"), ("H21", "<f4", (9,)), ("F21", "<f4", (9,))])      # sslam_two_view_result
 assert TWO_VIEW_RESULT_DTYPE.itemsize == 100
 
+SIM3_STATE_DTYPE = np.dtype([("its_done", "<i4"), ("best_inliers", "<i4"), ("best_it", "<i4"), ("n", "<i4"), ("max_its", "<i4"), ("found_it", "<i4"), ("n_inliers", "<i4"),
+                             ("no_more", "<i4"), ("s12", "<f4"), ("R12", "<f4", (9,)), ("t12", "<f4", (3,))])      # sslam_sim3_state
+assert SIM3_STATE_DTYPE.itemsize == 84
+
 _lib = None
 
 PIX_GRAY, PIX_RGB, PIX_BGR, PIX_RGBA, PIX_BGRA = 0, 1, 2, 3, 4      # SSLAM_PIX_* (include/sslam_frontend.h)
@@ -191,6 +195,41 @@ class Context:
         enqueues on `stream` (None: the context's) and returns without synchronising"""
         _chk(lib().sslam_two_view_ransac_batch_dev(self.h, _p(d_kp1), _p(d_n1), _p(d_kp2), _p(d_n2), int(cap), int(npairs), _p(d_matches12), _p(d_sets), int(iterations),
                                                    C.c_float(sigma), C.c_uint32(seed), _p(d_result), _p(d_inliers), C.c_void_p(stream or 0)))
+
+    def sim3_ransac(self, kp1, x3dc1, valid1, K1, kp2, x3dc2, valid2, K2, level_sigma2, matches12, state=None, fix_scale=False, probability=0.99, min_inliers=20,
+                    max_iterations=300, new_iterations=5, sets=None, seed=0):
+        """One iterate(new_iterations, ..) of a Sim3Solver (sslam_sim3_ransac) on one pair of keyframes: kp (KP_DTYPE: mvKeysUn), x3dc float32 [n, 3] (the map points in the
+        camera frame), valid uint8 [n] or None (both or neither), K = fx fy cx cy, matches12 int32 [n1], state a SIM3_STATE_DTYPE record to resume (None: a new solver), sets
+        None (the library draws) or [max_iterations, 3] indices into the correspondence list.  Returns (state: a SIM3_STATE_DTYPE record, inliers: uint8 [n1])"""
+        kp1 = np.ascontiguousarray(kp1, KP_DTYPE); kp2 = np.ascontiguousarray(kp2, KP_DTYPE)
+        x1 = np.ascontiguousarray(x3dc1, np.float32).reshape(-1, 3); x2 = np.ascontiguousarray(x3dc2, np.float32).reshape(-1, 3)
+        v1 = None if valid1 is None else np.ascontiguousarray(valid1, np.uint8); v2 = None if valid2 is None else np.ascontiguousarray(valid2, np.uint8)
+        m12 = np.ascontiguousarray(matches12, np.int32)
+        assert len(m12) == len(kp1) == len(x1) and len(kp2) == len(x2) and (v1 is None or len(v1) == len(kp1)) and (v2 is None or len(v2) == len(kp2))
+        K1 = np.ascontiguousarray(K1, np.float32).reshape(4); K2 = np.ascontiguousarray(K2, np.float32).reshape(4)
+        sig = np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        if sets is not None:
+            sets = np.ascontiguousarray(sets, np.int32)
+            assert sets.shape == (int(max_iterations), 3)
+        st = np.zeros(1, SIM3_STATE_DTYPE)
+        if state is not None:
+            st[0] = state
+        inl = np.zeros(len(kp1), np.uint8)
+        _chk(lib().sslam_sim3_ransac(self.h, _p(kp1), _p(x1), _p(v1), len(kp1), _p(K1), _p(kp2), _p(x2), _p(v2), len(kp2), _p(K2), _p(sig), len(sig), _p(m12), int(bool(fix_scale)),
+                                     C.c_double(probability), int(min_inliers), int(max_iterations), int(new_iterations), _p(sets), C.c_uint32(seed), _p(st), _p(inl)))
+        return st[0], inl
+
+    def sim3_ransac_batch_dev(self, d_kp, d_x3dc, d_valid, d_n, cap, nkeyframes, d_K, level_sigma2, d_pairs, npairs, d_matches12, d_state, d_inliers, fix_scale=False,
+                              probability=0.99, min_inliers=20, max_iterations=300, new_iterations=5, d_sets=None, seed=0, stream=None, nlevels=None):
+        """sslam_sim3_ransac_batch_dev on device tensors / pointers over the keyframe pool of search_by_bow_keyframes_batch_dev: slot k owns rows [k*cap, (k+1)*cap) of d_kp,
+        d_valid (None: all valid) and d_x3dc (float32, 3 per row), d_K holds fx fy cx cy per slot, level_sigma2 is a HOST float32 array, pair p owns rows [p*cap, (p+1)*cap) of
+        d_matches12 and d_inliers (uint8) and the SIM3_STATE_DTYPE record p of d_state (in/out, 84 bytes each), d_sets is None or [npairs, max_iterations, 3] int32; enqueues
+        on `stream` (None: the context's) and returns without synchronising"""
+        sig = None if level_sigma2 is None else np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        _chk(lib().sslam_sim3_ransac_batch_dev(self.h, _p(d_kp), _p(d_x3dc), _p(d_valid), _p(d_n), int(cap), int(nkeyframes), _p(d_K), _p(sig),
+                                               int((0 if sig is None else len(sig)) if nlevels is None else nlevels), _p(d_pairs), int(npairs), _p(d_matches12), int(bool(fix_scale)),
+                                               C.c_double(probability), int(min_inliers), int(max_iterations), int(new_iterations), _p(d_sets), C.c_uint32(seed), _p(d_state),
+                                               _p(d_inliers), C.c_void_p(stream or 0)))
 
     def search_by_projection(self, kind, mode, feats, desc, queries, qdesc, occupied=None, uright=None, nnratio=0.8, th_dist=100,
                              check_orientation=True, bounds=(0.0, 640.0, 0.0, 480.0)):
