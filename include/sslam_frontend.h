@@ -183,7 +183,7 @@ int sslam_orb_search_for_initialization_batch_dev(sslam_ctx* ctx,
  * below are their inputs.  kp1 / kp2 are the UNDISTORTED keypoints (mvKeysUn: sslam_undistort_keypoints_batch_dev); matches12[i] is the keypoint of frame 2 matched to keypoint i
  * of frame 1 or negative (vnMatches12: sslam_orb_search_for_initialization_batch_dev's d_matches12); a row counts as matched when 0 <= matches12[i] < n2, and the matched rows in
  * ascending i are the match list (mvMatches12, :67-76).  sigma is mSigma (1.0 in Tracking), iterations mMaxIterations (200).
- *   sets  NULL: iteration `it` of pair p draws its eight matches as :93-108 do, with randi = hash32(seed, p, it, j) % remaining (csrc/two_view_math.h states hash32; the
+ *   sets  NULL: iteration `it` of pair p draws its eight matches as :93-108 do, with randi = hash32(seed, p, it, j) % remaining (csrc/ransac_draw.h states hash32; the
  *         reference's rand() stream is per process and not reproducible per pair).  Otherwise sets[(p * iterations + it) * 8 + j] are indices into the match list and replace
  *         the draw -- the hook for a caller that wants the reference's own rand() stream.  An iteration with an index outside [0, nmatches) gets zero matrices and the score 0:
  *         it never wins.  H and F share the sets, as in the reference.
@@ -239,7 +239,7 @@ int sslam_two_view_ransac_batch_dev(sslam_ctx* ctx, const sslam_keypoint* d_kp1,
  *         A pair with a slot outside [0, nkeyframes) is skipped: n = 0, no_more = 1, found_it = -1, max_its = n_inliers = 0; its in/out words and d_inliers rows are not written.
  *   d_inliers[p*cap + i1], i1 < n[kf1]: 1 for an inlier of the returned hypothesis (vbInliers, :195-197), else 0; all 0 when found_it < 0.  Rows at or past the count are not
  *         touched.
- *   d_sets  NULL: iteration `it` of pair p draws as :166-177 do with randi = hash32(seed, p, it, j) % remaining (csrc/two_view_math.h states hash32); with N < 3 nothing can
+ *   d_sets  NULL: iteration `it` of pair p draws as :166-177 do with randi = hash32(seed, p, it, j) % remaining (csrc/ransac_draw.h states hash32); with N < 3 nothing can
  *         be drawn and the iteration counts as one with an index out of range.  Otherwise d_sets[(p*max_iterations + it)*3 + j] are indices into the correspondence list by
  *         ABSOLUTE iteration number (equal indices are legal); a set with an index outside [0, N) makes a hypothesis that never becomes the best and never returns.
  * What the reference leaves to OpenCV and libm (cv::eigen, atan2 + cv::Rodrigues, the matrix expressions, cv::reduce, cv::pow) is restated by decision D16 of DESIGN.md;

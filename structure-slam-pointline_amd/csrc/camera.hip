@@ -31,7 +31,7 @@ int sslam::undistort_launch(sslam_ctx* ctx, const sslam_camera& cam, const sslam
                             sslam_keypoint* d_kp_un, void* stream) {
     const unsigned rows = (unsigned)nframes * (unsigned)cap;
     if (rows == 0) return SSLAM_OK;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t st = pick(ctx, stream);
     const dim3 grid((rows + 255) / 256);
     sslam::ProfScope _ps(ctx, "k_undistort_kp", st);
     if (cam.k1 == 0.0f) hipLaunchKernelGGL(k_undistort_kp<false>, grid, dim3(256), 0, st, d_kp, d_counts, n, cap, rows, d_kp_un, cam);

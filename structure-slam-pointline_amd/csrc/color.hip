@@ -67,7 +67,7 @@ void launch(const uint8_t* src, size_t pitch, size_t image_stride, uint8_t* dst,
 int sslam::gray_from_color_launch(sslam_ctx* ctx, int format, const uint8_t* d_src, int w, int h, size_t pitch, size_t image_stride, int nframes,
                                   uint8_t* d_gray, size_t gray_pitch, size_t gray_image_stride, void* stream) {
     if (nframes == 0) return SSLAM_OK;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t st = pick(ctx, stream);
     const unsigned nchunk = (unsigned)((w + 15) / 16);
     const size_t perFrame = (size_t)h * nchunk;                        // <= 2^31 (gray_layout_ok)
     const int group = (int)std::min<size_t>((size_t)nframes, ((size_t)1 << 31) / perFrame);      // frames per launch: the lane index stays below 2^31

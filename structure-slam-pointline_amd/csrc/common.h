@@ -10,6 +10,7 @@
 #include <vector>
 #include <mutex>
 #include "../../include/sslam_frontend.h"
+#include "match_plan.h"
 
 namespace sslam {
 
@@ -94,7 +95,7 @@ enum {
     SCR_SFI_STATE = 3,       // sslam_orb_search_for_initialization_batch_dev: per-pair state (SfiArgs::scratch)
     SCR_SFI_STAGE = 4,       // sslam_orb_search_for_initialization: the pair and its results
     SCR_LINE_MATCH = 5,      // sslam_line_match
-    SCR_CALL = 6,            // the arena of search_proj_core, sslam_hamming_knn2_frames, sslam_distinctive_descriptors, sslam_fuse_search, sslam_orb_search_for_triangulation, bow_core, sslam_two_view_ransac (two_view.hip), sslam_sim3_ransac (sim3.hip)
+    SCR_CALL = 6,            // the arena of search_proj_core, sslam_hamming_knn2_frames, sslam_distinctive_descriptors, sslam_fuse_search, sslam_orb_search_for_triangulation, bow_core, sslam_two_view_ransac (two_view.hip), sslam_sim3_ransac (sim3.hip): laid out with ArenaLayout (match_plan.h), staged field by field through Staging (below) except by search_proj_core
     SCR_UPLOAD = 7,          // host features that a core with an arena in SCR_CALL reads (sslam_search_by_projection, sslam_bow_transform); the arena of search_by_bow_core
     SCR_COUNT = 8
 };
@@ -174,9 +175,47 @@ struct ProfScope {
 };
 }  // namespace sslam
 
-// ---- device helpers (wave64) ---------------------------------------------------
+namespace sslam {
+// the stream of a call: the caller's, or the context's own
+inline hipStream_t pick(sslam_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
+
+// Field-by-field staging of a host call through its arena (SCR_CALL, SCR_UPLOAD), bound to the arena's base and the call's stream: in() copies a host field up and
+// skips an empty or absent one, out() copies a result back, done() is the one wait at the end of the call.
+struct Staging {
+    uint8_t* base; hipStream_t st;
+    int in(size_t off, const void* src, size_t bytes) const { if (src && bytes) SSLAM_HIP(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, st)); return SSLAM_OK; }
+    int out(void* dst, size_t off, size_t bytes) const { if (bytes) SSLAM_HIP(hipMemcpyAsync(dst, base + off, bytes, hipMemcpyDeviceToHost, st)); return SSLAM_OK; }
+    int done() const { SSLAM_HIP(hipStreamSynchronize(st)); return SSLAM_OK; }
+};
+}  // namespace sslam
+
 #ifdef __HIPCC__
 namespace sslam {
+// ---- launches ------------------------------------------------------------------
+// a launch with more dynamic LDS than the default maximum has to be allowed per kernel
+inline int allow_dynamic_lds(const void* kernel, size_t bytes) {
+    if (bytes > DYNAMIC_LDS_DEFAULT_MAX) SSLAM_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return SSLAM_OK;
+}
+// The one launch of a kernel template k<bool TAP>(Args): k<false> is the product's, k<true> the same kernel with the stores of a testing tap compiled in.  The product
+// library holds k<false> alone: SSLAM_WITH_TAP(k) names both instantiations for launch_tapped, the second only under SSLAM_TESTING.
+#ifdef SSLAM_TESTING
+#define SSLAM_WITH_TAP(k) k<false>, k<true>
+#else
+#define SSLAM_WITH_TAP(k) k<false>, (decltype(&k<false>))nullptr
+#endif
+template <class Args>
+inline int launch_tapped(sslam_ctx* ctx, const char* name, void (*product)(Args), void (*tapped)(Args), bool tap, unsigned grid, unsigned threads, size_t ldsBytes, hipStream_t st, const Args& A) {
+    if (tap && !tapped) { set_error("%s: no tap in this library", name); return SSLAM_ERR_UNSUPPORTED; }
+    void (*const k)(Args) = tap ? tapped : product;
+    if (int rc = allow_dynamic_lds((const void*)k, ldsBytes)) return rc;
+    ProfScope _ps(ctx, name, st);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(threads), ldsBytes, st, A);
+    SSLAM_HIP(hipGetLastError());
+    return SSLAM_OK;
+}
+
+// ---- device helpers (wave64) ---------------------------------------------------
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 

@@ -8,7 +8,8 @@
 // Which kernel a call launches depends on its sizes alone: the rules are the pure host functions of match_plan.h, and an entry
 // point reads as validate, lock, lay out, stage, switch on the plan's form with one launch per case, copy back.  The batches that keep
 // their rows in LDS or in global memory share one plan (match_plan.h: batch_plan) and one launch path (launch_batch); the alignment and
-// size rules of device-resident batches are the named checks of match_check.h.
+// size rules of device-resident batches are the named checks of match_check.h.  The stream choice (pick), the dynamic-LDS opt-in (allow_dynamic_lds) and the
+// field-by-field staging of a single call through its arena (Staging) are common.h's, shared with two_view.hip and sim3.hip.
 #include "common.h"
 #include "match_plan.h"
 #include "match_check.h"
@@ -27,12 +28,6 @@ namespace {
 }  // namespace
 
 // =============================================================== host side
-static hipStream_t pick(sslam_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
-// a launch with more dynamic LDS than the default maximum has to be allowed per kernel
-static int allow_dynamic_lds(const void* kernel, size_t bytes) {
-    if (bytes > DYNAMIC_LDS_DEFAULT_MAX) SSLAM_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return SSLAM_OK;
-}
 // the one launch of a batch_plan (match_plan.h): the kernel's <true> instantiation with the rows in dynamic LDS, or <false> on global memory
 template <class Args>
 static int launch_batch(sslam_ctx* ctx, const char* name, void (*lds)(Args), void (*global)(Args), const BatchPlan& P, unsigned grid, hipStream_t st, const Args& A) {
@@ -334,9 +329,8 @@ extern "C" int sslam_search_by_projection(sslam_ctx* ctx, int kind, int mode, co
     int rc;
     if ((rc = ctx->scratch[SCR_UPLOAD].ensure(L.size()))) return rc;
     uint8_t* B = ctx->scratch[SCR_UPLOAD].as<uint8_t>();
-    SSLAM_HIP(hipMemcpyAsync(B + oF, feats, fsz * n, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oD, desc, 32 * (size_t)n, hipMemcpyHostToDevice, st));
-    if (uright) SSLAM_HIP(hipMemcpyAsync(B + oU, uright, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    const Staging S{B, st};
+    if ((rc = S.in(oF, feats, fsz * n)) || (rc = S.in(oD, desc, 32 * (size_t)n)) || (rc = S.in(oU, uright, 4 * (size_t)n))) return rc;
     return search_proj_core(ctx, kind, mode, B + oF, B + oD, n, bounds, uright ? (const float*)(B + oU) : nullptr, occupied, queries, qdesc, nq,
                             nnratio, th_dist, check_orientation, assigned_out, nmatches_out);
 }
@@ -607,13 +601,12 @@ extern "C" int sslam_distinctive_descriptors(sslam_ctx* ctx, const uint8_t* desc
     const size_t oD = L.take(32 * (size_t)std::max(total, 1)), oP = L.take(4 * (size_t)(nsets + 1)), oB = L.take(4 * (size_t)nsets);
     if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
     uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
-    if (total > 0) SSLAM_HIP(hipMemcpyAsync(B + oD, desc, 32 * (size_t)total, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oP, ptr, 4 * (size_t)(nsets + 1), hipMemcpyHostToDevice, st));
+    const Staging S{B, st};
+    if ((rc = S.in(oD, desc, 32 * (size_t)total)) || (rc = S.in(oP, ptr, 4 * (size_t)(nsets + 1)))) return rc;
     { sslam::ProfScope _ps(ctx, "k_distinctive", st); hipLaunchKernelGGL(k_distinctive, dim3(std::min(nsets, 4096)), dim3(64), 0, st, B + oD, (const int32_t*)(B + oP), nsets, (int32_t*)(B + oB)); }
     SSLAM_HIP(hipGetLastError());
-    SSLAM_HIP(hipMemcpyAsync(best_out, B + oB, 4 * (size_t)nsets, hipMemcpyDeviceToHost, st));
-    SSLAM_HIP(hipStreamSynchronize(st));
-    return SSLAM_OK;
+    if ((rc = S.out(best_out, oB, 4 * (size_t)nsets))) return rc;
+    return S.done();
 }
 
 // ---- the same choice for observation sets that name rows of a device-resident pool of keyframe slots, asynchronous (match_distinct.h)
@@ -661,9 +654,9 @@ extern "C" int sslam_fuse_search(sslam_ctx* ctx, const sslam_frame* kf, int chi2
     int rc;
     if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
     uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
-    SSLAM_HIP(hipMemcpyAsync(B + oQ, queries, sizeof(sslam_proj_query) * (size_t)nq, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oQD, qdesc, 32 * (size_t)nq, hipMemcpyHostToDevice, st));
-    if (chi2_mode) SSLAM_HIP(hipMemcpyAsync(B + oS, inv_level_sigma2, sizeof(float) * (size_t)nlevels, hipMemcpyHostToDevice, st));
+    const Staging S{B, st};
+    if ((rc = S.in(oQ, queries, sizeof(sslam_proj_query) * (size_t)nq)) || (rc = S.in(oQD, qdesc, 32 * (size_t)nq)) ||
+        (rc = S.in(oS, chi2_mode ? inv_level_sigma2 : nullptr, sizeof(float) * (size_t)nlevels))) return rc;
     FuseArgs A;
     A.kind = kf->kind; A.chi2 = chi2_mode; A.feats = kf->feats.p; A.desc = kf->desc.as<uint8_t>(); A.n = kf->n;
     A.minX = kf->bounds[0]; A.maxX = kf->bounds[1]; A.minY = kf->bounds[2]; A.maxY = kf->bounds[3];
@@ -671,10 +664,8 @@ extern "C" int sslam_fuse_search(sslam_ctx* ctx, const sslam_frame* kf, int chi2
     A.q = (const sslam_proj_query*)(B + oQ); A.qdesc = B + oQD; A.nq = nq; A.bestIdx = (int*)(B + oI); A.bestDist = (int*)(B + oD);
     { sslam::ProfScope _ps(ctx, "k_fuse_search", st); hipLaunchKernelGGL(k_fuse_search, dim3(std::min(nq, 8192)), dim3(64), 0, st, A); }
     SSLAM_HIP(hipGetLastError());
-    SSLAM_HIP(hipMemcpyAsync(best_idx_out, B + oI, 4 * (size_t)nq, hipMemcpyDeviceToHost, st));
-    SSLAM_HIP(hipMemcpyAsync(best_dist_out, B + oD, 4 * (size_t)nq, hipMemcpyDeviceToHost, st));
-    SSLAM_HIP(hipStreamSynchronize(st));
-    return SSLAM_OK;
+    if ((rc = S.out(best_idx_out, oI, 4 * (size_t)nq)) || (rc = S.out(best_dist_out, oD, 4 * (size_t)nq))) return rc;
+    return S.done();
 }
 
 // ---- the same candidate search for jobs (keyframe slot, block of queries) on a device-resident pool of keyframe slots, asynchronous
@@ -743,15 +734,11 @@ extern "C" int sslam_orb_search_for_triangulation(sslam_ctx* ctx, const sslam_fr
                  oM = L.take(4 * (size_t)n1), oQB = L.take(4 * (size_t)n1), oN = L.take(4);
     if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
     uint8_t* B = ctx->scratch[SCR_CALL].as<uint8_t>();
-    SSLAM_HIP(hipMemcpyAsync(B + oF1, free1, n1, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oF2, free2, n2, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oP1, node_kf1_ptr, 4 * (size_t)(nnodes + 1), hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oP2, node_kf2_ptr, 4 * (size_t)(nnodes + 1), hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oI1, kf1_idx, 4 * (size_t)total1, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oI2, kf2_idx, 4 * (size_t)total2, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oNO, nodeOf.data(), 4 * (size_t)total1, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oSF, scale_factors2, 4 * (size_t)nlevels, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(B + oSG, level_sigma2_2, 4 * (size_t)nlevels, hipMemcpyHostToDevice, st));
+    const Staging S{B, st};
+    const size_t ptrBytes = 4 * (size_t)(nnodes + 1), levelBytes = 4 * (size_t)nlevels;
+    if ((rc = S.in(oF1, free1, n1)) || (rc = S.in(oF2, free2, n2)) || (rc = S.in(oP1, node_kf1_ptr, ptrBytes)) || (rc = S.in(oP2, node_kf2_ptr, ptrBytes)) ||
+        (rc = S.in(oI1, kf1_idx, 4 * (size_t)total1)) || (rc = S.in(oI2, kf2_idx, 4 * (size_t)total2)) || (rc = S.in(oNO, nodeOf.data(), 4 * (size_t)total1)) ||
+        (rc = S.in(oSF, scale_factors2, levelBytes)) || (rc = S.in(oSG, level_sigma2_2, levelBytes))) return rc;
     SSLAM_HIP(hipMemsetAsync(B + oM, 0xFF, 4 * (size_t)n1, st));
     TriArgs A;
     A.kp1 = kf1->feats.as<sslam_keypoint>(); A.d1 = kf1->desc.as<uint8_t>(); A.ur1 = kf1->hasUright ? kf1->uright.as<float>() : nullptr; A.free1 = B + oF1; A.n1 = n1;
@@ -765,10 +752,8 @@ extern "C" int sslam_orb_search_for_triangulation(sslam_ctx* ctx, const sslam_fr
     { sslam::ProfScope _ps(ctx, "k_tri_search", st); hipLaunchKernelGGL(k_tri_search, dim3(std::min(total1, 8192)), dim3(64), 0, st, A); }
     { sslam::ProfScope _ps(ctx, "k_tri_finish", st); hipLaunchKernelGGL(k_rot_finish, dim3(1), dim3(256), 0, st, A.m12, A.qbin, n1, check_orientation, A.nmatches); }
     SSLAM_HIP(hipGetLastError());
-    SSLAM_HIP(hipMemcpyAsync(matches12_out, B + oM, 4 * (size_t)n1, hipMemcpyDeviceToHost, st));
-    SSLAM_HIP(hipMemcpyAsync(nmatches_out, B + oN, sizeof(int), hipMemcpyDeviceToHost, st));
-    SSLAM_HIP(hipStreamSynchronize(st));
-    return SSLAM_OK;
+    if ((rc = S.out(matches12_out, oM, 4 * (size_t)n1)) || (rc = S.out(nmatches_out, oN, sizeof(int)))) return rc;
+    return S.done();
 }
 
 // ---- SearchForTriangulation for pairs of keyframe slots that are already on the device, from per-feature node ids (sslam_bow_transform_batch_dev), asynchronous
@@ -845,11 +830,9 @@ static int bow_core(sslam_ctx* ctx, const sslam_vocab* v, const uint8_t* d_desc,
       hipLaunchKernelGGL(k_bow_transform, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, n, (const int*)nullptr, n, v->childPtr.as<int>(), v->children.as<int>(), v->desc.as<uint8_t>(),
                          v->wordId.as<int>(), v->weight.as<double>(), v->levels - levelsup, (int*)(B + oW), (double*)(B + oV), (int*)(B + oN)); }
     SSLAM_HIP(hipGetLastError());
-    SSLAM_HIP(hipMemcpyAsync(word_out, B + oW, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-    SSLAM_HIP(hipMemcpyAsync(weight_out, B + oV, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
-    SSLAM_HIP(hipMemcpyAsync(node_out, B + oN, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-    SSLAM_HIP(hipStreamSynchronize(st));
-    return SSLAM_OK;
+    const Staging S{B, st};
+    if ((rc = S.out(word_out, oW, 4 * (size_t)n)) || (rc = S.out(weight_out, oV, 8 * (size_t)n)) || (rc = S.out(node_out, oN, 4 * (size_t)n))) return rc;
+    return S.done();
 }
 
 extern "C" int sslam_bow_transform_frame(sslam_ctx* ctx, const sslam_vocab* vocab, const sslam_frame* frame, int levelsup,
@@ -873,7 +856,7 @@ extern "C" int sslam_bow_transform(sslam_ctx* ctx, const sslam_vocab* vocab, con
     SSLAM_HIP(hipSetDevice(ctx->device));
     int rc;
     if ((rc = ctx->scratch[SCR_UPLOAD].ensure(32 * (size_t)n))) return rc;
-    SSLAM_HIP(hipMemcpyAsync(ctx->scratch[SCR_UPLOAD].p, desc, 32 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = Staging{ctx->scratch[SCR_UPLOAD].as<uint8_t>(), ctx->stream}.in(0, desc, 32 * (size_t)n))) return rc;
     return bow_core(ctx, vocab, ctx->scratch[SCR_UPLOAD].as<uint8_t>(), n, levelsup, word_out, weight_out, node_out);
 }
 

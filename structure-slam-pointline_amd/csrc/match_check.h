@@ -1,5 +1,5 @@
-// The argument checks that matcher entry points share (match.hip): the CSR lists of vocabulary nodes, observation sets and children, and the
-// alignment and size rules of device-resident batches.  Host code and no HIP in here: tests/sim/host_checks.cpp compiles it with a plain host compiler under the sanitizers and supplies its own set_error.
+// The argument checks that matcher entry points share (match.hip, two_view.hip, sim3.hip): the CSR lists of vocabulary nodes, observation sets and children, the
+// alignment and size rules of device-resident batches, and the parameter rules of the RANSAC entry points.  Host code and no HIP in here: tests/sim/host_checks.cpp compiles it with a plain host compiler under the sanitizers and supplies its own set_error.
 #pragma once
 #include <cstdint>
 #include "../../include/sslam_frontend.h"
@@ -33,5 +33,8 @@ inline bool fits_31_bits(int slots, int cap) { return (long long)slots * (long l
 inline bool sim3_params_ok(const float* level_sigma2, int nlevels, double probability, int min_inliers, int max_iterations, int new_iterations) {
     return level_sigma2 && nlevels >= 1 && nlevels <= 64 && probability > 0.0 && probability < 1.0 && min_inliers >= 1 && max_iterations >= 1 && new_iterations >= 1;
 }
+// Injected sets of a RANSAC batch (d_sets: iterations sets per pair): their rows are indexed pair * iterations + it, which stays below 2^28 so that the index times the
+// words of a set fits 31 bits.  Without sets the rule asks nothing.
+inline bool injected_sets_ok(const void* d_sets, int npairs, int iterations) { return !d_sets || (long long)npairs * (long long)iterations < (1ll << 28); }
 
 }  // namespace sslam

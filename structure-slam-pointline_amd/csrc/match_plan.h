@@ -1,4 +1,4 @@
-// Host-side plans of the matcher entry points (match.hip): which kernel a call launches for its sizes, the sizes that follow from
+// Host-side plans of the matcher entry points (match.hip) and of the RANSAC units (two_view.hip, sim3.hip): which kernel a call launches for its sizes, the sizes that follow from
 // that choice (LDS bytes, capacities, grid), and how a staged call lays out its scratch arena.  Pure functions of integers and no HIP
 // in here: tests/sim/match_plan_dump.cpp compiles this header with a plain host compiler and tests/test_match_plan_cpu.py and the
 // tests/test_*_batch_plan_cpu.py check both sides of every boundary.  A size rule lives here and nowhere else; the kernels are chosen by arguments alone (no environment).
@@ -259,6 +259,32 @@ inline DistinctBatchPlan distinct_batch_plan(int nsets) {
     P.largeGrid = (unsigned)std::min<long long>(((long long)nsets + DISTINCT_LARGE_CHUNK - 1) / DISTINCT_LARGE_CHUNK, DISTINCT_LARGE_GRID_MAX);
     return P;
 }
+
+// -------------------------------------------------------------- RANSAC over the rows of a pair (sslam_two_view_ransac*, two_view.hip; sslam_sim3_ransac*, sim3.hip)
+// One wave per pair with the pair's compacted rows in dynamic LDS, rowBytes each, and fixedBytes behind them that do not grow with the capacity.  The capacity bound, beyond
+// which an entry point refuses before it launches, is whole steps of RANSAC_CAP_STEP rows: what one workgroup can have of the compute unit's LDS beside RANSAC_STATIC_LDS of
+// the kernel's static words, and no more than rowsMax bytes of rows.
+//   two-view  a row is (u1, v1, u2, v2); behind the rows the Jacobi workspace of the 64 lanes, TWO_VIEW_WS_DOUBLES doubles each (two_view_math.h: the upper triangle of a
+//             symmetric 9 x 9 and its eigenvectors); the rows stay within the 64 KB of the batch matchers' rows (BATCH_LDS_MAX): the workspace stays the larger part
+//   Sim3      a row is X1, X2, P1im1, P2im2, maxErr1, maxErr2 (sim3_math.h: s3::Row); nothing behind the rows, and they may take the whole LDS
+constexpr size_t LDS_PER_CU = 160 * 1024, RANSAC_STATIC_LDS = 256;
+constexpr int RANSAC_CAP_STEP = 1024, RANSAC_LANES = 64, TWO_VIEW_ROW_BYTES = 16, TWO_VIEW_WS_DOUBLES = 45 + 81, SIM3_ROW_BYTES = 48;
+constexpr size_t TWO_VIEW_WS_BYTES = sizeof(double) * TWO_VIEW_WS_DOUBLES * RANSAC_LANES;
+constexpr int ransac_max_cap(size_t rowBytes, size_t fixedBytes, size_t rowsMax) {
+    return (int)(std::min(LDS_PER_CU - RANSAC_STATIC_LDS - fixedBytes, rowsMax) / rowBytes / RANSAC_CAP_STEP) * RANSAC_CAP_STEP;
+}
+constexpr int TWO_VIEW_MAX_CAP = ransac_max_cap(TWO_VIEW_ROW_BYTES, TWO_VIEW_WS_BYTES, BATCH_LDS_MAX), SIM3_MAX_CAP = ransac_max_cap(SIM3_ROW_BYTES, 0, LDS_PER_CU);
+static_assert(TWO_VIEW_MAX_CAP == 4096 && SIM3_MAX_CAP == 3072, "the capacities include/sslam_frontend.h promises");
+struct RansacPlan {
+    int rowBytes; size_t ldsBytes; int ldsOptIn;      // dynamic LDS per workgroup, the rows of the capacity and the fixed part, and whether it needs the per-kernel opt-in
+    unsigned threads; int maxCap;                     // one wave; the capacity bound (ldsBytes means nothing beyond it)
+};
+inline RansacPlan ransac_plan(int rowBytes, size_t fixedBytes, int maxCap, int cap) {
+    const size_t lds = (size_t)rowBytes * (size_t)cap + fixedBytes;
+    return {rowBytes, lds, lds > DYNAMIC_LDS_DEFAULT_MAX ? 1 : 0, RANSAC_LANES, maxCap};
+}
+inline RansacPlan two_view_plan(int cap) { return ransac_plan(TWO_VIEW_ROW_BYTES, TWO_VIEW_WS_BYTES, TWO_VIEW_MAX_CAP, cap); }
+inline RansacPlan sim3_plan(int cap) { return ransac_plan(SIM3_ROW_BYTES, 0, SIM3_MAX_CAP, cap); }
 
 // arena of search_proj_core.  occ | q | qdesc go up in ONE copy (occ .. assigned), assigned | count come back in one (assigned .. count + 4);
 // only that head (.. count + 256) has a pinned mirror.  projK = list length of k_proj_topk (PROJ_K).

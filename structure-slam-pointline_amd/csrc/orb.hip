@@ -1396,8 +1396,8 @@ static int orb_tail(sslam_orb* o, const Plan& P, int nframes, hipStream_t st, ss
         int NC, NCp2; size_t lds;
         octree_lds(P, NC, NCp2, lds);
         if (octreeLdsOut) *octreeLdsOut = lds;
-        // more dynamic LDS than the default 48 KB has to be allowed per kernel (build_plan has held the size against the device's limit)
-        if (lds > 48 * 1024) SSLAM_HIP(hipFuncSetAttribute((const void*)k_octree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int rc;
+        if ((rc = allow_dynamic_lds((const void*)k_octree, lds))) return rc;      // build_plan has held the size against the device's limit
         dim3 grd(P.nlevels, nframes);
         { sslam::ProfScope _ps(o->ctx, "k_octree", st); hipLaunchKernelGGL(k_octree, grd, dim3(64), lds, st, o->dCand.as<unsigned>(), o->dCellCount.as<int>(), o->dCells.as<CellInfo>(),
                            o->dBufA.as<unsigned>(), o->dBufB.as<unsigned>(), o->dSel.as<unsigned>(), o->dSelCount.as<int>(), P, NC, NCp2); }

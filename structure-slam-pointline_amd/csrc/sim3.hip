@@ -3,7 +3,7 @@
 // its entry points.
 //
 // k_sim3_ransac: one wave per pair of keyframe slots.
-//   1. the pair's correspondences (the constructor's filters, :62-103) are compacted into 48-byte rows in LDS, ascending keyframe-1 row (ballot + popcount prefix):
+//   1. the pair's correspondences (the constructor's filters, :62-103) are compacted into 48-byte rows in LDS, ascending keyframe-1 row (ballot + popcount prefix: for_rows, pair_rows.h):
 //      X1, X2, P1im1, P2im2 (FromCameraToImage), maxErr1, maxErr2
 //   2. a round is 64 iterations, its_done + lane: every lane draws or reads its set, solves it (the 4 x 4 Jacobi is unrolled over static (p, q): registers, no scratch) and
 //      walks all rows in order (all lanes read the same row: a broadcast), keeping its count and its s, R, t in registers
@@ -13,6 +13,7 @@
 // Every output word has one writer; no atomics.
 #include "common.h"
 #include "match_check.h"
+#include "pair_rows.h"
 #include "sim3_math.h"
 #include <algorithm>
 
@@ -20,12 +21,10 @@ using namespace sslam;
 
 namespace {
 
-constexpr int S3_LANES = 64;
-constexpr int S3_ROW_BYTES = 48;
-constexpr int S3_MAX_CAP = 3072;      // 144 KB of rows: what one workgroup can have of the compute unit's 160 KB beside the kernel's static words
+constexpr int S3_LANES = RANSAC_LANES;
 constexpr int S3_MAX_LEVELS = 64;
 constexpr int S3_TAP_FLOATS = 13;     // s12, R12, t12
-static_assert(sizeof(s3::Row) == S3_ROW_BYTES, "a correspondence is three 16-byte words");
+static_assert(sizeof(s3::Row) == SIM3_ROW_BYTES, "a correspondence is three 16-byte words: sim3_plan (match_plan.h) sizes this kernel's LDS");
 static_assert(sizeof(sslam_sim3_state) == 84, "sslam_sim3_state has no padding");
 
 struct Sim3Args {
@@ -50,7 +49,7 @@ struct LdsRows {
 struct Pair {
     const sslam_keypoint* kp1; const sslam_keypoint* kp2; const uint8_t* v1; const uint8_t* v2; const int32_t* m12;
     int n1, n2, nlevels;
-    __device__ __forceinline__ int match(int i) const {
+    __device__ __forceinline__ int operator()(int i) const {
         if (i >= n1) return -1;
         const int m = m12[i];
         if (m < 0 || m >= n2) return -1;
@@ -88,23 +87,17 @@ __global__ __launch_bounds__(S3_LANES) void k_sim3_ransac(Sim3Args A) {
     float4* rows = (float4*)lds;
 
     // 1. mvX3Dc1 / 2, mvP1im1 / mvP2im2, mvnMaxError1 / 2 in mvnIndices1's order
-    int N = 0;
-    for (int i0 = 0; i0 < P.n1; i0 += S3_LANES) {
-        const int i = i0 + lane;
-        const int m = P.match(i);
-        const unsigned long long mask = __ballot(m >= 0);
-        if (m >= 0) {
-            const float x1[3] = {X1[3 * (size_t)i], X1[3 * (size_t)i + 1], X1[3 * (size_t)i + 2]}, x2[3] = {X2[3 * (size_t)m], X2[3 * (size_t)m + 1], X2[3 * (size_t)m + 2]};
-            float p1[2], p2[2];
-            s3::camera_to_image(x1, K1, p1);
-            s3::camera_to_image(x2, K2, p2);
-            float4* r = rows + 3 * (N + mbcnt(mask));
-            r[0] = make_float4(x1[0], x1[1], x1[2], x2[0]);
-            r[1] = make_float4(x2[1], x2[2], p1[0], p1[1]);
-            r[2] = make_float4(p2[0], p2[1], A.maxErr[P.kp1[i].octave], A.maxErr[P.kp2[m].octave]);
-        }
-        N += __popcll(mask);
-    }
+    const int N = for_rows(P.n1, lane, P, [&](int i, int m, int slot) {
+        if (slot < 0) return;
+        const float x1[3] = {X1[3 * (size_t)i], X1[3 * (size_t)i + 1], X1[3 * (size_t)i + 2]}, x2[3] = {X2[3 * (size_t)m], X2[3 * (size_t)m + 1], X2[3 * (size_t)m + 2]};
+        float p1[2], p2[2];
+        s3::camera_to_image(x1, K1, p1);
+        s3::camera_to_image(x2, K2, p2);
+        float4* r = rows + 3 * slot;
+        r[0] = make_float4(x1[0], x1[1], x1[2], x2[0]);
+        r[1] = make_float4(x2[1], x2[2], p1[0], p1[1]);
+        r[2] = make_float4(p2[0], p2[1], A.maxErr[P.kp1[i].octave], A.maxErr[P.kp2[m].octave]);
+    });
     __syncthreads();
 
     // the solver object (:37-38, :137): a zero-filled state is a new one
@@ -134,7 +127,7 @@ __global__ __launch_bounds__(S3_LANES) void k_sim3_ransac(Sim3Args A) {
 #pragma unroll
                     for (int j = 0; j < 3; ++j) { set[j] = s[j]; valid = valid && set[j] >= 0 && set[j] < N; }
                 } else if (N >= 3) {
-                    s3::draw_set(A.seed, (uint32_t)(A.pair0 + p), (uint32_t)it, N, set);
+                    draw_set<3>(A.seed, (uint32_t)(A.pair0 + p), (uint32_t)it, N, set);
                 } else {
                     valid = false;
                 }
@@ -198,32 +191,11 @@ __global__ __launch_bounds__(S3_LANES) void k_sim3_ransac(Sim3Args A) {
     s3::Transforms T;
     s3::transforms(best, T);
     const LdsRows R{rows};
-    int seen = 0;
-    for (int i0 = 0; i0 < P.n1; i0 += S3_LANES) {
-        const int i = i0 + lane;
-        const int m = P.match(i);
-        const unsigned long long mask = __ballot(m >= 0);
+    for_rows(P.n1, lane, P, [&](int i, int, int slot) {
         uint8_t b = 0;
-        if (m >= 0 && found >= 0) b = s3::check_row(T, K1, K2, R(seen + mbcnt(mask))) ? 1 : 0;
+        if (slot >= 0 && found >= 0) b = s3::check_row(T, K1, K2, R(slot)) ? 1 : 0;
         if (i < P.n1) A.inl[bp + i] = b;
-        seen += __popcll(mask);
-    }
-}
-
-// the product library holds k_sim3_ransac<false> alone; the instantiation with the tap's stores exists in the testing library
-int sim3_launch(sslam_ctx* ctx, const Sim3Args& A, int npairs, bool tap, hipStream_t st) {
-    const size_t ldsBytes = (size_t)S3_ROW_BYTES * A.cap;
-#ifdef SSLAM_TESTING
-    void (*const k)(Sim3Args) = tap ? k_sim3_ransac<true> : k_sim3_ransac<false>;
-#else
-    void (*const k)(Sim3Args) = k_sim3_ransac<false>;
-    if (tap) { set_error("k_sim3_ransac: no tap in this library"); return SSLAM_ERR_UNSUPPORTED; }
-#endif
-    if (ldsBytes > DYNAMIC_LDS_DEFAULT_MAX) SSLAM_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-    sslam::ProfScope _ps(ctx, "k_sim3_ransac", st);
-    hipLaunchKernelGGL(k, dim3(npairs), dim3(S3_LANES), ldsBytes, st, A);
-    SSLAM_HIP(hipGetLastError());
-    return SSLAM_OK;
+    });
 }
 
 // mRansacMaxIts for every N in [min_inliers, cap] (SetRansacParameters, :114-138, on the host with libm), cap + 1 int32 on the device.  Rebuilt only when its key changes; a
@@ -249,7 +221,8 @@ int sim3_enqueue(sslam_ctx* ctx, Sim3Args& A, const float* level_sigma2, double 
     int rc;
     if ((rc = sim3_table(ctx, probability, A.minInliers, A.maxIterations, A.cap, st))) return rc;
     A.table = ctx->sim3Table.dev.as<int32_t>();
-    if ((rc = sim3_launch(ctx, A, npairs, tap, st))) return rc;
+    const RansacPlan P = sim3_plan(A.cap);
+    if ((rc = launch_tapped(ctx, "k_sim3_ransac", SSLAM_WITH_TAP(k_sim3_ransac), tap, (unsigned)npairs, P.threads, P.ldsBytes, st, A))) return rc;
     return ctx->sim3Table.dev.mark(st);
 }
 
@@ -264,57 +237,40 @@ int sim3_host_pair(sslam_ctx* ctx, const char* fn, const sslam_keypoint* kp1, co
         set_error("%s: invalid arguments", fn); return SSLAM_ERR_INVALID;
     }
     const int cap = std::max(std::max(n1, n2), 1);
-    if (cap > S3_MAX_CAP) { set_error("%s: %d rows exceed the supported %d", fn, cap, S3_MAX_CAP); return SSLAM_ERR_UNSUPPORTED; }
+    if (cap > SIM3_MAX_CAP) { set_error("%s: %d rows exceed the supported %d", fn, cap, SIM3_MAX_CAP); return SSLAM_ERR_UNSUPPORTED; }
     const bool tap = sets_out != nullptr;
     const bool hasValid = valid1 || valid2;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t its = (size_t)max_iterations;
+    const size_t its = (size_t)max_iterations, setsBytes = 12 * its, matsBytes = 4 * S3_TAP_FLOATS * its, countsBytes = 4 * its;
     // a pool of two slots: slot 1 starts cap rows behind slot 0 in every array
-    const size_t kb = up(sizeof(sslam_keypoint) * 2 * (size_t)cap), xb = up(24 * (size_t)cap), vb = up(2 * (size_t)cap), mb = up(4 * (size_t)cap), sb = up(sets ? 12 * its : 0);
-    const size_t oX = kb, oV = oX + xb, oHead = oV + vb, oM = oHead + 256, oS = oM + mb, oState = oS + sb, oI = oState + 256, oTS = oI + up((size_t)cap);
-    const size_t oTM = oTS + up(tap ? 12 * its : 0), oTC = oTM + up(tap ? 4 * S3_TAP_FLOATS * its : 0), total = oTC + up(tap ? 4 * its : 0);
+    const size_t ks = sizeof(sslam_keypoint);
+    ArenaLayout L;
+    const size_t oK = L.take(ks * 2 * (size_t)cap), oX = L.take(24 * (size_t)cap), oV = L.take(2 * (size_t)cap), oHead = L.take(256), oM = L.take(4 * (size_t)cap),
+                 oS = L.take(sets ? setsBytes : 0), oState = L.take(256), oI = L.take((size_t)cap),
+                 oTS = L.take(tap ? setsBytes : 0), oTM = L.take(tap ? matsBytes : 0), oTC = L.take(tap ? countsBytes : 0);
     int rc;
-    if ((rc = ctx->scratch[SCR_CALL].ensure(total))) return rc;
+    if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
     uint8_t* d = ctx->scratch[SCR_CALL].as<uint8_t>();
+    const Staging S{d, ctx->stream};
     struct { int32_t n[2]; int32_t pairs[2]; float K[8]; } head;      // counts, the pair (0, 1), fx fy cx cy of both slots
     head.n[0] = n1; head.n[1] = n2; head.pairs[0] = 0; head.pairs[1] = 1;
     memcpy(head.K, K1, 16); memcpy(head.K + 4, K2, 16);
-    if (n1) {
-        SSLAM_HIP(hipMemcpyAsync(d, kp1, sizeof(sslam_keypoint) * (size_t)n1, hipMemcpyHostToDevice, st));
-        SSLAM_HIP(hipMemcpyAsync(d + oX, x3dc1, 12 * (size_t)n1, hipMemcpyHostToDevice, st));
-        if (valid1) SSLAM_HIP(hipMemcpyAsync(d + oV, valid1, (size_t)n1, hipMemcpyHostToDevice, st));
-        SSLAM_HIP(hipMemcpyAsync(d + oM, matches12, 4 * (size_t)n1, hipMemcpyHostToDevice, st));
-    }
-    if (n2) {
-        SSLAM_HIP(hipMemcpyAsync(d + sizeof(sslam_keypoint) * (size_t)cap, kp2, sizeof(sslam_keypoint) * (size_t)n2, hipMemcpyHostToDevice, st));
-        SSLAM_HIP(hipMemcpyAsync(d + oX + 12 * (size_t)cap, x3dc2, 12 * (size_t)n2, hipMemcpyHostToDevice, st));
-        if (valid2) SSLAM_HIP(hipMemcpyAsync(d + oV + (size_t)cap, valid2, (size_t)n2, hipMemcpyHostToDevice, st));
-    }
-    SSLAM_HIP(hipMemcpyAsync(d + oHead, &head, sizeof(head), hipMemcpyHostToDevice, st));
-    if (sets) SSLAM_HIP(hipMemcpyAsync(d + oS, sets, 12 * its, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(d + oState, state, sizeof(sslam_sim3_state), hipMemcpyHostToDevice, st));
-    if (tap) SSLAM_HIP(hipMemsetAsync(d + oTS, 0, total - oTS, st));      // rows of iterations the loop did not run stay zero
+    if ((rc = S.in(oK, kp1, ks * (size_t)n1)) || (rc = S.in(oX, x3dc1, 12 * (size_t)n1)) || (rc = S.in(oV, valid1, (size_t)n1)) || (rc = S.in(oM, matches12, 4 * (size_t)n1)) ||
+        (rc = S.in(oK + ks * (size_t)cap, kp2, ks * (size_t)n2)) || (rc = S.in(oX + 12 * (size_t)cap, x3dc2, 12 * (size_t)n2)) || (rc = S.in(oV + (size_t)cap, valid2, (size_t)n2)) ||
+        (rc = S.in(oHead, &head, sizeof(head))) || (rc = S.in(oS, sets, setsBytes)) || (rc = S.in(oState, state, sizeof(sslam_sim3_state)))) return rc;
+    if (tap) SSLAM_HIP(hipMemsetAsync(d + oTS, 0, L.size() - oTS, S.st));      // rows of iterations the loop did not run stay zero
     Sim3Args A;
-    A.kp = (const sslam_keypoint*)d; A.x3dc = (const float*)(d + oX); A.valid = hasValid ? d + oV : nullptr; A.n = (const int32_t*)(d + oHead);
+    A.kp = (const sslam_keypoint*)(d + oK); A.x3dc = (const float*)(d + oX); A.valid = hasValid ? d + oV : nullptr; A.n = (const int32_t*)(d + oHead);
     A.K = (const float*)(d + oHead + 16); A.pairs = (const int32_t*)(d + oHead + 8); A.m12 = (const int32_t*)(d + oM); A.table = nullptr;
     A.sets = sets ? (const int32_t*)(d + oS) : nullptr;
     A.cap = cap; A.nkeyframes = 2; A.nlevels = nlevels; A.fixScale = fix_scale; A.minInliers = min_inliers; A.maxIterations = max_iterations; A.newIterations = new_iterations;
     A.pair0 = pair; A.seed = seed;
     A.state = (sslam_sim3_state*)(d + oState); A.inl = d + oI;
     A.tapSets = tap ? (int32_t*)(d + oTS) : nullptr; A.tapMats = tap ? (float*)(d + oTM) : nullptr; A.tapCounts = tap ? (int32_t*)(d + oTC) : nullptr;
-    if ((rc = sim3_enqueue(ctx, A, level_sigma2, probability, 1, tap, st))) return rc;
-    SSLAM_HIP(hipMemcpyAsync(state, d + oState, sizeof(sslam_sim3_state), hipMemcpyDeviceToHost, st));
-    if (n1) SSLAM_HIP(hipMemcpyAsync(inliers, d + oI, (size_t)n1, hipMemcpyDeviceToHost, st));
-    if (tap) {
-        SSLAM_HIP(hipMemcpyAsync(sets_out, d + oTS, 12 * its, hipMemcpyDeviceToHost, st));
-        SSLAM_HIP(hipMemcpyAsync(mats_out, d + oTM, 4 * S3_TAP_FLOATS * its, hipMemcpyDeviceToHost, st));
-        SSLAM_HIP(hipMemcpyAsync(counts_out, d + oTC, 4 * its, hipMemcpyDeviceToHost, st));
-    }
-    SSLAM_HIP(hipStreamSynchronize(st));
-    return SSLAM_OK;
+    if ((rc = sim3_enqueue(ctx, A, level_sigma2, probability, 1, tap, S.st)) || (rc = S.out(state, oState, sizeof(sslam_sim3_state))) || (rc = S.out(inliers, oI, (size_t)n1))) return rc;
+    if (tap && ((rc = S.out(sets_out, oTS, setsBytes)) || (rc = S.out(mats_out, oTM, matsBytes)) || (rc = S.out(counts_out, oTC, countsBytes)))) return rc;
+    return S.done();
 }
 
 }  // namespace
@@ -326,10 +282,10 @@ extern "C" int sslam_sim3_ransac_batch_dev(sslam_ctx* ctx, const sslam_keypoint*
     if (!ctx || !d_kp || !d_x3dc || !d_n || !d_K || !d_pairs || !d_matches12 || !d_state || !d_inliers || cap < 1 || nkeyframes < 0 || npairs < 0 ||
         !sim3_params_ok(level_sigma2, nlevels, probability, min_inliers, max_iterations, new_iterations) ||
         !all_aligned<4>(d_kp) || !all_aligned<4>(d_x3dc, d_K) || !all_aligned<4>(d_n, d_pairs, d_matches12, d_sets) || !all_aligned<4>(d_state) ||
-        !fits_31_bits(npairs, cap) || !fits_31_bits(nkeyframes, cap) || (d_sets && (long long)npairs * max_iterations >= (1ll << 28))) {
+        !fits_31_bits(npairs, cap) || !fits_31_bits(nkeyframes, cap) || !injected_sets_ok(d_sets, npairs, max_iterations)) {
         set_error("sslam_sim3_ransac_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
-    if (cap > S3_MAX_CAP) { set_error("sslam_sim3_ransac_batch_dev: cap=%d exceeds the supported %d (48 bytes of LDS per row)", cap, S3_MAX_CAP); return SSLAM_ERR_UNSUPPORTED; }
+    if (cap > SIM3_MAX_CAP) { set_error("sslam_sim3_ransac_batch_dev: cap=%d exceeds the supported %d (48 bytes of LDS per row)", cap, SIM3_MAX_CAP); return SSLAM_ERR_UNSUPPORTED; }
     if (npairs == 0) return SSLAM_OK;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
@@ -337,7 +293,7 @@ extern "C" int sslam_sim3_ransac_batch_dev(sslam_ctx* ctx, const sslam_keypoint*
     A.kp = d_kp; A.x3dc = d_x3dc; A.valid = d_valid; A.n = d_n; A.K = d_K; A.pairs = d_pairs; A.m12 = d_matches12; A.table = nullptr; A.sets = d_sets;
     A.cap = cap; A.nkeyframes = nkeyframes; A.nlevels = nlevels; A.fixScale = fix_scale; A.minInliers = min_inliers; A.maxIterations = max_iterations; A.newIterations = new_iterations;
     A.pair0 = 0; A.seed = seed; A.state = d_state; A.inl = d_inliers; A.tapSets = nullptr; A.tapMats = nullptr; A.tapCounts = nullptr;
-    return sim3_enqueue(ctx, A, level_sigma2, probability, npairs, false, stream ? (hipStream_t)stream : ctx->stream);
+    return sim3_enqueue(ctx, A, level_sigma2, probability, npairs, false, pick(ctx, stream));
 }
 
 extern "C" int sslam_sim3_ransac(sslam_ctx* ctx, const sslam_keypoint* kp1, const float* x3dc1, const uint8_t* valid1, int n1, const float K1[4],

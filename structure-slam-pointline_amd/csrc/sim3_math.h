@@ -19,8 +19,8 @@
 //            v == 0 exactly is 0 / 0 at :280: R12 is all NaN and the hypothesis has no inlier.
 //   table    SetRansacParameters' log / pow / ceil are libm's, evaluated on the host (ransac_max_its below is host code) for every N the kernel can meet.
 //
-// The draw: DUtils::Random::RandomInt is rand(); here randi = hash32(seed, pair, it, j) % remaining (two_view_math.h states hash32) for j = 0, 1, 2, and the swap-with-back
-// of :170-176 is replayed without the copy of all indices.  Fewer than three correspondences cannot be drawn from (the reference would ask RandomInt(0, -1)): such an
+// The draw: DUtils::Random::RandomInt is rand(); here randi = hash32(seed, pair, it, j) % remaining (draw_set<3> of ransac_draw.h, which states hash32 and the replay of the
+// swap-with-back of :170-176).  Fewer than three correspondences cannot be drawn from (the reference would ask RandomInt(0, -1)): such an
 // iteration counts like an injected set with an index out of range -- it is walked, never becomes the best and never returns.
 //
 // A consequence of iterate's control flow: `mnInliersi >= mnBestInliers` (:183) sits in front of `mnInliersi > mRansacMinInliers` (:192).  So a call returns at the FIRST
@@ -30,7 +30,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
-#include "two_view_math.h"
+#include "ransac_draw.h"
 
 #if defined(__HIPCC__)
 #define S3_FN __host__ __device__ __forceinline__
@@ -41,7 +41,7 @@
 namespace sslam {
 namespace s3 {
 
-constexpr int JACOBI_SWEEPS = tv::JACOBI_SWEEPS;
+using sslam::draw_set;      // :168-176 for one iteration over n >= 3 correspondences: set is an int[3]
 
 struct Cam { float fx, fy, cx, cy; };
 // one correspondence: mvX3Dc1 / mvX3Dc2, mvP1im1 / mvP2im2, mvnMaxError1 / 2 as the floats the comparison of :356 converts them to.  48 bytes
@@ -69,20 +69,6 @@ S3_FN void project(const float A[9], const float t[3], const float X[3], const C
     float c[3];
     for (int i = 0; i < 3; ++i) c[i] = ((A[i * 3] * X[0] + A[i * 3 + 1] * X[1]) + A[i * 3 + 2] * X[2]) + t[i];
     camera_to_image(c, K, p);
-}
-
-// :168-176 for one iteration over n >= 3 correspondences (tv::draw_set for three)
-S3_FN void draw_set(uint32_t seed, uint32_t pair, uint32_t it, int n, int set[3]) {
-    const int r0 = (int)(tv::hash32(seed, pair, it, 0u) % (uint32_t)n);
-    const int r1 = (int)(tv::hash32(seed, pair, it, 1u) % (uint32_t)(n - 1));
-    const int r2 = (int)(tv::hash32(seed, pair, it, 2u) % (uint32_t)(n - 2));
-    // step 0 writes n - 1 to position r0; step 1 reads r1 and writes what sits at n - 2 to it; step 2 reads r2
-    const int at1 = r1 == r0 ? n - 1 : r1;
-    const int back1 = (n - 2) == r0 ? n - 1 : n - 2;
-    int at2 = r2;
-    if (r2 == r0) at2 = n - 1;
-    if (r2 == r1) at2 = back1;
-    set[0] = r0; set[1] = at1; set[2] = at2;
 }
 
 // one (p, q) rotation of the cyclic Jacobi on the upper triangle a (a[i][j], i <= j) and the eigenvector columns v; every index is a compile-time constant
@@ -124,7 +110,7 @@ S3_FN void jacobi_largest(const float n[10], double q[4]) {
     v[1][0] = 0.0; v[1][1] = 1.0; v[1][2] = 0.0; v[1][3] = 0.0;
     v[2][0] = 0.0; v[2][1] = 0.0; v[2][2] = 1.0; v[2][3] = 0.0;
     v[3][0] = 0.0; v[3][1] = 0.0; v[3][2] = 0.0; v[3][3] = 1.0;
-    TV_NOUNROLL
+    RANSAC_NOUNROLL
     for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
         rotate<0, 1>(a, v); rotate<0, 2>(a, v); rotate<0, 3>(a, v); rotate<1, 2>(a, v); rotate<1, 3>(a, v); rotate<2, 3>(a, v);
     }

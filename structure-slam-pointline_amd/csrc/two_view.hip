@@ -4,7 +4,7 @@
 //
 // k_two_view: one wave per frame pair.
 //   1. the pair's keypoint coordinates go to LDS; lanes 0 .. 3 run the four sequential Normalize chains (x and y of both frames) on them
-//   2. matches12 is compacted into (u1, v1, u2, v2) rows in LDS, ascending keypoint-1 index (ballot + popcount prefix), over the staged coordinates
+//   2. matches12 is compacted into (u1, v1, u2, v2) rows in LDS, ascending keypoint-1 index (ballot + popcount prefix: for_rows, pair_rows.h), over the staged coordinates
 //   3. lane l takes iterations l, l + 64, ...: draws or reads the set, solves H then F (the Jacobi matrices of the lane sit in LDS, lane-interleaved: double k of lane l is
 //      word k * 64 + l, so run-time indices make no private array and the 32 lanes of a half wave hit 64 distinct banks with their 8-byte accesses), composes, and walks the
 //      rows in order (all lanes read the same row: a broadcast), keeping the best (score, iteration, matrix) of its own iterations
@@ -12,6 +12,7 @@
 // Every output word has one writer; no atomics.
 #include "common.h"
 #include "match_check.h"
+#include "pair_rows.h"
 #include "two_view_math.h"
 #include <algorithm>
 
@@ -19,9 +20,9 @@ using namespace sslam;
 
 namespace {
 
-constexpr int TV_LANES = 64;
-constexpr int TV_MAX_CAP = 4096;
+constexpr int TV_LANES = RANSAC_LANES;
 constexpr int TV_TAP_MATS = 45;      // Hn, H21i, H12i, Fn, F21i
+static_assert(tv::WS_DOUBLES == TWO_VIEW_WS_DOUBLES && sizeof(float4) == TWO_VIEW_ROW_BYTES, "two_view_plan (match_plan.h) sizes this kernel's LDS");
 
 struct TwoViewArgs {
     const sslam_keypoint* kp1; const int32_t* n1;
@@ -40,6 +41,11 @@ struct LdsWs {      // tv::WS_DOUBLES doubles of this lane, lane-interleaved
 struct LdsRows {
     const float4* r;
     __device__ __forceinline__ tv::Row operator()(int i) const { const float4 v = r[i]; return tv::Row{v.x, v.y, v.z, v.w}; }
+};
+// mvMatches12 (:67-76) for keypoint-1 row i: a row is matched when 0 <= matches12 < n2; the keypoint-2 row, or -1
+struct Matches12 {
+    const int32_t* m12; int n1, n2;
+    __device__ __forceinline__ int operator()(int i) const { const int m = i < n1 ? m12[i] : -1; return m >= 0 && m < n2 ? m : -1; }
 };
 
 // (score, iteration) order of the selection: a strictly greater score wins, equal scores go to the lower iteration (the first in the reference's loop); it < 0: no candidate
@@ -80,16 +86,11 @@ __global__ __launch_bounds__(TV_LANES) void k_two_view(TwoViewArgs A) {
     __syncthreads();
     const tv::Norm N1{sNorm[0], sNorm[1], sNorm[2], sNorm[3]}, N2{sNorm[4], sNorm[5], sNorm[6], sNorm[7]};
 
-    // 2. mvMatches12 (:67-76): a row is matched when 0 <= matches12 < n2
-    int nm = 0;
-    for (int i0 = 0; i0 < n1; i0 += TV_LANES) {
-        const int i = i0 + lane;
-        const int m = i < n1 ? A.m12[base + i] : -1;
-        const bool ok = m >= 0 && m < n2;
-        const unsigned long long mask = __ballot(ok);
-        if (ok) rows[nm + mbcnt(mask)] = make_float4(kp1[i].x, kp1[i].y, kp2[m].x, kp2[m].y);
-        nm += __popcll(mask);
-    }
+    // 2. mvMatches12 (:67-76)
+    const Matches12 M{A.m12 + base, n1, n2};
+    const int nm = for_rows(n1, lane, M, [&](int i, int m, int slot) {
+        if (slot >= 0) rows[slot] = make_float4(kp1[i].x, kp1[i].y, kp2[m].x, kp2[m].y);
+    });
     __syncthreads();
 
     float bestSH = 0.f, bestSF = 0.f;
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(TV_LANES) void k_two_view(TwoViewArgs A) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { set[j] = s[j]; valid = valid && set[j] >= 0 && set[j] < nm; }
             } else {
-                tv::draw_set(A.seed, (uint32_t)(A.pair0 + p), (uint32_t)it, nm, set);
+                draw_set<8>(A.seed, (uint32_t)(A.pair0 + p), (uint32_t)it, nm, set);
             }
             tv::Hypothesis h;
             tv::hypothesis(R, nm, N1, N2, set, valid, A.sigma, ws, h);
@@ -163,40 +164,21 @@ __global__ __launch_bounds__(TV_LANES) void k_two_view(TwoViewArgs A) {
 
     // vbMatchesInliersH / F of the winners, by keypoint 1; rows [n1, cap) are not written
     const float iss = tv::inv_sigma_square(A.sigma);
-    int seen = 0;
-    for (int i0 = 0; i0 < n1; i0 += TV_LANES) {
-        const int i = i0 + lane;
-        const int m = i < n1 ? A.m12[base + i] : -1;
-        const bool ok = m >= 0 && m < n2;
-        const unsigned long long mask = __ballot(ok);
+    for_rows(n1, lane, M, [&](int i, int, int slot) {
         int b = 0;
-        if (ok && nm >= 8) {
-            const float4 r = rows[seen + mbcnt(mask)];
+        if (slot >= 0 && nm >= 8) {
+            const float4 r = rows[slot];
             float s = 0.f;
             if (itH >= 0 && tv::check_homography_match(H21, H12, r.x, r.y, r.z, r.w, iss, s)) b |= 1;
             if (itF >= 0 && tv::check_fundamental_match(F21, r.x, r.y, r.z, r.w, iss, s)) b |= 2;
         }
         if (i < n1) A.inl[base + i] = (uint8_t)b;
-        seen += __popcll(mask);
-    }
+    });
 }
 
-size_t two_view_lds_bytes(int cap) { return 16 * (size_t)cap + sizeof(double) * tv::WS_DOUBLES * TV_LANES; }
-
-// the product library holds k_two_view<false> alone; the instantiation with the tap's stores exists in the testing library
 int two_view_launch(sslam_ctx* ctx, const TwoViewArgs& A, int npairs, bool tap, hipStream_t st) {
-    const size_t ldsBytes = two_view_lds_bytes(A.cap);
-#ifdef SSLAM_TESTING
-    void (*const k)(TwoViewArgs) = tap ? k_two_view<true> : k_two_view<false>;
-#else
-    void (*const k)(TwoViewArgs) = k_two_view<false>;
-    if (tap) { set_error("k_two_view: no tap in this library"); return SSLAM_ERR_UNSUPPORTED; }
-#endif
-    if (ldsBytes > DYNAMIC_LDS_DEFAULT_MAX) SSLAM_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-    sslam::ProfScope _ps(ctx, "k_two_view", st);
-    hipLaunchKernelGGL(k, dim3(npairs), dim3(TV_LANES), ldsBytes, st, A);
-    SSLAM_HIP(hipGetLastError());
-    return SSLAM_OK;
+    const RansacPlan P = two_view_plan(A.cap);
+    return launch_tapped(ctx, "k_two_view", SSLAM_WITH_TAP(k_two_view), tap, (unsigned)npairs, P.threads, P.ldsBytes, st, A);
 }
 
 // one host pair on the device and back: shared by the single call and the testing tap
@@ -207,41 +189,32 @@ int two_view_host_pair(sslam_ctx* ctx, const char* fn, const sslam_keypoint* kp1
         set_error("%s: invalid arguments", fn); return SSLAM_ERR_INVALID;
     }
     const int cap = std::max(std::max(n1, n2), 1);
-    if (cap > TV_MAX_CAP) { set_error("%s: %d keypoints exceed the supported %d", fn, cap, TV_MAX_CAP); return SSLAM_ERR_UNSUPPORTED; }
+    if (cap > TWO_VIEW_MAX_CAP) { set_error("%s: %d keypoints exceed the supported %d", fn, cap, TWO_VIEW_MAX_CAP); return SSLAM_ERR_UNSUPPORTED; }
     const bool tap = sets_out != nullptr;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t kb = up(sizeof(sslam_keypoint) * (size_t)cap), mb = up(4 * (size_t)cap), sb = up(sets ? 32 * (size_t)iterations : 0);
-    const size_t oK2 = kb, oN = 2 * kb, oM = oN + 256, oS = oM + mb, oR = oS + sb, oI = oR + 256, oTS = oI + up((size_t)cap);
-    const size_t oTM = oTS + up(tap ? 32 * (size_t)iterations : 0), oTC = oTM + up(tap ? 4 * TV_TAP_MATS * (size_t)iterations : 0), total = oTC + up(tap ? 8 * (size_t)iterations : 0);
+    const size_t its = (size_t)iterations, setsBytes = 32 * its, matsBytes = 4 * TV_TAP_MATS * its, scoresBytes = 8 * its;
+    ArenaLayout L;
+    const size_t oK1 = L.take(sizeof(sslam_keypoint) * (size_t)cap), oK2 = L.take(sizeof(sslam_keypoint) * (size_t)cap), oN = L.take(256), oM = L.take(4 * (size_t)cap),
+                 oS = L.take(sets ? setsBytes : 0), oR = L.take(256), oI = L.take((size_t)cap),
+                 oTS = L.take(tap ? setsBytes : 0), oTM = L.take(tap ? matsBytes : 0), oTC = L.take(tap ? scoresBytes : 0);
     int rc;
-    if ((rc = ctx->scratch[SCR_CALL].ensure(total))) return rc;
+    if ((rc = ctx->scratch[SCR_CALL].ensure(L.size()))) return rc;
     uint8_t* d = ctx->scratch[SCR_CALL].as<uint8_t>();
+    const Staging S{d, ctx->stream};
     const int hn[2] = {n1, n2};
-    if (n1) SSLAM_HIP(hipMemcpyAsync(d, kp1, sizeof(sslam_keypoint) * (size_t)n1, hipMemcpyHostToDevice, st));
-    if (n2) SSLAM_HIP(hipMemcpyAsync(d + oK2, kp2, sizeof(sslam_keypoint) * (size_t)n2, hipMemcpyHostToDevice, st));
-    SSLAM_HIP(hipMemcpyAsync(d + oN, hn, sizeof(hn), hipMemcpyHostToDevice, st));
-    if (n1) SSLAM_HIP(hipMemcpyAsync(d + oM, matches12, 4 * (size_t)n1, hipMemcpyHostToDevice, st));
-    if (sets) SSLAM_HIP(hipMemcpyAsync(d + oS, sets, 32 * (size_t)iterations, hipMemcpyHostToDevice, st));
-    if (tap) SSLAM_HIP(hipMemsetAsync(d + oTS, 0, total - oTS, st));      // a pair below 8 matches runs no iteration
+    if ((rc = S.in(oK1, kp1, sizeof(sslam_keypoint) * (size_t)n1)) || (rc = S.in(oK2, kp2, sizeof(sslam_keypoint) * (size_t)n2)) || (rc = S.in(oN, hn, sizeof(hn))) ||
+        (rc = S.in(oM, matches12, 4 * (size_t)n1)) || (rc = S.in(oS, sets, setsBytes))) return rc;
+    if (tap) SSLAM_HIP(hipMemsetAsync(d + oTS, 0, L.size() - oTS, S.st));      // a pair below 8 matches runs no iteration
     TwoViewArgs A;
-    A.kp1 = (const sslam_keypoint*)d; A.n1 = (const int32_t*)(d + oN); A.kp2 = (const sslam_keypoint*)(d + oK2); A.n2 = (const int32_t*)(d + oN) + 1;
+    A.kp1 = (const sslam_keypoint*)(d + oK1); A.n1 = (const int32_t*)(d + oN); A.kp2 = (const sslam_keypoint*)(d + oK2); A.n2 = (const int32_t*)(d + oN) + 1;
     A.m12 = (const int32_t*)(d + oM); A.sets = sets ? (const int32_t*)(d + oS) : nullptr;
     A.cap = cap; A.iterations = iterations; A.pair0 = pair; A.sigma = sigma; A.seed = seed;
     A.res = (sslam_two_view_result*)(d + oR); A.inl = d + oI;
     A.tapSets = tap ? (int32_t*)(d + oTS) : nullptr; A.tapMats = tap ? (float*)(d + oTM) : nullptr; A.tapScores = tap ? (float*)(d + oTC) : nullptr;
-    if ((rc = two_view_launch(ctx, A, 1, tap, st))) return rc;
-    SSLAM_HIP(hipMemcpyAsync(result, d + oR, sizeof(sslam_two_view_result), hipMemcpyDeviceToHost, st));
-    if (n1) SSLAM_HIP(hipMemcpyAsync(inliers, d + oI, (size_t)n1, hipMemcpyDeviceToHost, st));
-    if (tap) {
-        SSLAM_HIP(hipMemcpyAsync(sets_out, d + oTS, 32 * (size_t)iterations, hipMemcpyDeviceToHost, st));
-        SSLAM_HIP(hipMemcpyAsync(mats_out, d + oTM, 4 * TV_TAP_MATS * (size_t)iterations, hipMemcpyDeviceToHost, st));
-        SSLAM_HIP(hipMemcpyAsync(scores_out, d + oTC, 8 * (size_t)iterations, hipMemcpyDeviceToHost, st));
-    }
-    SSLAM_HIP(hipStreamSynchronize(st));
-    return SSLAM_OK;
+    if ((rc = two_view_launch(ctx, A, 1, tap, S.st)) || (rc = S.out(result, oR, sizeof(sslam_two_view_result))) || (rc = S.out(inliers, oI, (size_t)n1))) return rc;
+    if (tap && ((rc = S.out(sets_out, oTS, setsBytes)) || (rc = S.out(mats_out, oTM, matsBytes)) || (rc = S.out(scores_out, oTC, scoresBytes)))) return rc;
+    return S.done();
 }
 
 }  // namespace
@@ -251,17 +224,17 @@ extern "C" int sslam_two_view_ransac_batch_dev(sslam_ctx* ctx, const sslam_keypo
                                                sslam_two_view_result* d_result, uint8_t* d_inliers, void* stream) {
     if (!ctx || !d_kp1 || !d_n1 || !d_kp2 || !d_n2 || !d_matches12 || !d_result || !d_inliers || cap <= 0 || npairs <= 0 || iterations < 1 || !(sigma > 0.f) ||
         !all_aligned<4>(d_kp1, d_kp2) || !all_aligned<4>(d_n1, d_n2, d_matches12, d_sets) || !all_aligned<4>(d_result) || !fits_31_bits(npairs, cap) ||
-        (d_sets && (long long)npairs * iterations >= (1ll << 28))) {
+        !injected_sets_ok(d_sets, npairs, iterations)) {
         set_error("sslam_two_view_ransac_batch_dev: invalid arguments"); return SSLAM_ERR_INVALID;
     }
-    if (cap > TV_MAX_CAP) { set_error("sslam_two_view_ransac_batch_dev: cap=%d exceeds the supported %d (16 bytes of LDS per row)", cap, TV_MAX_CAP); return SSLAM_ERR_UNSUPPORTED; }
+    if (cap > TWO_VIEW_MAX_CAP) { set_error("sslam_two_view_ransac_batch_dev: cap=%d exceeds the supported %d (16 bytes of LDS per row)", cap, TWO_VIEW_MAX_CAP); return SSLAM_ERR_UNSUPPORTED; }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SSLAM_HIP(hipSetDevice(ctx->device));
     TwoViewArgs A;
     A.kp1 = d_kp1; A.n1 = d_n1; A.kp2 = d_kp2; A.n2 = d_n2; A.m12 = d_matches12; A.sets = d_sets;
     A.cap = cap; A.iterations = iterations; A.pair0 = 0; A.sigma = sigma; A.seed = seed;
     A.res = d_result; A.inl = d_inliers; A.tapSets = nullptr; A.tapMats = nullptr; A.tapScores = nullptr;
-    return two_view_launch(ctx, A, npairs, false, stream ? (hipStream_t)stream : ctx->stream);
+    return two_view_launch(ctx, A, npairs, false, pick(ctx, stream));
 }
 
 extern "C" int sslam_two_view_ransac(sslam_ctx* ctx, const sslam_keypoint* kp1, int n1, const sslam_keypoint* kp2, int n2, const int32_t* matches12, const int32_t* sets,

@@ -10,54 +10,21 @@
 //   gemm     a float 3 x 3 product accumulates each element in double (acc = 0; acc += a_ik * b_kj for k = 0, 1, 2) and rounds once; A*B*C is (A*B)*C.
 //   inverse  cofactors; determinant and its reciprocal in double, each element (cofactor * reciprocal) rounded once; a zero determinant gives the zero matrix.
 //
-// The draw: the reference's randi comes from rand(), seeded once per process; here randi = hash32(seed, pair, it, j) % remaining with
-//   mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16          (lowbias32)
-//   hash32(seed, pair, it, j) = mix(mix(mix(mix(seed + 0x9e3779b9) ^ pair) ^ it) ^ j)
-// in 32-bit unsigned arithmetic.  The swap-with-back of :101-106 is replayed without the copy of all indices: at most eight overwritten positions are remembered.
+// The draw (:93-108): draw_set<8> of ransac_draw.h, which states the hash that stands in for rand() and the replay of the swap-with-back.
 #pragma once
 #include <cstdint>
+#include "ransac_draw.h"
 
-#if defined(__HIPCC__)
-#define TV_FN __host__ __device__ inline
-#define TV_UNROLL _Pragma("unroll")
-#define TV_NOUNROLL _Pragma("nounroll")
-#else
-#define TV_FN inline
-#define TV_UNROLL
-#define TV_NOUNROLL
-#endif
+#define TV_FN RANSAC_FN
+#define TV_UNROLL RANSAC_UNROLL
+#define TV_NOUNROLL RANSAC_NOUNROLL
 
 namespace sslam {
 namespace tv {
 
-constexpr int JACOBI_SWEEPS = 8;
+using sslam::draw_set;      // :93-108 for one iteration over nm >= 8 matches: set is an int[8]
+
 constexpr int WS_DOUBLES = 45 + 81;      // per solve: the upper triangle of a symmetric 9 x 9 and the 9 x 9 of eigenvectors
-
-TV_FN uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-TV_FN uint32_t hash32(uint32_t seed, uint32_t pair, uint32_t it, uint32_t j) {
-    return mix32(mix32(mix32(mix32(seed + 0x9e3779b9u) ^ pair) ^ it) ^ j);
-}
-
-// :93-108 for one iteration over nm >= 8 matches.  pos[k] / val[k]: vAvailableIndices[pos[k]] was overwritten with val[k] in step k (the latest entry for a position holds).
-TV_FN void draw_set(uint32_t seed, uint32_t pair, uint32_t it, int nm, int set[8]) {
-    int pos[8], val[8];
-    TV_UNROLL
-    for (int j = 0; j < 8; ++j) {
-        const int remaining = nm - j;
-        const int randi = (int)(hash32(seed, pair, it, (uint32_t)j) % (uint32_t)remaining);
-        int idx = randi, back = remaining - 1;
-        TV_UNROLL
-        for (int k = 0; k < 8; ++k) if (k < j) {
-            if (pos[k] == randi) idx = val[k];
-            if (pos[k] == remaining - 1) back = val[k];
-        }
-        set[j] = idx;
-        pos[j] = randi; val[j] = back;
-    }
-}
 
 // :784-830 for one coordinate of one frame: mean and scale over ALL n keypoints.  get(i) = vKeys[i].pt.x (or .y)
 template <class Get>

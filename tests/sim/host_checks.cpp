@@ -2,6 +2,7 @@
 // -fsanitize=address,undefined -DSSLAM_TESTING (no GPU, no HIP: tests/sim/hip_stub stands in for the runtime):
 //   check_csr (csrc/match_check.h)        which CSR lists a call accepts, and that a refused list is never read past what its offsets promise
 //   all_aligned, rows_in_range, fits_31_bits (csrc/match_check.h)   the alignment and size rules of the device-resident batches, on both sides of every bound
+//   sim3_params_ok, injected_sets_ok (csrc/match_check.h)   the parameter rules of the RANSAC entry points (two_view.hip, sim3.hip), on both sides of every bound
 //   StreamOrderedBuf (csrc/common.h)      which runtime calls acquire / mark / release make, in which order
 //   gather_to_root (csrc/group_exchange.h) over the RCCL stand-in (csrc/rccl_standin.h), a thread per rank: the lengths' all-gather and the payload
 //                                         exchange of both group forms, for several rank counts, with and without the root's own bytes through the table
@@ -10,7 +11,9 @@
 #include "../../structure-slam-pointline_amd/csrc/match_check.h"
 #include "../../structure-slam-pointline_amd/csrc/group_exchange.h"
 #include "../../structure-slam-pointline_amd/csrc/rccl_standin.h"
+#include <cmath>
 #include <cstdarg>
+#include <limits>
 #include <memory>
 #include <thread>
 
@@ -71,6 +74,28 @@ static int check_argument_rules() {
     CHECK(fits_31_bits(1, INT32_MAX) && fits_31_bits(INT32_MAX, 1) && !fits_31_bits(1 << 16, 1 << 15) && !fits_31_bits(2, 1 << 30));      // 2^31 - 1 and 2^31
     CHECK(fits_31_bits((1 << 16) - 1, 1 << 15) && fits_31_bits(0, INT32_MAX) && fits_31_bits(INT32_MAX, 0) && !fits_31_bits(INT32_MAX, INT32_MAX));      // no wrap in 64 bits
     printf("argument rules ok\n");
+    return 0;
+}
+
+static int check_ransac_rules() {
+    std::unique_ptr<float[]> table(new float[1]{1.f});      // the rule looks at the pointer, never at a level
+    const float* t = table.get();
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    CHECK(sim3_params_ok(t, 1, 0.99, 1, 1, 1) && sim3_params_ok(t, 64, 0.99, 20, 300, 5));
+    CHECK(!sim3_params_ok(t, 0, 0.99, 1, 1, 1) && !sim3_params_ok(t, 65, 0.99, 1, 1, 1) && !sim3_params_ok(t, -1, 0.99, 1, 1, 1));      // nlevels in 1 .. 64
+    CHECK(!sim3_params_ok(nullptr, 1, 0.99, 1, 1, 1) && !sim3_params_ok(nullptr, 64, 0.99, 1, 1, 1));
+    CHECK(!sim3_params_ok(t, 8, 0.0, 1, 1, 1) && !sim3_params_ok(t, 8, 1.0, 1, 1, 1) && !sim3_params_ok(t, 8, nan, 1, 1, 1) && !sim3_params_ok(t, 8, -0.0, 1, 1, 1));
+    CHECK(sim3_params_ok(t, 8, std::nextafter(0.0, 1.0), 1, 1, 1) && sim3_params_ok(t, 8, std::nextafter(1.0, 0.0), 1, 1, 1));      // the nearest doubles inside (0, 1)
+    CHECK(!sim3_params_ok(t, 8, std::nextafter(1.0, 2.0), 1, 1, 1) && !sim3_params_ok(t, 8, -std::nextafter(0.0, 1.0), 1, 1, 1));
+    CHECK(!sim3_params_ok(t, 8, 0.99, 0, 1, 1) && !sim3_params_ok(t, 8, 0.99, 1, 0, 1) && !sim3_params_ok(t, 8, 0.99, 1, 1, 0));      // each count at 0 beside the 1s above
+    CHECK(!sim3_params_ok(t, 8, 0.99, -1, 1, 1) && !sim3_params_ok(t, 8, 0.99, 1, INT32_MIN, 1) && sim3_params_ok(t, 8, 0.99, INT32_MAX, INT32_MAX, INT32_MAX));
+    // injected sets: npairs * iterations stays below 2^28, asked only where sets are given
+    const int32_t sets[1] = {0};
+    CHECK(injected_sets_ok(sets, 1, (1 << 28) - 1) && !injected_sets_ok(sets, 1, 1 << 28) && injected_sets_ok(sets, (1 << 28) - 1, 1) && !injected_sets_ok(sets, 1 << 28, 1));
+    CHECK(injected_sets_ok(sets, 1 << 14, (1 << 14) - 1) && !injected_sets_ok(sets, 1 << 14, 1 << 14) && injected_sets_ok(sets, (1 << 14) + 1, (1 << 14) - 1));      // 2^28 - 2^14, 2^28, 2^28 - 1
+    CHECK(injected_sets_ok(nullptr, 1, 1 << 28) && injected_sets_ok(nullptr, 1 << 28, 1) && injected_sets_ok(nullptr, INT32_MAX, INT32_MAX) && injected_sets_ok(nullptr, 1, (1 << 28) - 1));
+    CHECK(!injected_sets_ok(sets, INT32_MAX, INT32_MAX) && injected_sets_ok(sets, 0, INT32_MAX));      // no wrap in 64 bits
+    printf("ransac rules ok\n");
     return 0;
 }
 
@@ -166,7 +191,7 @@ static int check_exchange() {
 }
 
 int main() {
-    if (check_csr_cases() || check_argument_rules() || check_stream_ordered_buf() || check_exchange()) return 1;
+    if (check_csr_cases() || check_argument_rules() || check_ransac_rules() || check_stream_ordered_buf() || check_exchange()) return 1;
     printf("ok\n");
     return 0;
 }

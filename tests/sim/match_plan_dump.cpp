@@ -7,6 +7,7 @@
 //   bow_arena NKF NF NNODES NK NFI   -> in[0..8] assigned count qbin validF total
 //   arena BYTES...                   -> the offset of every take(), then size()
 //   sizes                            -> sizeof(sslam_keypoint) sizeof(sslam_proj_query)
+//   twoview CAP, sim3 CAP            -> rowBytes ldsBytes ldsOptIn threads maxCap (two_view_plan, sim3_plan: the RANSAC units)
 // The first token of a line may name the family of a device-resident batch instead:
 //   proj_batch (sslam_search_by_projection_batch_dev)
 //     consts                                      -> PROJ_MAXN PROJ_TWO_KERNEL_MAXN PROJ_K PROJ_BATCH_SCRATCH_MAX PROJ_BATCH_MAX_SLICE DYNAMIC_LDS_DEFAULT_MAX
@@ -53,6 +54,9 @@ static bool single_calls(const std::string& cmd, const long long* v, int nv) {
         const BowArena a = bow_arena((int)v[0], (int)v[1], (int)v[2], (int)v[3], (int)v[4]);
         for (int i = 0; i < 9; ++i) printf("%zu ", a.in[i]);
         printf("%zu %zu %zu %zu %zu\n", a.assigned, a.count, a.qbin, a.validF, a.total);
+    } else if ((cmd == "twoview" || cmd == "sim3") && nv == 1) {
+        const RansacPlan P = cmd == "sim3" ? sim3_plan((int)v[0]) : two_view_plan((int)v[0]);
+        printf("%d %zu %d %u %d\n", P.rowBytes, P.ldsBytes, P.ldsOptIn, P.threads, P.maxCap);
     } else if (cmd == "sizes") {
         printf("%zu %zu\n", sizeof(sslam_keypoint), sizeof(sslam_proj_query));
     } else return false;

@@ -5,26 +5,9 @@ csrc/sim3_math.h: the constructor's filters and values (:62-109), SetRansacParam
 checked against LAPACK in tests/test_sim3_cases_cpu.py); everything downstream of it is recomputed here."""
 import math
 import numpy as np
+from ransac_ref import mix32, hash32, draw      # the draw of :163-177 given the random integers, and the library's stand-in for rand()
 
 f32, f64 = np.float32, np.float64
-M32 = 0xFFFFFFFF
-
-
-def mix32(x):
-    x ^= x >> 16; x = (x * 0x7feb352d) & M32; x ^= x >> 15; x = (x * 0x846ca68b) & M32; x ^= x >> 16
-    return x
-
-
-def hash32(seed, pair, it, j):
-    return mix32(mix32(mix32(mix32((seed + 0x9e3779b9) & M32) ^ pair) ^ it) ^ j)
-
-
-def draw(n, randi):
-    """:163-177: vAvailableIndices = mvAllIndices, three times take [randi] and move the back into its place"""
-    avail = list(range(n)); out = []
-    for r in randi:
-        out.append(avail[r]); avail[r] = avail[-1]; avail.pop()
-    return out
 
 
 def max_its(probability, min_inliers, max_iterations, N):

@@ -7,35 +7,19 @@ fix_scale, probability, min_inliers, max_iterations, calls (the new_iterations o
 [max_iterations, 3]), seed, pair.  The answer per case: n, idx1 (int [N]: mvnIndices1), img (float32 [N, 6]: P1im1, P2im2, maxErr1, maxErr2) and calls, one dict per
 call: its (the iterations it ran), sets (int32 [k, 3]), mats (float32 [k, 13]: s, R, t), counts (int32 [k]), nent (float32 [k, 10]), q (float64 [k, 4]), marks
 (uint8 [k, N]: mvbInliersi), state (a frontend.SIM3_STATE_DTYPE record) and inliers (uint8 [n1])."""
-import atexit, functools, os, shutil, subprocess, tempfile
+import os
 import numpy as np
+import host_sim
 import pkg
+from host_sim import bits as _bits, ints as _ints, floats as _floats
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "sim", "sim3_sim.cpp")
 
 
-@functools.lru_cache(maxsize=None)
 def programs():
-    """(plain, sanitised): the two builds of the sim, in a directory that goes away with the process"""
-    d = tempfile.mkdtemp(prefix="sim3_sim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    plain, san = os.path.join(d, "sim3_sim"), os.path.join(d, "sim3_sim_san")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", SRC, "-o", plain])
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", SRC, "-o", san])
-    return plain, san
-
-
-def _bits(a):
-    return " ".join(map(str, np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()))
-
-
-def _ints(a):
-    return " ".join(map(str, np.asarray(a, np.int64).ravel().tolist()))
-
-
-def _floats(tokens):
-    return np.array([int(t) for t in tokens], np.uint64).astype(np.uint32).view(np.float32)
+    """(plain, sanitised): the two builds of the sim (host_sim.py)"""
+    return host_sim.programs(SRC)
 
 
 def encode(c):
@@ -90,17 +74,8 @@ def decode(text, cases):
 
 def run_plain(cases):
     """the plain build alone: for the searches of tests/sim3_cases.py, whose finds go through run() afterwards"""
-    r = subprocess.run([programs()[0]], input="".join(encode(c) for c in cases), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-2000:])
-    return decode(r.stdout, cases)
+    return decode(host_sim.run_plain(SRC, "".join(encode(c) for c in cases)), cases)
 
 
 def run(cases):
-    text = "".join(encode(c) for c in cases)
-    outs = []
-    for exe in programs():
-        r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0 and r.stderr == "", (exe, r.returncode, r.stderr[-2000:])
-        outs.append(r.stdout)
-    assert outs[0] == outs[1], "the plain and the sanitised build of the sim answer differently"
-    return decode(outs[0], cases)
+    return decode(host_sim.run(SRC, "".join(encode(c) for c in cases)), cases)

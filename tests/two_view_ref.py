@@ -3,6 +3,7 @@ the source has float and float64 where it has double.  Written from the referenc
 CheckFundamental (:334-497), the draw of :93-108 given the random integers, and the selection (:118, :143, :196, :246).  The 8-point solves and the matrix compositions are
 OpenCV's (decision D15) and are not here: the Check functions take the matrices the sim made."""
 import numpy as np
+from ransac_ref import mix32, hash32, draw      # the draw of :93-108 given the random integers, and the library's stand-in for rand()
 
 f32, f64 = np.float32, np.float64
 
@@ -147,19 +148,6 @@ def check_fundamental(F21, rows, sigma):
     return sum_in_order(terms), inl
 
 
-def draw(N, randi):
-    """:93-108 for one iteration: randi[j] = the integer RandomInt(0, vAvailableIndices.size() - 1) returned in step j"""
-    avail = list(range(N))
-    out = []
-    for j in range(8):
-        r = int(randi[j])
-        assert 0 <= r <= len(avail) - 1
-        out.append(avail[r])
-        avail[r] = avail[-1]
-        avail.pop()
-    return out
-
-
 def select(scores):
     """:168-201 / :218-251 over the scores of the iterations in order: (best score, winning iteration or -1)"""
     best, it = f32(0), -1
@@ -174,14 +162,3 @@ def model(SH, SF):
     with np.errstate(all="ignore"):
         RH = f32(f32(SH) / f32(f32(SH) + f32(SF)))
     return RH, 1 if f64(RH) > 0.40 else 2
-
-
-def mix32(x):
-    x &= 0xFFFFFFFF
-    x ^= x >> 16; x = (x * 0x7feb352d) & 0xFFFFFFFF; x ^= x >> 15; x = (x * 0x846ca68b) & 0xFFFFFFFF; x ^= x >> 16
-    return x
-
-
-def hash32(seed, pair, it, j):
-    """the library's stand-in for rand() (include/sslam_frontend.h, csrc/two_view_math.h)"""
-    return mix32(mix32(mix32(mix32(seed + 0x9e3779b9) ^ pair) ^ it) ^ j)

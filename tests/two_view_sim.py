@@ -4,31 +4,19 @@ loaded into Python.  run(cases) sends every case through both builds: both must 
 (float32 [n, 2]: the undistorted pt.x, pt.y), m12 (int32 [n1]), sets (None or int32 [iterations, 8]), iterations, sigma, seed and pair; the answer per case is a dict
 with norm (float32 [8]), sets (int32 [iterations, 8]), mats (float32 [iterations, 6, 9]: Hn, H21i, H12i, Fn, F21i and Fpre, which the testing tap does not return), scores (float32 [iterations, 2]), result (a
 frontend.TWO_VIEW_RESULT_DTYPE record) and inliers (uint8 [n1]); a pair below 8 matches has zeros in sets, mats and scores, as the testing tap has."""
-import atexit, functools, os, shutil, subprocess, tempfile
+import os
 import numpy as np
+import host_sim
 import pkg
+from host_sim import bits as _bits, ints as _ints, floats as _floats
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "sim", "two_view_sim.cpp")
 
 
-@functools.lru_cache(maxsize=None)
 def programs():
-    """(plain, sanitised): the two builds of the sim, in a directory that goes away with the process"""
-    d = tempfile.mkdtemp(prefix="two_view_sim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    plain, san = os.path.join(d, "two_view_sim"), os.path.join(d, "two_view_sim_san")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", SRC, "-o", plain])
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", SRC, "-o", san])
-    return plain, san
-
-
-def _bits(a):
-    return " ".join(map(str, np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()))
-
-
-def _ints(a):
-    return " ".join(map(str, np.asarray(a, np.int64).ravel().tolist()))
+    """(plain, sanitised): the two builds of the sim (host_sim.py)"""
+    return host_sim.programs(SRC)
 
 
 def encode(c):
@@ -39,10 +27,6 @@ def encode(c):
         assert np.asarray(c["sets"]).shape == (c["iterations"], 8)
         parts.append(_ints(c["sets"]))
     return "\n".join(parts) + "\n"
-
-
-def _floats(tokens):
-    return np.array([int(t) for t in tokens], np.uint64).astype(np.uint32).view(np.float32)
 
 
 def decode(text, cases):
@@ -78,17 +62,8 @@ def decode(text, cases):
 
 def run_plain(cases):
     """the plain build alone: for the searches of tests/two_view_cases.py, whose finds go through run() afterwards"""
-    r = subprocess.run([programs()[0]], input="".join(encode(c) for c in cases), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-2000:])
-    return decode(r.stdout, cases)
+    return decode(host_sim.run_plain(SRC, "".join(encode(c) for c in cases)), cases)
 
 
 def run(cases):
-    text = "".join(encode(c) for c in cases)
-    outs = []
-    for exe in programs():
-        r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0 and r.stderr == "", (exe, r.returncode, r.stderr[-2000:])
-        outs.append(r.stdout)
-    assert outs[0] == outs[1], "the plain and the sanitised build of the sim answer differently"
-    return decode(outs[0], cases)
+    return decode(host_sim.run(SRC, "".join(encode(c) for c in cases)), cases)

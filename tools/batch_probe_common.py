@@ -1,5 +1,6 @@
 """What the tools/*_batch_probe.py share: the command line, the collected lines and their --out file, the library that route (a) runs on, the
-timing of one enqueued pass of route (b), alternating passes, the closing JSON line and the exit status.  A probe keeps what is its own: the workload,
+timing of one enqueued pass of route (b), alternating passes, a kernel's own time through the profile drain, the bitwise comparison of floats, the closing JSON
+line and the exit status.  A probe keeps what is its own: the workload,
 the loop (a), the call (b) and the comparison of their results."""
 import argparse, ctypes as C, json, sys, time
 import numpy as np
@@ -95,3 +96,26 @@ def alternate(reps, run_a, run_b):
 def b_medians(tb):
     """-> the medians of (device ms, wall ms, enqueue ms) over the passes of timed_pass"""
     return tuple(med([x[i] for x in tb]) for i in range(3))
+
+
+def drain(L, h):
+    """sslam_profile_drain of context h on library L -> {kernel name: ms} since the last drain"""
+    names = (C.c_char_p * 16)(); ms = (C.c_double * 16)(); cnt = (C.c_int * 16)()
+    n = L.sslam_profile_drain(h, names, ms, cnt, 16)
+    return {names[i].decode(): ms[i] for i in range(n)}
+
+
+def kernel_passes(L, h, st, enqueue, kernel, reps):
+    """a kernel's own time: a warm-up pass and `reps` passes of enqueue() on stream st with the profile on -> the ms of `kernel` in each of the `reps`"""
+    L.sslam_profile_enable(h, 1)
+    k = []
+    for _ in range(reps + 1):
+        enqueue(); st.synchronize()
+        k.append(drain(L, h)[kernel])
+    L.sslam_profile_enable(h, 0)
+    return k[1:]
+
+
+def same_floats(a, b):
+    """float32 values alike bit for bit, a NaN equal to any NaN"""
+    return bool(((np.ascontiguousarray(a, np.float32).view(np.uint32) == np.ascontiguousarray(b, np.float32).view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())

@@ -15,7 +15,7 @@ k_distinct_batch + k_distinct_large of (b) on the same sets.  THE CONDITION (64 
 more than the spread (max - min) of k_distinctive's own passes.
 --loop-lib: the library (a) runs on, e.g. a build of the parent commit (default: the library under test).  d_best and the table of (b) must equal (a)'s
 for every set, or the probe exits non-zero."""
-import ctypes as C, os, sys, time
+import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
@@ -26,12 +26,6 @@ import batch_probe_common as bp
 from batch_probe_common import med
 
 POINTS, K, N = 2000, 21, 1000
-
-
-def drain(L, h):
-    names = (C.c_char_p * 16)(); ms = (C.c_double * 16)(); cnt = (C.c_int * 16)()
-    n = L.sslam_profile_drain(h, names, ms, cnt, 16)
-    return {names[i].decode(): ms[i] for i in range(n)}
 
 
 def main():
@@ -93,12 +87,12 @@ def main():
         LA.sslam_profile_enable(hA, 1)
         for _ in range(a.reps + 1):
             if LA.sslam_distinctive_descriptors(hA, p_(rows), p_(ptr), ns, p_(best_a)): raise RuntimeError(LA.sslam_last_error())
-            ka.append(drain(LA, hA)["k_distinctive"])
+            ka.append(bp.drain(LA, hA)["k_distinctive"])
         LA.sslam_profile_enable(hA, 0)
         fe.lib().sslam_profile_enable(ctx.h, 1)
         for _ in range(a.reps + 1):
             enqueue_b(); st.synchronize()
-            d = drain(fe.lib(), ctx.h)
+            d = bp.drain(fe.lib(), ctx.h)
             kb.append(d["k_distinct_batch"] + d["k_distinct_large"]); kb_split.append((d["k_distinct_batch"], d["k_distinct_large"]))
         fe.lib().sslam_profile_enable(ctx.h, 0)
         ka, kb, kb_split = ka[1:], kb[1:], kb_split[1:]                       # the first pass of each is the warm-up

@@ -12,7 +12,7 @@ batch is unique pair p % unique (its draw still hashes p).
 (b): device time between two HIP events around the call on a side stream, wall time from the call to the end of a stream synchronise, and k_sim3_ransac alone through
 sslam_profile_enable / sslam_profile_drain.  After a warm-up pass, `reps` passes; medians, with the lowest and highest pass.  The states and inlier rows of the first `unique`
 pairs of every batch must equal the sim's bit for bit, or the probe exits non-zero."""
-import ctypes as C, os, sys, time
+import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
@@ -27,14 +27,8 @@ N, MATCHES, SEED = 1000, 150, 2026
 INTS = ("its_done", "best_inliers", "best_it", "n", "max_its", "found_it", "n_inliers", "no_more")
 
 
-def drain(L, h):
-    names = (C.c_char_p * 16)(); ms = (C.c_double * 16)(); cnt = (C.c_int * 16)()
-    n = L.sslam_profile_drain(h, names, ms, cnt, 16)
-    return {names[i].decode(): ms[i] for i in range(n)}
-
-
 def same_state(got, want):
-    f = lambda a, b: bool(((np.ascontiguousarray(a, np.float32).view(np.uint32) == np.ascontiguousarray(b, np.float32).view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
+    f = bp.same_floats
     return all(int(got[k]) == int(want[k]) for k in INTS) and all(f(got[k], want[k]) for k in ("s12", "R12", "t12"))
 
 
@@ -86,13 +80,7 @@ def main():
             same = all(same_state(got[p], want[p]["calls"][0]["state"]) and np.array_equal(gi[p], want[p]["calls"][0]["inliers"]) for p in range(min(B, U)))
             all_equal = all_equal and same
             tb = [bp.timed_pass(st, enqueue) for _ in range(a.reps)]
-            fe.lib().sslam_profile_enable(ctx.h, 1)
-            kb = []
-            for _ in range(a.reps + 1):
-                enqueue(); st.synchronize()
-                kb.append(drain(fe.lib(), ctx.h)["k_sim3_ransac"])
-            fe.lib().sslam_profile_enable(ctx.h, 0)
-            kb = kb[1:]
+            kb = bp.kernel_passes(fe.lib(), ctx.h, st, enqueue, "k_sim3_ransac", a.reps)
             dev_ms, wall_ms, enq_ms = bp.b_medians(tb)
             report[tag]["B%d" % B] = dict(pairs=B, equal=same, b_device_ms=dev_ms, b_wall_ms=wall_ms, b_enqueue_ms=enq_ms, b_all_ms=tb, k_sim3_ransac_ms=med(kb), k_sim3_ransac_all_ms=kb,
                                           us_per_pair=dev_ms * 1e3 / B)

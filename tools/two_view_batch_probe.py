@@ -9,7 +9,7 @@ noise), the rest anywhere; 200 iterations, sigma 1, the library draws the sets. 
 (b): device time between two HIP events around the call on a side stream, wall time from the call to the end of a stream synchronise, and k_two_view alone through
 sslam_profile_enable / sslam_profile_drain.  After a warm-up pass, `reps` passes; medians, with the lowest and highest pass.  The results of the first `unique` pairs of every
 batch must equal the sim's bit for bit, or the probe exits non-zero."""
-import ctypes as C, os, sys, time
+import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
@@ -23,14 +23,8 @@ from batch_probe_common import med
 N, MATCHES, ITERATIONS, SIGMA, SEED = 1000, 300, 200, 1.0, 2026
 
 
-def drain(L, h):
-    names = (C.c_char_p * 16)(); ms = (C.c_double * 16)(); cnt = (C.c_int * 16)()
-    n = L.sslam_profile_drain(h, names, ms, cnt, 16)
-    return {names[i].decode(): ms[i] for i in range(n)}
-
-
 def same_result(got, want):
-    f = lambda a, b: bool(((np.ascontiguousarray(a, np.float32).view(np.uint32) == np.ascontiguousarray(b, np.float32).view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
+    f = bp.same_floats
     return all(int(got[k]) == int(want[k]) for k in ("nmatches", "model", "best_it_h", "best_it_f")) and all(f(got[k], want[k]) for k in ("score_h", "score_f", "rh", "H21", "F21"))
 
 
@@ -67,13 +61,7 @@ def main():
         same = all(same_result(got[p], want[p]["result"]) and np.array_equal(gi[p], want[p]["inliers"]) for p in range(min(B, U)))
         all_equal = all_equal and same
         tb = [bp.timed_pass(st, enqueue) for _ in range(a.reps)]
-        fe.lib().sslam_profile_enable(ctx.h, 1)
-        kb = []
-        for _ in range(a.reps + 1):
-            enqueue(); st.synchronize()
-            kb.append(drain(fe.lib(), ctx.h)["k_two_view"])
-        fe.lib().sslam_profile_enable(ctx.h, 0)
-        kb = kb[1:]
+        kb = bp.kernel_passes(fe.lib(), ctx.h, st, enqueue, "k_two_view", a.reps)
         dev_ms, wall_ms, enq_ms = bp.b_medians(tb)
         report["B%d" % B] = dict(pairs=B, equal=same, b_device_ms=dev_ms, b_wall_ms=wall_ms, b_enqueue_ms=enq_ms, b_all_ms=tb, k_two_view_ms=med(kb), k_two_view_all_ms=kb,
                                  us_per_pair=dev_ms * 1e3 / B, models=[int((got["model"] == m).sum()) for m in (0, 1, 2)])
