@@ -275,6 +275,61 @@ int sslam_sim3_ransac(sslam_ctx* ctx, const sslam_keypoint* kp1, const float* x3
         const int32_t* sets /* NULL or [max_iterations*3] */, uint32_t seed,
         sslam_sim3_state* state /* in/out */, uint8_t* inliers /* [n1] */);
 
+/* PnPsolver (src/PnPsolver.cc), the pose RANSAC of Tracking::Relocalization (src/Tracking.cc:2004-2030) between SearchByBoW (:1996, sslam_orb_search_by_bow_batch_dev)
+ * and SearchByProjection (:2071, :2085, sslam_search_by_projection_batch_dev): one iterate(new_iterations, ..) call (:165-258) for `npairs` (keyframe, frame) pairs of
+ * device-resident slots, asynchronously.  The layouts and the pair arrays are those of sslam_orb_search_by_bow_batch_dev: frame slot f owns rows [f*cap, f*cap + d_nf[f])
+ * of d_f_kp (mvKeysUn) and d_f_K[4f .. 4f+4) = fx fy cx cy; keyframe slot k owns rows [k*kfcap, k*kfcap + d_nkf[k]) of d_kf_xw (three floats a row: GetWorldPos of the
+ * keyframe's map point, the caller fills it) and d_kf_valid (= vpMapPointsKF[i] && !isBad(); NULL: all valid).  A count below 0 is read as 0, one above its capacity as
+ * the capacity.  Pair p takes keyframe slot d_pair_kf[p] and frame slot d_pair_f[p]; either array may be NULL, which means slot p and requires that side's slot count
+ * to equal npairs.  A pair with a slot outside its range is skipped: its state reads n = min_inliers = max_its = found = n_inliers = 0, found_it = -1, no_more = 1 and
+ * nothing else of it is written.  d_assigned[p*cap + j] is what the matcher wrote and is read where it lies.
+ * The constructor (:67-110): frame row j < nf is a correspondence when 0 <= a = d_assigned[p*cap + j] < nkf, keyframe row a is valid and the keypoint's octave lies in
+ * [0, nlevels); the list is in ascending j (mvKeyPointIndices) and has N entries; mvMaxError = level_sigma2[octave] * th2 in float (:156).  SetRansacParameters
+ * (:121-157) with the minimal set of four: the adjusted mRansacMinInliers and mRansacMaxIts of every N come from a table that the context builds on the host with libm and
+ * keeps on the device until (probability, min_inliers, max_iterations, epsilon, cap) change.  iterate's loop condition (:182) is an OR: a call runs up to iteration
+ * max(max_its, its_done + new_iterations), so the first call runs all max_its iterations unless it returns.  An iteration whose count is >= min_inliers becomes the best
+ * when it is strictly greater than every earlier one, then Refine (:260-305) runs on the best set and the call returns when the refined count is > min_inliers
+ * (found = 1, :226-236); the call after such a return returns again at its first qualifying iteration.  A call that ends with its_done >= max_its sets no_more and, with
+ * best_inliers >= min_inliers, returns the unrefined best (found = 2, :241-255).  d_inliers[p*cap + j], j < nf, = vbInliers of the return by frame row (0 without
+ * one); rows at or past the frame's count are not touched.  The OpenCV leaves of EPnP (:375-950) are decision D17 of DESIGN.md.
+ * The draw: DUtils::Random::RandomInt is replaced by hash32(seed, pair, iteration, j) (csrc/ransac_draw.h).  With d_sets, iteration `it` of pair p takes the four
+ * indices d_sets[(p*nsets + it)*4 ..) into the correspondence list; a set for an iteration >= nsets or with an index outside [0, N) makes a hypothesis that never
+ * qualifies; equal indices are legal.
+ * level_sigma2 is HOST memory (nlevels floats, 1 .. 64); every other pointer is a device pointer, 4-byte aligned, d_state 8-byte.  One launch on `stream` (NULL: the
+ * context's stream), no synchronise, no host memory touched but the table's upload.  SSLAM_ERR_INVALID (nothing enqueued): a NULL buffer other than d_kf_valid, the pair
+ * arrays and d_sets, a misaligned one, probability outside (0, 1), min_inliers, max_iterations or new_iterations < 1, epsilon outside (0, 1], th2 <= 0 or NaN, cap or
+ * kfcap < 1, npairs * cap, nframes * cap or nkeyframes * kfcap >= 2^31, with d_sets npairs * nsets >= 2^28, a NULL pair array whose side has another slot count than
+ * npairs.  SSLAM_ERR_UNSUPPORTED (nothing enqueued): cap > 2048 (the correspondences sit in LDS, 24 bytes each, beside the EPnP workspace).  npairs == 0 is SSLAM_OK and
+ * enqueues nothing.  The single call takes one pair from host memory, runs it as pair 0 of the same kernel with cap = nf rounded up to a multiple of 512 (one table serves candidates of different sizes) and synchronises. */
+typedef struct sslam_pnp_state {       /* 192 bytes, no padding; zero-filled = a new PnPsolver */
+    int32_t its_done;        /* in/out  mnIterations */
+    int32_t best_inliers;    /* in/out  mnBestInliers */
+    int32_t best_it;         /* in/out  iteration that holds the best, -1 none yet (read as -1 when its_done == 0) */
+    int32_t refine_ok;       /* in/out  whether Refine of the best set succeeds; 0 while there is no best */
+    int32_t n;               /* out     N: correspondences the call saw */
+    int32_t min_inliers;     /* out     the adjusted mRansacMinInliers */
+    int32_t max_its;         /* out     mRansacMaxIts; 0 when n < min_inliers */
+    int32_t found;           /* out     0 none, 1 the refined pose (:226-236), 2 the best at exhaustion (:244-253) */
+    int32_t found_it;        /* out     found 1: the iteration iterate() returned at; found 2: best_it; else -1 */
+    int32_t n_inliers;       /* out     nInliers of that return, else 0 */
+    int32_t no_more;         /* out     bNoMore */
+    int32_t pad_;            /* keeps the doubles 8-byte aligned; not written */
+    double  best_R[9], best_t[3];   /* in/out  mRi / mti of the best iteration (row-major) */
+    float   Tcw[12];         /* out     rows 0 .. 2 of the returned 4 x 4, float as :217-223 / :294-300; zeros without a return */
+} sslam_pnp_state;
+int sslam_pnp_ransac_batch_dev(sslam_ctx* ctx, const sslam_keypoint* d_f_kp, const int32_t* d_nf, int cap, int nframes, const float* d_f_K /* [nframes*4] */,
+        const float* d_kf_xw /* [nkeyframes*kfcap*3] */, const uint8_t* d_kf_valid, const int32_t* d_nkf, int kfcap, int nkeyframes,
+        const float* level_sigma2 /* HOST, nlevels */, int nlevels,
+        const int32_t* d_pair_kf, const int32_t* d_pair_f, int npairs, const int32_t* d_assigned,
+        double probability, int min_inliers, int max_iterations, float epsilon, float th2, int new_iterations,
+        const int32_t* d_sets /* NULL or [npairs*nsets*4] */, int nsets, uint32_t seed,
+        sslam_pnp_state* d_state /* [npairs] in/out */, uint8_t* d_inliers /* [npairs*cap], by frame row */, void* stream);
+int sslam_pnp_ransac(sslam_ctx* ctx, const sslam_keypoint* f_kp, int nf, const float f_K[4], const float* kf_xw, const uint8_t* kf_valid, int nkf,
+        const float* level_sigma2, int nlevels, const int32_t* assigned /* [nf] */,
+        double probability, int min_inliers, int max_iterations, float epsilon, float th2, int new_iterations,
+        const int32_t* sets /* NULL or [nsets*4] */, int nsets, uint32_t seed,
+        sslam_pnp_state* state /* in/out */, uint8_t* inliers /* [nf] */);
+
 /* The projection-window matcher family.  The tracker keeps the projection / visibility logic (poses, map
  * points: host state) and hands over one query per map point or map line; the device replays the
  * window search, the best/second-best Hamming selection, the level-consistent ratio test, the

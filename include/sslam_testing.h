@@ -142,6 +142,16 @@ int sslam_testing_sim3_hypotheses(sslam_ctx* ctx, const sslam_keypoint* kp1, con
                                   const int32_t* sets, uint32_t seed, int pair, sslam_sim3_state* state, uint8_t* inliers,
                                   int32_t* sets_out, float* mats_out, int32_t* counts_out);
 
+/* sslam_pnp_ransac for one host pair with EVERY iteration the reference's loop ran copied back: the same kernel with its stores enabled, run as pair `pair` of a batch.  By
+ * absolute iteration it < tap_rows (later ones are not recorded): sets_out[it*4 .. +4) = the four indices into the correspondence list, poses_out[it*12 .. +12) = mRi
+ * (row-major), mti in double, counts_out[it*4 .. +4) = mnInliersi (-1 for a set that never qualifies, whose pose is zero), the N that compute_pose chose (:518-520) in the low byte with the branches the solve reached above it (bit 8: the det < 0 flip, 9: the pcs[2] < 0 sign change, 10: b4[0] < 0, 11: a dropped singular value of CC),
+ * whether Refine ran at this iteration in the reference's loop (:226) and mnRefinedInliers of that run, trace_out[it*15 .. +15) = rep_errors[1 .. 3] and Betas[1 .. 3]
+ * after gauss_newton.  Rows of iterations this call did not run are zero.  state and inliers as sslam_pnp_ransac. */
+int sslam_testing_pnp_hypotheses(sslam_ctx* ctx, const sslam_keypoint* f_kp, int nf, const float f_K[4], const float* kf_xw, const uint8_t* kf_valid, int nkf,
+                                 const float* level_sigma2, int nlevels, const int32_t* assigned, double probability, int min_inliers, int max_iterations, float epsilon,
+                                 float th2, int new_iterations, const int32_t* sets, int nsets, uint32_t seed, int pair, sslam_pnp_state* state, uint8_t* inliers,
+                                 int tap_rows, int32_t* sets_out, double* poses_out, int32_t* counts_out, double* trace_out);
+
 #ifdef __cplusplus
 }
 #endif

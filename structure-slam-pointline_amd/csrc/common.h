@@ -89,13 +89,13 @@ struct sslam_prof_rec { const char* name; hipEvent_t a, b; };
 
 // Slots of sslam_ctx::scratch and ::pinned (match.hip) with their users.  A slot with several users is safe to share because every one of
 // them holds ctx->mu for the whole call and synchronises the stream before it returns.  The two buffers whose users return with kernels still
-// running on the caller's stream are no slots: sslam_ctx::knnExpand, ::projBatch, ::recordOffsets and ::sim3Table.dev, a StreamOrderedBuf each.
+// running on the caller's stream are no slots: sslam_ctx::knnExpand, ::projBatch, ::recordOffsets, ::sim3Table.dev and ::pnpTable.dev, a StreamOrderedBuf each.
 enum {
     SCR_KNN_Q = 0, SCR_KNN_T = 1, SCR_KNN_OUT = 2,      // sslam_hamming_knn2, sslam_hamming_matrix: query rows, train rows, result
     SCR_SFI_STATE = 3,       // sslam_orb_search_for_initialization_batch_dev: per-pair state (SfiArgs::scratch)
     SCR_SFI_STAGE = 4,       // sslam_orb_search_for_initialization: the pair and its results
     SCR_LINE_MATCH = 5,      // sslam_line_match
-    SCR_CALL = 6,            // the arena of search_proj_core, sslam_hamming_knn2_frames, sslam_distinctive_descriptors, sslam_fuse_search, sslam_orb_search_for_triangulation, bow_core, sslam_two_view_ransac (two_view.hip), sslam_sim3_ransac (sim3.hip): laid out with ArenaLayout (match_plan.h), staged field by field through Staging (below) except by search_proj_core
+    SCR_CALL = 6,            // the arena of search_proj_core, sslam_hamming_knn2_frames, sslam_distinctive_descriptors, sslam_fuse_search, sslam_orb_search_for_triangulation, bow_core, sslam_two_view_ransac (two_view.hip), sslam_sim3_ransac (sim3.hip), sslam_pnp_ransac (pnp.hip): laid out with ArenaLayout (match_plan.h), staged field by field through Staging (below) except by search_proj_core
     SCR_UPLOAD = 7,          // host features that a core with an arena in SCR_CALL reads (sslam_search_by_projection, sslam_bow_transform); the arena of search_by_bow_core
     SCR_COUNT = 8
 };
@@ -126,6 +126,14 @@ struct sslam_ctx {
         double probability = 0;
         int minInliers = 0, maxIterations = 0, cap = 0;
     } sim3Table;
+    struct PnpTable {                      // sslam_pnp_ransac_batch_dev: (mRansacMinInliers, mRansacMaxIts) for every N in 0 .. cap and the key it was built for (pnp.hip)
+        sslam::StreamOrderedBuf dev;
+        sslam::HostPinned host;
+        bool built = false;
+        double probability = 0;
+        float epsilon = 0;
+        int minInliers = 0, maxIterations = 0, cap = 0;
+    } pnpTable;
     int num_cus = 0;
     void* batchCache = nullptr;                  // sslam_frontend_batch: staging buffers, streams, events kept between calls (batch.hip)
     void (*batchCacheFree)(void*) = nullptr;

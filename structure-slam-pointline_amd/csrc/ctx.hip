@@ -73,13 +73,13 @@ extern "C" int sslam_ctx_destroy(sslam_ctx* c) {
     if (!c) return SSLAM_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->knnExpand.release(); c->projBatch.release(); c->recordOffsets.release(); c->sim3Table.dev.release();      // a batch matcher call or a pack may still run on a caller's stream: release() waits for it
+    c->knnExpand.release(); c->projBatch.release(); c->recordOffsets.release(); c->sim3Table.dev.release(); c->pnpTable.dev.release();      // a batch matcher call or a pack may still run on a caller's stream: release() waits for it
     if (c->batchCache && c->batchCacheFree) { c->batchCacheFree(c->batchCache); c->batchCache = nullptr; }
     for (auto& b : c->scratch) b.release();
     c->camKp.release();
     c->colorIn.release(); c->colorGray.release();
     for (auto& b : c->pinned) b.release();
-    c->sim3Table.host.release();
+    c->sim3Table.host.release(); c->pnpTable.host.release();
     (void)hipStreamDestroy(c->stream);
     delete c;
     return SSLAM_OK;

@@ -1,4 +1,4 @@
-// The argument checks that matcher entry points share (match.hip, two_view.hip, sim3.hip): the CSR lists of vocabulary nodes, observation sets and children, the
+// The argument checks that matcher entry points share (match.hip, two_view.hip, sim3.hip, pnp.hip): the CSR lists of vocabulary nodes, observation sets and children, the
 // alignment and size rules of device-resident batches, and the parameter rules of the RANSAC entry points.  Host code and no HIP in here: tests/sim/host_checks.cpp compiles it with a plain host compiler under the sanitizers and supplies its own set_error.
 #pragma once
 #include <cstdint>
@@ -32,6 +32,16 @@ inline bool fits_31_bits(int slots, int cap) { return (long long)slots * (long l
 // iterate's nIterations.  probability lies strictly inside (0, 1): log(1 - probability) has to be finite and negative; a NaN fails both comparisons.
 inline bool sim3_params_ok(const float* level_sigma2, int nlevels, double probability, int min_inliers, int max_iterations, int new_iterations) {
     return level_sigma2 && nlevels >= 1 && nlevels <= 64 && probability > 0.0 && probability < 1.0 && min_inliers >= 1 && max_iterations >= 1 && new_iterations >= 1;
+}
+// The parameters sslam_pnp_ransac and sslam_pnp_ransac_batch_dev share (pnp.hip): as above, and SetRansacParameters' epsilon in (0, 1] and th2 > 0; a NaN fails every
+// comparison.  The minimal set is four.
+inline bool pnp_params_ok(const float* level_sigma2, int nlevels, double probability, int min_inliers, int max_iterations, int new_iterations, float epsilon, float th2) {
+    return sim3_params_ok(level_sigma2, nlevels, probability, min_inliers, max_iterations, new_iterations) && epsilon > 0.f && epsilon <= 1.f && th2 > 0.f;
+}
+// The sizes of a PnP batch: rows are indexed pair * cap + j, frame * cap + j and keyframe * kfcap + i in 31 bits; the caller's sets pair * nsets + it below 2^28
+inline bool pnp_sizes_ok(int npairs, int cap, int nframes, int nkeyframes, int kfcap, const void* d_sets, int nsets) {
+    return npairs >= 0 && cap >= 1 && nframes >= 0 && nkeyframes >= 0 && kfcap >= 1 && fits_31_bits(npairs, cap) && fits_31_bits(nframes, cap) && fits_31_bits(nkeyframes, kfcap) &&
+           (!d_sets || (nsets >= 0 && (long long)npairs * (long long)nsets < (1ll << 28)));
 }
 // Injected sets of a RANSAC batch (d_sets: iterations sets per pair): their rows are indexed pair * iterations + it, which stays below 2^28 so that the index times the
 // words of a set fits 31 bits.  Without sets the rule asks nothing.

@@ -1,4 +1,4 @@
-// Host-side plans of the matcher entry points (match.hip) and of the RANSAC units (two_view.hip, sim3.hip): which kernel a call launches for its sizes, the sizes that follow from
+// Host-side plans of the matcher entry points (match.hip) and of the RANSAC units (two_view.hip, sim3.hip, pnp.hip): which kernel a call launches for its sizes, the sizes that follow from
 // that choice (LDS bytes, capacities, grid), and how a staged call lays out its scratch arena.  Pure functions of integers and no HIP
 // in here: tests/sim/match_plan_dump.cpp compiles this header with a plain host compiler and tests/test_match_plan_cpu.py and the
 // tests/test_*_batch_plan_cpu.py check both sides of every boundary.  A size rule lives here and nowhere else; the kernels are chosen by arguments alone (no environment).
@@ -260,13 +260,15 @@ inline DistinctBatchPlan distinct_batch_plan(int nsets) {
     return P;
 }
 
-// -------------------------------------------------------------- RANSAC over the rows of a pair (sslam_two_view_ransac*, two_view.hip; sslam_sim3_ransac*, sim3.hip)
+// -------------------------------------------------------------- RANSAC over the rows of a pair (sslam_two_view_ransac*, two_view.hip; sslam_sim3_ransac*, sim3.hip; sslam_pnp_ransac*, pnp.hip)
 // One wave per pair with the pair's compacted rows in dynamic LDS, rowBytes each, and fixedBytes behind them that do not grow with the capacity.  The capacity bound, beyond
 // which an entry point refuses before it launches, is whole steps of RANSAC_CAP_STEP rows: what one workgroup can have of the compute unit's LDS beside RANSAC_STATIC_LDS of
 // the kernel's static words, and no more than rowsMax bytes of rows.
 //   two-view  a row is (u1, v1, u2, v2); behind the rows the Jacobi workspace of the 64 lanes, TWO_VIEW_WS_DOUBLES doubles each (two_view_math.h: the upper triangle of a
 //             symmetric 9 x 9 and its eigenvectors); the rows stay within the 64 KB of the batch matchers' rows (BATCH_LDS_MAX): the workspace stays the larger part
 //   Sim3      a row is X1, X2, P1im1, P2im2, maxErr1, maxErr2 (sim3_math.h: s3::Row); nothing behind the rows, and they may take the whole LDS
+//   PnP       a row is Xw, pt, maxErr (pnp_math.h: pnp::Row); behind the rows the EPnP workspace of the 64 lanes, PNP_WS_DOUBLES doubles each (the upper triangle of the
+//             symmetric 12 x 12 and its eigenvectors), and one bit per row of the bound for Refine's set; the rows may take the rest of the LDS
 constexpr size_t LDS_PER_CU = 160 * 1024, RANSAC_STATIC_LDS = 256;
 constexpr int RANSAC_CAP_STEP = 1024, RANSAC_LANES = 64, TWO_VIEW_ROW_BYTES = 16, TWO_VIEW_WS_DOUBLES = 45 + 81, SIM3_ROW_BYTES = 48;
 constexpr size_t TWO_VIEW_WS_BYTES = sizeof(double) * TWO_VIEW_WS_DOUBLES * RANSAC_LANES;
@@ -285,6 +287,11 @@ inline RansacPlan ransac_plan(int rowBytes, size_t fixedBytes, int maxCap, int c
 }
 inline RansacPlan two_view_plan(int cap) { return ransac_plan(TWO_VIEW_ROW_BYTES, TWO_VIEW_WS_BYTES, TWO_VIEW_MAX_CAP, cap); }
 inline RansacPlan sim3_plan(int cap) { return ransac_plan(SIM3_ROW_BYTES, 0, SIM3_MAX_CAP, cap); }
+constexpr int PNP_ROW_BYTES = 24, PNP_WS_DOUBLES = 78 + 144, PNP_MASK_BYTES = 256;
+constexpr size_t PNP_WS_BYTES = sizeof(double) * PNP_WS_DOUBLES * RANSAC_LANES, PNP_FIXED_BYTES = PNP_WS_BYTES + PNP_MASK_BYTES;
+constexpr int PNP_MAX_CAP = ransac_max_cap(PNP_ROW_BYTES, PNP_FIXED_BYTES, LDS_PER_CU);
+static_assert(PNP_MAX_CAP == 2048 && PNP_MAX_CAP <= 8 * PNP_MASK_BYTES, "the capacity include/sslam_frontend.h promises (the c2 configuration extracts 2000 keypoints); one mask bit per row");
+inline RansacPlan pnp_plan(int cap) { return ransac_plan(PNP_ROW_BYTES, PNP_FIXED_BYTES, PNP_MAX_CAP, cap); }
 
 // arena of search_proj_core.  occ | q | qdesc go up in ONE copy (occ .. assigned), assigned | count come back in one (assigned .. count + 4);
 // only that head (.. count + 256) has a pinned mirror.  projK = list length of k_proj_topk (PROJ_K).

@@ -40,6 +40,10 @@ assert TWO_VIEW_RESULT_DTYPE.itemsize == 100
 SIM3_STATE_DTYPE = np.dtype([("its_done", "<i4"), ("best_inliers", "<i4"), ("best_it", "<i4"), ("n", "<i4"), ("max_its", "<i4"), ("found_it", "<i4"), ("n_inliers", "<i4"),
                              ("no_more", "<i4"), ("s12", "<f4"), ("R12", "<f4", (9,)), ("t12", "<f4", (3,))])      # sslam_sim3_state
 assert SIM3_STATE_DTYPE.itemsize == 84
+PNP_STATE_DTYPE = np.dtype([("its_done", "<i4"), ("best_inliers", "<i4"), ("best_it", "<i4"), ("refine_ok", "<i4"), ("n", "<i4"), ("min_inliers", "<i4"), ("max_its", "<i4"),
+                            ("found", "<i4"), ("found_it", "<i4"), ("n_inliers", "<i4"), ("no_more", "<i4"), ("pad_", "<i4"), ("best_R", "<f8", (9,)), ("best_t", "<f8", (3,)),
+                            ("Tcw", "<f4", (12,))])      # sslam_pnp_state
+assert PNP_STATE_DTYPE.itemsize == 192
 
 _lib = None
 
@@ -230,6 +234,44 @@ class Context:
                                                int((0 if sig is None else len(sig)) if nlevels is None else nlevels), _p(d_pairs), int(npairs), _p(d_matches12), int(bool(fix_scale)),
                                                C.c_double(probability), int(min_inliers), int(max_iterations), int(new_iterations), _p(d_sets), C.c_uint32(seed), _p(d_state),
                                                _p(d_inliers), C.c_void_p(stream or 0)))
+
+    def pnp_ransac(self, f_kp, f_K, kf_xw, kf_valid, level_sigma2, assigned, state=None, probability=0.99, min_inliers=10, max_iterations=300, epsilon=0.5, th2=5.991,
+                   new_iterations=5, sets=None, seed=0):
+        """One iterate(new_iterations, ..) of a PnPsolver (sslam_pnp_ransac) on one (keyframe, frame) pair: f_kp (KP_DTYPE: the frame's mvKeysUn), f_K = fx fy cx cy, kf_xw
+        float32 [nkf, 3] (the world positions of the keyframe's map points), kf_valid uint8 [nkf] or None, assigned int32 [nf] (what SearchByBoW wrote), state a
+        PNP_STATE_DTYPE record to resume (None: a new solver), sets None (the library draws) or [nsets, 4] indices into the correspondence list.  Returns (state: a
+        PNP_STATE_DTYPE record, inliers: uint8 [nf])"""
+        kp = np.ascontiguousarray(f_kp, KP_DTYPE)
+        xw = np.ascontiguousarray(kf_xw, np.float32).reshape(-1, 3)
+        v = None if kf_valid is None else np.ascontiguousarray(kf_valid, np.uint8)
+        a = np.ascontiguousarray(assigned, np.int32)
+        assert len(a) == len(kp) and (v is None or len(v) == len(xw))
+        K = np.ascontiguousarray(f_K, np.float32).reshape(4)
+        sig = np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        nsets = 0
+        if sets is not None:
+            sets = np.ascontiguousarray(sets, np.int32).reshape(-1, 4)
+            nsets = len(sets)
+        st = np.zeros(1, PNP_STATE_DTYPE)
+        if state is not None:
+            st[0] = state
+        inl = np.zeros(len(kp), np.uint8)
+        _chk(lib().sslam_pnp_ransac(self.h, _p(kp), len(kp), _p(K), _p(xw), _p(v), len(xw), _p(sig), len(sig), _p(a), C.c_double(probability), int(min_inliers),
+                                    int(max_iterations), C.c_float(epsilon), C.c_float(th2), int(new_iterations), _p(sets), int(nsets), C.c_uint32(seed), _p(st), _p(inl)))
+        return st[0], inl
+
+    def pnp_ransac_batch_dev(self, d_f_kp, d_nf, cap, nframes, d_f_K, d_kf_xw, d_kf_valid, d_nkf, kfcap, nkeyframes, level_sigma2, d_pair_kf, d_pair_f, npairs, d_assigned,
+                             d_state, d_inliers, probability=0.99, min_inliers=10, max_iterations=300, epsilon=0.5, th2=5.991, new_iterations=5, d_sets=None, nsets=0, seed=0,
+                             stream=None, nlevels=None):
+        """sslam_pnp_ransac_batch_dev on device tensors / pointers in the layout of search_by_bow_batch_dev: frame slot f owns rows [f*cap, (f+1)*cap) of d_f_kp and
+        d_f_K[4f:4f+4], keyframe slot k rows [k*kfcap, (k+1)*kfcap) of d_kf_xw (float32, 3 per row) and d_kf_valid (None: all valid), level_sigma2 is a HOST float32 array,
+        pair p owns rows [p*cap, (p+1)*cap) of d_assigned and d_inliers (uint8) and the PNP_STATE_DTYPE record p of d_state (in/out, 192 bytes each), d_sets is None or
+        [npairs, nsets, 4] int32; enqueues on `stream` (None: the context's) and returns without synchronising"""
+        sig = None if level_sigma2 is None else np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        _chk(lib().sslam_pnp_ransac_batch_dev(self.h, _p(d_f_kp), _p(d_nf), int(cap), int(nframes), _p(d_f_K), _p(d_kf_xw), _p(d_kf_valid), _p(d_nkf), int(kfcap), int(nkeyframes),
+                                              _p(sig), int((0 if sig is None else len(sig)) if nlevels is None else nlevels), _p(d_pair_kf), _p(d_pair_f), int(npairs),
+                                              _p(d_assigned), C.c_double(probability), int(min_inliers), int(max_iterations), C.c_float(epsilon), C.c_float(th2),
+                                              int(new_iterations), _p(d_sets), int(nsets), C.c_uint32(seed), _p(d_state), _p(d_inliers), C.c_void_p(stream or 0)))
 
     def search_by_projection(self, kind, mode, feats, desc, queries, qdesc, occupied=None, uright=None, nnratio=0.8, th_dist=100,
                              check_orientation=True, bounds=(0.0, 640.0, 0.0, 480.0)):
