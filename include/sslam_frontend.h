@@ -971,8 +971,15 @@ int sslam_shard_chunk_count(int n, int ngpu, int chunk, int gpu);
 /* ---- Stage taps (diagnostics).  They read back intermediate results of the LAST extraction of a handle so that a maintainer who pins this
  * library against the reference built with OpenCV 3.4 can compare stage by stage (pyramid level bytes, FAST candidates, blurred patches: sslam_orb_debug_*, declared with
  * the extractor above; LSD segments before the top-N cut: below).  Synchronous; nothing on the product path calls them. */
-/* Stage tap: all LSD segments (x1,y1,x2,y2 float) of frame `frame` of the last batch, before top-N. */
+/* Stage tap: all LSD segments (x1,y1,x2,y2 float) of frame `frame` of the last batch, before top-N.  On a handle with sslam_lines_set_topn_only on, and a call of the
+ * one-launch NFA form (2 048 frames or more), the tap returns the accepted segments among the candidates that were VALIDATED, in emission order: every segment that can
+ * be among the max_lines output lines is in it, shorter ones may be missing. */
 int sslam_lines_debug_segments(sslam_lines* ln, int frame, float* seg_out, int cap, int* n_out);
+/* The caller's contract "only the max_lines best lines leave this handle": on != 0 states that nothing reads the segments before the top-N cut (the tap above), so the
+ * NFA stage may stop validating candidate rectangles once none of the remaining ones can reach the output (a rectangle's response is known before validation up to a
+ * small margin: csrc/nfa_topn.h).  Key lines, descriptors, line equations and counts are bit for bit those of the default.  Not a tuning knob: the default is 0 because the
+ * tap exists.  Returns the previous value (0 for a NULL handle). */
+int sslam_lines_set_topn_only(sslam_lines* ln, int on);
 /* Stage clocks of the sequential LSD core for frame `frame` of the last call (grow, rect, refine, radius reduction, total, ...): zeros unless
  * the library was built with -DSSLAM_LSD_CYCLES (tools/lsd_cycles.py). */
 int sslam_lines_debug_cycles(sslam_lines* ln, int frame, long long* out8);

@@ -39,6 +39,7 @@ using namespace sslam;
 extern "C" int sslam_orb_batch_status_dev(sslam_orb* orb, int cap, int32_t* d_status4, void* stream);
 extern "C" int sslam_lines_batch_status_dev(sslam_lines* lines, int cap, int32_t* d_status4, void* stream);
 extern "C" int sslam_lines_set_core_event(sslam_lines* lines, void* hip_event);
+extern "C" int sslam_lines_set_topn_only(sslam_lines* lines, int on);
 extern "C" int sslam_lines_core_guest_form(sslam_lines* lines, int nframes);
 extern "C" int sslam_orb_set_gate_event(sslam_orb* orb, void* hip_event);
 
@@ -247,6 +248,8 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
     };
     const bool twoStreams = lines != nullptr;
     if (lines) (void)sslam_lines_set_core_event(lines, twoStreams ? (void*)B.evCore : nullptr);
+    // what leaves this call per frame is the lcap output lines and nothing before the top-N cut: for its duration the NFA stage may validate no more candidates than that takes
+    const int topnBefore = lines ? sslam_lines_set_topn_only(lines, 1) : 0;
     int k = 0;
     for (int f0 = 0; f0 < n && rc == SSLAM_OK; f0 += C, ++k) {
         Slot& s = slot[k & 1];
@@ -349,7 +352,7 @@ int batch_impl(const char* fn, sslam_orb* orb, sslam_lines* lines, const uint8_t
     if (rc == SSLAM_OK) rc = drain((k + 1) & 1);
     gStage.wait(); drained(0); drained(1);           // (also on the error paths: no task may outlive the caller's buffers)
     (void)hipStreamSynchronize(cp); (void)hipStreamSynchronize(cpOut); (void)hipStreamSynchronize(stL); (void)hipStreamSynchronize(stP);
-    if (lines) (void)sslam_lines_set_core_event(lines, nullptr);
+    if (lines) { (void)sslam_lines_set_core_event(lines, nullptr); (void)sslam_lines_set_topn_only(lines, topnBefore); }
     (void)sslam_orb_set_gate_event(orb, nullptr);
     for (int i = 0; i < 2; ++i) slot[i].count = 0;
     return rc != SSLAM_OK ? rc : firstStatus;

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void k_keylines(uint8_t* __restrict__ ws, LsdP
         int basePos = 0;
         for (int i0 = 0; i0 < nCand; i0 += 256) {
             const int i = i0 + tid;
-            const bool ok = i < nCand && flag[i] != 0;
+            const bool ok = i < nCand && flag[i] == topn::FLAG_ACCEPTED;      // (rejected, or left out by the stage's top-N form as not needed: nfa_topn.h)
             const float4 v = ok ? seg[i] : make_float4(0, 0, 0, 0);
             const unsigned long long m = __ballot(ok);
             if (lane == 0) wcnt[wv] = __popcll(m);
@@ -66,30 +66,25 @@ __global__ __launch_bounds__(256) void k_keylines(uint8_t* __restrict__ ws, LsdP
     for (int i = tid; i < n; i += 256) {
         float4 s = seg[i];
         float e0 = s.x, e1 = s.y, e2 = s.z, e3 = s.w;
-        const float W = (float)P.w, H = (float)P.h;           // checkLineExtremes
-        if (e0 < 0) e0 = 0; if (e0 >= W) e0 = W - 1.0f;
-        if (e2 < 0) e2 = 0; if (e2 >= W) e2 = W - 1.0f;
-        if (e1 < 0) e1 = 0; if (e1 >= H) e1 = H - 1.0f;
-        if (e3 < 0) e3 = 0; if (e3 >= H) e3 = H - 1.0f;
+        topn::check_line_extremes(e0, e1, e2, e3, P.w, P.h);      // (length and response: nfa_topn.h, the instructions the NFA stage's ranking predicts them with)
         sslam_keyline k;
         k.startPointX = e0; k.startPointY = e1; k.endPointX = e2; k.endPointY = e3;
         k.sPointInOctaveX = e0; k.sPointInOctaveY = e1; k.ePointInOctaveX = e2; k.ePointInOctaveY = e3;
-        const double ddx = (double)__fsub_rn(e0, e2), ddy = (double)__fsub_rn(e1, e3);
-        k.lineLength = (float)sqrt(ddx * ddx + ddy * ddy);
+        k.lineLength = topn::line_length(e0, e1, e2, e3);
         const int ax = cv_roundf(e0), ay = cv_roundf(e1), bx = cv_roundf(e2), by = cv_roundf(e3);
         k.numOfPixels = max(abs(bx - ax), abs(by - ay)) + 1;
         k.angle = (float)atan2((double)__fsub_rn(e3, e1), (double)__fsub_rn(e2, e0));     // D5
         k.class_id = i; k.octave = 0;
         k.size = __fmul_rn(__fsub_rn(e2, e0), __fsub_rn(e3, e1));
-        k.response = __fdiv_rn(k.lineLength, (float)max(P.w, P.h));
+        k.response = topn::response_of_length(k.lineLength, P.w, P.h);
         k.pt_x = __fdiv_rn(__fadd_rn(e2, e0), 2.f); k.pt_y = __fdiv_rn(__fadd_rn(e3, e1), 2.f);
         klw[i] = k;
-        const unsigned long long key = ((unsigned long long)(~__float_as_uint(k.response)) << 32) | (unsigned)i;   // response >= 0: descending response, ascending index (D3 stable)
+        const unsigned long long key = topn::rank_key(k.response, i);   // response >= 0: descending response, ascending index (D3 stable)
         if (inLds) keysL[i] = key; else keysG[i] = key;
     }
     __syncthreads();
     int nOut = n;
-    const bool doSort = n > maxLines;
+    const bool doSort = n > maxLines;      // (the stage's top-N form leaves candidates out only with MORE than maxLines accepted among the validated ones: the same decision as on all of them)
     if (doSort) {
         int P2 = 1; while (P2 < n) P2 <<= 1;
         if (inLds) {

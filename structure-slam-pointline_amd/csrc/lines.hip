@@ -15,6 +15,7 @@
 //   * all order-dependent fp64 sums are accumulated in the reference's order, so the segments match the CPU oracle bit for bit.
 // This file: the per-frame workspace plan and the C-ABI entry points (sslam_lines_*).
 #include "common.h"
+#include "nfa_topn.h"
 #include <cmath>
 #include <cstdlib>
 #include <cfloat>
@@ -22,7 +23,7 @@
 
 namespace sslam { int launch_nfa_stream(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, uint8_t* clArea, size_t clFrameBytes,
                                         size_t stageOff, int nframes, int waves, long long spinTicks, bool besideCore); }      // lines_nfa.hip
-namespace sslam { int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes, int* form3); }      // lines_nfa.hip
+namespace sslam { int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes, int topnMaxLines, int* form3); }      // lines_nfa.hip
 
 using namespace sslam;
 
@@ -38,7 +39,7 @@ namespace {
 __global__ void k_zero_misc(uint8_t* ws, LsdPlan P) {
     Misc* m = (Misc*)(ws + (size_t)blockIdx.x * P.frameBytes + P.offMisc);
     if (threadIdx.x == 0) {
-        m->maxS = 0; m->nDefined = 0; m->nSeg = 0; m->nCand = 0; m->nKl = 0; m->overflow = 0; m->claim = 0;
+        m->maxS = 0; m->nDefined = 0; m->nSeg = 0; m->nCand = 0; m->nKl = 0; m->overflow = 0; m->claim = 0; m->topn = 0;
 #if defined(SSLAM_LSD_DRIFT_VERIFY) || defined(SSLAM_LSD_CYCLES)
         m->cyc[5] = 0; m->cyc[6] = 0; m->cyc[7] = 0;      // shortcut decisions that disagree with the exact test; (shortcuts << 32) + decisions
 #endif
@@ -81,6 +82,7 @@ struct sslam_lines {
     bool constsUploaded = false;
     int blurVariant = 0;            // sslam_lines_set_blur_variant
     int nfaVariant = 1, lbdBitOrder = 1, lsdResize = 0;      // sslam_lines_set_nfa_variant / _lbd_bit_order / _resize_variant (decisions D11, D12, D7): D11 and D12 default to the OpenCV-as-recalled forms since round 5
+    int topnOnly = 0;               // sslam_lines_set_topn_only: the caller takes nothing but the maxLines output lines (the NFA stage may leave candidates out: nfa_topn.h)
     int seedOrder = 0;              // sslam_lines_set_seed_order (decision D2): 1 = the seeds are ordered by the host's std::sort
     int sMin = 0;                   // smallest |g|^2 of a defined pixel (k_grad_smin, with the gradient table)
     bool fusedGeometry = false;     // lines_build_plan: the plan admits k_lsd_grad_fused
@@ -572,7 +574,7 @@ static int lines_tail(const LinesCall& c, CoreForm form, size_t nfaStageOff, Sid
     if (form == CoreForm::ClusterStream) {      // what the concurrent consumers left (nothing, unless they gave up waiting): the same kernel behind both, everything published, no waiting
         side.join();
         if ((rc = sslam::launch_nfa_stream(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), L->clFrame, nfaStageOff, nframes, 16, 0, false))) return rc;
-    } else if ((rc = sslam::launch_nfa_stage(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), nframes, L->lastForms + 4))) return rc;
+    } else if ((rc = sslam::launch_nfa_stage(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), nframes, L->topnOnly ? L->maxLines : 0, L->lastForms + 4))) return rc;
     lines_describe(c, side, d_kl, d_ldesc, d_linefn, d_counts, cap);
     return SSLAM_OK;
 }
@@ -720,6 +722,14 @@ extern "C" int sslam_lines_debug_segments(sslam_lines* L, int frame, float* seg_
     int n = std::min(m.nSeg, cap);
     if (n > 0 && seg_out) SSLAM_HIP(hipMemcpy(seg_out, base + P.offSeg, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost));
     return SSLAM_OK;
+}
+
+extern "C" int sslam_lines_set_topn_only(sslam_lines* L, int on) {
+    if (!L) return 0;
+    std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
+    const int old = L->topnOnly;
+    L->topnOnly = on ? 1 : 0;
+    return old;
 }
 
 extern "C" int sslam_lines_set_core_event(sslam_lines* L, void* hip_event) {

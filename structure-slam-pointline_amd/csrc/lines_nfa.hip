@@ -6,6 +6,7 @@
 // 12 288 frames.  The sequential core in lines.hip is the other way round (78.9 -> 79.4 ms without the hoisting), hence two units
 // (docs/history/DESIGN_rounds_1-4.md 5g).  The kernels are launched from here; lines.hip calls sslam::launch_nfa_stage.
 #include "common.h"
+#include "nfa_topn.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -33,7 +34,9 @@ NfaKnobs nfa_knobs() {
 namespace sslam {
 
 // form3 (unless null): what was chosen -- {1: the 18 launches, 2: k_nfa_all}, evaluating waves per frame, counting waves per frame (sslam_testing_lines_last_forms)
-int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes, int* form3) {
+// topnMaxLines > 0 (sslam_lines_set_topn_only): only that many lines leave a frame, and the one-launch form validates no more candidates than that takes (k_nfa_topn,
+// lsd_nfa.h); the 18 launches validate everything as before.
+int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes, int topnMaxLines, int* form3) {
     if (planBytes != sizeof(LsdPlan)) { set_error("launch_nfa_stage: plan layout mismatch between translation units"); return SSLAM_ERR_INVALID; }
     LsdPlan P; memcpy(&P, plan, sizeof(P));
     const NfaKnobs K = nfa_knobs();
@@ -45,7 +48,10 @@ int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* pl
     // What helped instead: 128 counting and 32 evaluating waves per frame (6.09 / 7.16).
     const bool nfaFused = K.fused == 2 || (K.fused != 0 && countWaves == 1 && evalWaves == 1);
     if (form3) { form3[0] = nfaFused ? 2 : 1; form3[1] = nfaFused ? 1 : evalWaves; form3[2] = nfaFused ? 1 : countWaves; }
-    if (nfaFused) {
+    if (nfaFused && topnMaxLines > 0) {
+        sslam::ProfScope _ps(ctx, "k_nfa_all", st);
+        hipLaunchKernelGGL(k_nfa_topn<768>, dim3(nframes), dim3(64), 0, st, ws, P, lgam, topnMaxLines);
+    } else if (nfaFused) {
         sslam::ProfScope _ps(ctx, "k_nfa_all", st);
         hipLaunchKernelGGL(k_nfa_all<768>, dim3(nframes), dim3(64), 0, st, ws, P, lgam);
     } else {

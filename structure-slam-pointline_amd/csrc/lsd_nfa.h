@@ -770,6 +770,9 @@ __global__ __launch_bounds__(256) void k_nfa_accept(uint8_t* __restrict__ ws, Ls
     nfa_accept_body(ws + (size_t)blockIdx.y * P.frameBytes, P, stage, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
 
+// the output segment of a rectangle record (flsd's conversion, nfa_topn.h: also what the top-N form's ranking predicts the response from)
+__device__ __forceinline__ float4 rect_segment(const double* o) { return make_float4(topn::seg_coord(o[0]), topn::seg_coord(o[1]), topn::seg_coord(o[2]), topn::seg_coord(o[3])); }
+
 __device__ __forceinline__ void nfa_finish_range(uint8_t* __restrict__ base, const LsdPlan& P, int c0, int c1, int tid, int nthreads) {
     const double* rects = (const double*)(base + P.offCand);
     const NfaState* st = (const NfaState*)(base + P.offNfa);
@@ -777,12 +780,8 @@ __device__ __forceinline__ void nfa_finish_range(uint8_t* __restrict__ base, con
     int* flag = (int*)(base + P.offFlag);
     for (int c = c0 + tid; c < c1; c += nthreads) {
         const bool ok = st[c].logNfa > 0.0;
-        flag[c] = ok ? 1 : 0;
-        if (ok) {
-            const double* o = rects + (size_t)c * 12;
-            const double SCALE = 0.8;
-            seg[c] = make_float4((float)((o[0] + 0.5) / SCALE), (float)((o[1] + 0.5) / SCALE), (float)((o[2] + 0.5) / SCALE), (float)((o[3] + 0.5) / SCALE));
-        }
+        flag[c] = ok ? topn::FLAG_ACCEPTED : topn::FLAG_REJECTED;
+        if (ok) seg[c] = rect_segment(rects + (size_t)c * 12);
     }
 }
 
@@ -834,6 +833,138 @@ __global__ __launch_bounds__(64, SSLAM_NFA_ALL_MINWAVES) void k_nfa_all(uint8_t*
     __shared__ NfaLdsT<CH> L;
     const int b = xcd_mix_frame(blockIdx.x, gridDim.x);
     nfa_all_body<CH>(ws + (size_t)b * P.frameBytes, P, lgam, 0, 1, threadIdx.x, L);
+}
+
+// ------------------------------------------------------------------ the top-N form (nfa_topn.h; sslam_lines_set_topn_only): k_nfa_topn in place of k_nfa_all
+// Only the maxLines lines of the largest response leave the extractor, and a candidate's response is known before it is validated up to a small margin (exactly, when its
+// first evaluation accepts).  The frame's wave first orders the candidates by that upper bound u, then runs the stage -- the same bodies -- on slices of the ranked list
+// and stops when no candidate that is left can reach the output.
+//   * Ranked copy: the bodies address a rectangle and its NfaState by ONE index, so the ranked list is a copy of the rectangle records at the indices
+//     [NFA_RANK_BASE, NFA_RANK_BASE + nCand) of the same arrays (free: a ranked frame has at most NFA_RANK_CAP candidates, MAX_SEG is eight times the base).  Beside it, at
+//     the same indices: the emission index in the flag array, {u, final response or -1} in the segment array.  Flags and segments are written at the EMISSION index as in
+//     every other form, so k_keylines' compaction keeps emission order (the stable tie-break) and nothing behind the stage knows about the ranking.
+//   * The ranking is the wave's own, in its LDS (one 64-bit key per candidate, NFA_RANK_CAP of them in the 7.5 KB): a candidate's position is the number of smaller keys,
+//     counted against broadcast reads -- n^2 / 64 compares per lane, some ten thousand instructions for the 420 candidates of a bench frame, where the stage itself runs
+//     millions.  (As a kernel of its own in front of the stage -- 256 threads, bitonic sort -- the ranking cost 1.3 ms per 12 288 frames on the line stream: profiles/nfa_topn.txt.)
+//   * A frame that is not ranked (topn::ranks: at most maxLines candidates, more than NFA_RANK_CAP, an image beyond topn::MAX_SIDE) is validated in full, in place.
+constexpr int NFA_RANK_BASE = 1024, NFA_RANK_CAP = 960;
+static_assert(NFA_RANK_BASE + NFA_RANK_CAP <= MAX_SEG && NFA_RANK_CAP <= NFA_RANK_BASE, "the ranked copy lies behind the emitted rectangles");
+
+__device__ __forceinline__ void nfa_topn_rank(uint8_t* __restrict__ base, const LsdPlan& P, int n, int lane, unsigned long long* __restrict__ keys) {
+    double* rects = (double*)(base + P.offCand);
+    float4* seg = (float4*)(base + P.offSeg);
+    int* flag = (int*)(base + P.offFlag);
+    for (int i = lane; i < n; i += 64) {
+        const double* o = rects + (size_t)i * 12;
+        const float u = topn::upper(topn::rect_response(o[0], o[1], o[2], o[3], P.w, P.h), topn::margin(o[0], o[1], o[2], o[3], P.w, P.h));
+        keys[i] = topn::rank_key(u, i);
+    }
+    nfa_wave_sync();
+    for (int i = lane; i < n; i += 64) {
+        const unsigned long long k = keys[i];
+        int pos = 0;
+        for (int j = 0; j < n; ++j) pos += keys[j] < k ? 1 : 0;          // (the keys are distinct: the emission index is part of them)
+        flag[NFA_RANK_BASE + pos] = i;
+        seg[NFA_RANK_BASE + pos] = make_float4(__uint_as_float(~(unsigned)(k >> 32)), -1.f, 0.f, 0.f);
+        const double* o = rects + (size_t)i * 12;
+        double* r = rects + (size_t)(NFA_RANK_BASE + pos) * 12;
+#pragma unroll
+        for (int q = 0; q < 12; ++q) r[q] = o[q];
+    }
+    __syncthreads();
+}
+
+// the slice's verdicts: flag and segment at the emission index, the final response beside u (what tau is taken from)
+__device__ __forceinline__ void nfa_topn_finish_range(uint8_t* __restrict__ base, const LsdPlan& P, int c0, int c1, int lane) {
+    const double* rects = (const double*)(base + P.offCand);
+    const NfaState* st = (const NfaState*)(base + P.offNfa);
+    float4* seg = (float4*)(base + P.offSeg);
+    int* flag = (int*)(base + P.offFlag);
+    for (int c = c0 + lane; c < c1; c += 64) {
+        const bool ok = st[c].logNfa > 0.0;
+        const int e = flag[c];
+        flag[e] = ok ? topn::FLAG_ACCEPTED : topn::FLAG_REJECTED;
+        if (ok) {
+            const float4 s = rect_segment(rects + (size_t)c * 12);
+            seg[e] = s;
+            seg[c].y = topn::seg_response(s.x, s.y, s.z, s.w, P.w, P.h);
+        }
+    }
+}
+
+// Where the next slice ends (ranked positions; s1 = where the last one ended, n = the frame's candidates).  words: the wave's LDS, free between two slices.
+// tau = the maxLines-th largest final response accepted in [0, s1): the largest t with at least maxLines values >= t, found by bisection on the bit patterns (responses are
+// >= 0: the patterns order as the floats; stored + 1, 0 = not accepted).  The candidates behind s1 that tau does not exclude are a prefix: they are ordered by u.
+__device__ __forceinline__ int nfa_topn_next(uint8_t* __restrict__ base, const LsdPlan& P, int s1, int n, int maxLines, int lane, unsigned* __restrict__ words) {
+    const float4* rk = (const float4*)(base + P.offSeg) + NFA_RANK_BASE;
+    int nAcc = 0;
+    for (int i = lane; i < s1; i += 64) {
+        const float r = rk[i].y;
+        words[i] = r >= 0.f ? __float_as_uint(r) + 1u : 0u;
+        nAcc += r >= 0.f ? 1 : 0;
+    }
+    nAcc = __builtin_amdgcn_readfirstlane(wave_sum_dpp(nAcc));
+    nfa_wave_sync();
+    int s2;
+    if (nAcc <= maxLines) s2 = min(n, s1 + topn::slice_size(maxLines + 1 - nAcc));      // not yet MORE than maxLines accepted: nothing can be excluded (nfa_topn.h)
+    else {
+        unsigned lo = 1u, hi = 0x7F800001u;
+        while (lo < hi) {
+            const unsigned mid = lo + ((hi - lo + 1u) >> 1);
+            int cnt = 0;
+            for (int i = lane; i < s1; i += 64) cnt += words[i] >= mid ? 1 : 0;
+            cnt = __builtin_amdgcn_readfirstlane(wave_sum_dpp(cnt));
+            if (cnt >= maxLines) lo = mid; else hi = mid - 1u;
+        }
+        const float tau = __uint_as_float(lo - 1u);
+        int more = 0;
+        for (int i = s1 + lane; i < n; i += 64) more += topn::excluded(rk[i].x, tau) ? 0 : 1;
+        s2 = s1 + __builtin_amdgcn_readfirstlane(wave_sum_dpp(more));
+    }
+    nfa_wave_sync();
+    return s2;
+}
+
+template <int CH>
+__global__ __launch_bounds__(64, SSLAM_NFA_ALL_MINWAVES) void k_nfa_topn(uint8_t* __restrict__ ws, LsdPlan P, const double* __restrict__ lgam, int maxLines) {
+    __shared__ NfaLdsT<CH> L;
+    static_assert(sizeof(NfaLdsT<CH>) >= sizeof(unsigned long long) * NFA_RANK_CAP, "the ranking keeps one key per candidate in the wave's LDS (nfa_topn_next: one word)");
+    const int b = xcd_mix_frame(blockIdx.x, gridDim.x);
+    uint8_t* base = ws + (size_t)b * P.frameBytes;
+    int lane = threadIdx.x;
+    Misc* misc = (Misc*)(base + P.offMisc);
+    const int n = __builtin_amdgcn_readfirstlane(misc->nCand);
+    const bool ranked = topn::ranks(n, maxLines, NFA_RANK_CAP, P.w, P.h);
+    if (ranked) nfa_topn_rank(base, P, n, lane, (unsigned long long*)&L);
+    int s0 = 0, s1 = ranked ? min(n, topn::slice_size(maxLines + 1)) : n;
+    const int cb = ranked ? NFA_RANK_BASE : 0;
+#pragma unroll 1
+    while (s1 > s0) {
+#pragma unroll 1
+        for (int it = -1; it <= 4; ++it) {
+#define NFA_OPAQUE() asm volatile("" : "+s"(base), "+s"(lgam), "+v"(lane))       // (as in nfa_all_body: nothing of a body's address arithmetic may be hoisted across the chain)
+            NFA_OPAQUE();
+            if (it != 0) { nfa_count_range<CH>(base, P, it < 0 ? 0 : it, cb + s0, cb + s1, lane, L.c); __syncthreads(); }
+            NFA_OPAQUE();
+            nfa_eval_range<CH>(base, P, it, lgam, cb + s0, cb + s1, lane, L.items);
+            __syncthreads();
+            NFA_OPAQUE();
+            nfa_accept_range(base, P, it, cb + s0, cb + s1, lane, 64);
+            __syncthreads();
+        }
+        NFA_OPAQUE();
+#undef NFA_OPAQUE
+        if (!ranked) { nfa_finish_range(base, P, s0, s1, lane, 64); break; }
+        nfa_topn_finish_range(base, P, cb + s0, cb + s1, lane);
+        __syncthreads();
+        s0 = s1;
+        s1 = nfa_topn_next(base, P, s1, n, maxLines, lane, (unsigned*)&L);
+    }
+    if (ranked) {
+        int* flag = (int*)(base + P.offFlag);
+        for (int i = s1 + lane; i < n; i += 64) flag[flag[NFA_RANK_BASE + i]] = topn::FLAG_NOT_NEEDED;
+        if (lane == 0) misc->topn = n - s1;
+    }
 }
 
 

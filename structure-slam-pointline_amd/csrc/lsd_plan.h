@@ -61,7 +61,7 @@ struct Misc {                 // per-frame scalars
     int nKl;
     int overflow;
     int claim;                // frame 0 only: frames handed out so far to the persistent workgroups of the sequential core (k_lsd_regions)
-    int pad_;
+    int topn;                 // the NFA stage's top-N form (nfa_topn.h, k_nfa_topn): candidates it left out as not needed (statistics; > 0 only with more than maxLines accepted).  0 in every other form
     long long cyc[8];         // master-wave cycle breakdown (debug): grow, rect, refine, nfa count, nfa math, seed scan
 };
 

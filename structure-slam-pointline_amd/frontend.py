@@ -825,6 +825,11 @@ class LineExtractor:
         """decision D2: 0 = raster order inside a gradient bin (default, on the device); 1 = the host's std::sort (sslam_lines_set_seed_order)"""
         _chk(lib().sslam_lines_set_seed_order(self.h, int(variant)))
 
+    def set_topn_only(self, on):
+        """sslam_lines_set_topn_only: the caller takes nothing but the max_lines output lines (the NFA stage may then leave candidates out; debug_segments returns the
+        validated ones) -> the previous value"""
+        return int(lib().sslam_lines_set_topn_only(self.h, int(bool(on))))
+
     def set_core_event(self, hip_event):
         """hipEvent_t handle (int) recorded right before the sequential LSD core of every following batch call; 0 / None clears it"""
         _chk(lib().sslam_lines_set_core_event(self.h, C.c_void_p(int(hip_event or 0))))

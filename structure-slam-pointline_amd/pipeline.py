@@ -25,6 +25,9 @@ class FrontendBatch:
         self.with_lines, self.with_match = with_lines, with_match
         self.orb = fe.OrbExtractor(ctx, nfeatures, 1.2, 8, 20, 7)
         self.lines = fe.LineExtractor(ctx, max_lines) if with_lines else None
+        if self.lines is not None:
+            self.lines.set_topn_only(True)      # nothing here reads the segments before the top-N cut: the NFA stage validates no more candidates than the cut takes
+
         self.cap, self.lcap = self.orb.cap, max_lines
         B, cap, lcap = batch, self.cap, self.lcap
         z = lambda *s, dt=torch.uint8: torch.zeros(*s, dtype=dt, device=self.dev)

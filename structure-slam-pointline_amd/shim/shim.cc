@@ -29,6 +29,7 @@ struct Global {
         std::lock_guard<std::mutex> lk(mu);
         if (!lines) {
             if (sslam_lines_create(c, maxLines, &lines) != SSLAM_OK) throw std::runtime_error(sslam_last_error());
+            (void)sslam_lines_set_topn_only(lines, 1);      // ExtractLineSegment hands out the nfeatures best lines and nothing before that cut
             // the other leaves of the line path whose upstream form is a stated decision (include/sslam_frontend.h): one environment variable each, so
             // that the day `make -C oracle/ref_pin pin` first runs against a real OpenCV no recompilation stands between a maintainer and the matching variant
             struct { const char* env; int (*set)(sslam_lines*, int); } knobs[] = {
