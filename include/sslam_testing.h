@@ -102,6 +102,25 @@ int sslam_testing_lines_prologue(sslam_lines* ln, const uint8_t* gray, int w, in
  * would) if the handle has none. */
 int sslam_testing_lines_grad_table(sslam_lines* ln, float* tab_out, int32_t* smin_out);
 
+/* The NFA stage -- rect_nfa / rect_improve of LSD_REFINE_ADV (OpenCV imgproc lsd.cpp, reached from src/ExtractLineSegment.cpp:38-40) as the 18 launches, k_nfa_all or
+ * k_nfa_topn (csrc/lsd_nfa.h, csrc/nfa_topn.h) -- on candidate rectangles the CALLER supplies in place of the sequential core's, so that a test can drive the stage, and
+ * above all the top-N form's ranking, slices and stopping rule, at their own edges and compare every flag.  `nframes` gray images of one size on the host, passed as
+ * sslam_testing_lines_tail takes them; rects[nframes][nmax][12] = the RectD records (x1, y1, x2, y2, width, x, y, theta, dx, dy, prec, p in scaled pixels) in emission order;
+ * ncand[nframes] <= min(nmax, 8192); topn_max_lines = what sslam_lines_set_topn_only hands the stage (0: the full validation).  Before any launch, SSLAM_ERR_INVALID for a record
+ * the core could not have emitted -- the kernels are only ever given their normal value range --: every value finite; the centre inside the scaled image
+ * [0, sw - 1] x [0, sh - 1] and both end points within `width` of it (region2rect projects the region's pixels onto the axis: the core's own end points lie up to a few pixels
+ * outside on ordinary frames, and the counters clip every row and column to the image); 0 < width <= max(sw, sh); |dx^2 + dy^2 - 1| <= 1e-9; prec and p equal to the plan's.  The call runs lines_prepare, k_zero_misc and
+ * lines_prologue() as sslam_lines_extract_batch_dev does (the T plane is the product's own), fills every frame's flag, segment and NfaState regions with the byte 0xA5, writes
+ * the records and Misc::nCand where the core leaves them and calls sslam::launch_nfa_stage with topn_max_lines, nothing else: the form is chosen as on the product path by
+ * SSLAM_NFA_FUSED and the number of frames, and recorded for sslam_testing_lines_last_forms (words 2 .. 6; the core's words stay -1).  The streaming form takes its records
+ * from a cluster slot and is not reached from here.  Outputs on the host: flags_out[nframes][nmax] and segs_out[nframes][nmax][4] at EMISSION indices (flag 0 rejected,
+ * 1 accepted with its segment written, 2 left out by the top-N form), topn_out[nframes] = Misc::topn.  Rows at or past ncand still hold the fill, and so does the segment
+ * of every row that is not flagged 1 -- with ONE exception, documented rather than refused (a call may mix ranked frames with frames of more than 1024 rectangles): in a
+ * frame that k_nfa_topn ranks (topn_max_lines < ncand <= 960) the rows from 1024 (NFA_RANK_BASE) on are the kernel's ranked copy and unspecified; only [0, 1024) is
+ * meaningful there.  The handle must have been created by THIS library. */
+int sslam_testing_lines_nfa(sslam_lines* ln, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, const double* rects, const int32_t* ncand,
+                            int nmax, int topn_max_lines, int32_t* flags_out, float* segs_out, int32_t* topn_out);
+
 /* The ORB tail -- k_octree (DistributeOctTree, src/ORBextractor.cc:539-763) and k_describe (IC_Angle, the 7x7 blur, computeOrbDescriptor and the KeyPoint fill, :77-147,
  * :835-847, :1085-1101) -- on FAST candidates the CALLER supplies in place of k_fast_cells', so that a test can drive the two kernels at their own edges.  `nframes` gray
  * images of one size on the host (row pitch `stride`, `image_stride` bytes from frame to frame), uploaded the way sslam_orb_extract uploads its frame;

@@ -900,6 +900,74 @@ extern "C" int sslam_testing_lines_grad_table(sslam_lines* L, float* tab_out, in
     return SSLAM_OK;
 }
 
+// The NFA stage on rectangles the caller supplies (include/sslam_testing.h): the upload of sslam_testing_lines_tail, then lines_prepare, k_zero_misc and lines_prologue() --
+// the product path's functions: the T plane is the product's own --, the records and Misc::nCand written where the core leaves them, and sslam::launch_nfa_stage, the one
+// function lines_tail calls.  The core does not run (no pixel of T carries the used bit, which the stage masks off anyway), nor does anything behind the stage.
+extern "C" int sslam_testing_lines_nfa(sslam_lines* L, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, const double* rects,
+                                       const int32_t* ncand, int nmax, int topn_max_lines, int32_t* flags_out, float* segs_out, int32_t* topn_out) {
+    if (!L || !gray || !ncand || !topn_out || w <= 0 || h <= 0 || nframes <= 0 || nmax < 0 || nmax > MAX_SEG || stride < (size_t)w || topn_max_lines < 0 || topn_max_lines > MAX_SEG ||
+        (nmax > 0 && (!rects || !flags_out || !segs_out))) {
+        set_error("sslam_testing_lines_nfa: invalid arguments"); return SSLAM_ERR_INVALID;
+    }
+    if (nframes > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w) { set_error("sslam_testing_lines_nfa: the frames overlap"); return SSLAM_ERR_INVALID; }
+    {   // a record the core could not have emitted is refused before anything is launched (the plan's sizes and tolerances as lines_build_plan computes them)
+        const int sw = (int)lrint(w * 0.8), sh = (int)lrint(h * 0.8);
+        const double prec = kPI * LSD_ANG_TH / 180, p = LSD_ANG_TH / 180;
+        for (int b = 0; b < nframes; ++b) {
+            if (ncand[b] < 0 || ncand[b] > MAX_SEG || ncand[b] > nmax) { set_error("sslam_testing_lines_nfa: frame %d holds %d rectangles (at most %d)", b, ncand[b], std::min(nmax, MAX_SEG)); return SSLAM_ERR_INVALID; }
+            for (int i = 0; i < ncand[b]; ++i) {
+                const double* o = rects + ((size_t)b * nmax + i) * 12;
+                bool ok = true;
+                for (int q = 0; q < 12; ++q) ok = ok && std::isfinite(o[q]);
+                // region2rect: the centre is a weighted mean of the region's pixels, inside the image; an end point is the projection of one of them onto the axis through
+                // the centre, no further from that pixel than its offset across the axis, which the width spans: within `width` of the image
+                for (int q = 0; ok && q < 3; ++q) {
+                    const double x = o[q == 2 ? 5 : 2 * q], y = o[q == 2 ? 6 : 2 * q + 1], m = q == 2 ? 0.0 : o[4];
+                    ok = x >= -m && x <= sw - 1 + m && y >= -m && y <= sh - 1 + m;
+                }
+                ok = ok && o[4] > 0 && o[4] <= std::max(sw, sh) && std::fabs(o[8] * o[8] + o[9] * o[9] - 1.0) <= 1e-9 && o[10] == prec && o[11] == p;
+                if (!ok) { set_error("sslam_testing_lines_nfa: rectangle %d of frame %d is not one the core emits (scaled image %d x %d)", i, b, sw, sh); return SSLAM_ERR_INVALID; }
+            }
+        }
+    }
+    std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
+    for (int& f : L->lastForms) f = -1;
+    SSLAM_HIP(hipSetDevice(L->ctx->device));
+    hipStream_t st = L->ctx->stream;
+    int rc;
+    const size_t dpitch = ((size_t)w + 63) & ~(size_t)63, dframe = dpitch * h;
+    if ((rc = L->dImg.ensure(dframe * nframes))) return rc;
+    L->lastN = -1;      // (the buffers of the last sslam_lines_extract are overwritten)
+    for (int b = 0; b < nframes; ++b)
+        SSLAM_HIP(hipMemcpy2DAsync(L->dImg.as<uint8_t>() + (size_t)b * dframe, dpitch, gray + (size_t)b * image_stride, stride, w, h, hipMemcpyHostToDevice, st));
+    if ((rc = lines_prepare(L, w, h, nframes, st))) return rc;
+    const LsdPlan& P = L->plan;
+    const LinesCall c{L, P, L->dImg.as<uint8_t>(), dpitch, dframe, nframes, st, L->dWs.as<uint8_t>()};
+    hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c.ws, P);
+    if ((rc = lines_prologue(c))) return rc;
+    for (int b = 0; b < nframes; ++b) {      // what the stage does not write still holds 0xA5 afterwards
+        uint8_t* base = c.ws + (size_t)b * P.frameBytes;
+        SSLAM_HIP(hipMemsetAsync(base + P.offFlag, 0xA5, sizeof(int) * MAX_SEG, st));
+        SSLAM_HIP(hipMemsetAsync(base + P.offSeg, 0xA5, sizeof(float4) * MAX_SEG, st));
+        SSLAM_HIP(hipMemsetAsync(base + P.offNfa, 0xA5, sizeof(NfaState) * MAX_SEG, st));
+        if (ncand[b] > 0) SSLAM_HIP(hipMemcpyAsync(base + P.offCand, rects + (size_t)b * nmax * 12, sizeof(double) * 12 * (size_t)ncand[b], hipMemcpyHostToDevice, st));
+        SSLAM_HIP(hipMemcpyAsync(base + P.offMisc + offsetof(Misc, nCand), &ncand[b], sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    if ((rc = sslam::launch_nfa_stage(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), nframes, topn_max_lines, L->lastForms + 4))) return rc;
+    SSLAM_HIP(hipGetLastError());
+    L->lastFrames = nframes;
+    for (int b = 0; b < nframes; ++b) {
+        const uint8_t* base = c.ws + (size_t)b * P.frameBytes;
+        if (nmax > 0) {
+            SSLAM_HIP(hipMemcpyAsync(flags_out + (size_t)b * nmax, base + P.offFlag, sizeof(int) * (size_t)std::min(nmax, MAX_SEG), hipMemcpyDeviceToHost, st));
+            SSLAM_HIP(hipMemcpyAsync(segs_out + (size_t)b * nmax * 4, base + P.offSeg, sizeof(float4) * (size_t)std::min(nmax, MAX_SEG), hipMemcpyDeviceToHost, st));
+        }
+        SSLAM_HIP(hipMemcpyAsync(topn_out + b, base + P.offMisc + offsetof(Misc, topn), sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    SSLAM_HIP(hipStreamSynchronize(st));
+    return SSLAM_OK;
+}
+
 // Self-test of the table-based exact division used in the NFA tail (tests/test_lines_gpu.py): returns the number of
 // random (a, b) pairs, 1 <= a, b < n, whose quotient differs from the hardware IEEE division (must be 0).
 namespace {

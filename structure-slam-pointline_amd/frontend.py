@@ -938,6 +938,57 @@ class LinePrologue:
             self.h = C.c_void_p()
 
 
+class LineNfaStage:
+    """A sslam_lines handle of the TESTING library with the tap of the NFA stage, sslam_testing_lines_nfa (include/sslam_testing.h): the stage's kernels on rectangle records
+    the caller supplies, over the product's own T plane of the frames."""
+    FILL = 0xA5A5A5A5          # the 32 bits of a flag or a segment coordinate the stage did not write (view the arrays as uint32)
+
+    def __init__(self, ctx, max_lines=40):
+        self.T = testing_lib()
+        self.T.sslam_testing_lines_nfa.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3
+        self.h = C.c_void_p()
+        rc = self.T.sslam_lines_create(ctx.h, int(max_lines), C.byref(self.h))
+        if rc != 0:
+            raise SslamError("%s: %s" % (self.T.sslam_status_str(rc).decode(), self.T.sslam_last_error().decode()), rc)
+
+    def __enter__(self): return self
+
+    def __exit__(self, *a): self.close()
+
+    def raw(self, images, rects, ncand, topn_max_lines):
+        """images [nf, h, w] uint8, rects [nf, nmax, 12] float64, ncand [nf] -> (status, (flags [nf, nmax] int32, segs [nf, nmax, 4] float32, topn [nf] int32)): the arrays
+        copied back WHOLE (FILL where the stage did not write; include/sslam_testing.h says which rows of a ranked frame are unspecified)"""
+        images = np.ascontiguousarray(images, np.uint8); rects = np.ascontiguousarray(rects, np.float64); ncand = np.ascontiguousarray(ncand, np.int32)
+        nf, h, w = images.shape
+        assert rects.ndim == 3 and rects.shape[0] == nf and rects.shape[2] == 12 and ncand.shape == (nf,)
+        nmax = rects.shape[1]
+        flags = np.zeros((nf, nmax), np.int32); segs = np.zeros((nf, nmax, 4), np.float32); topn = np.full(nf, -1, np.int32)
+        rc = self.T.sslam_testing_lines_nfa(self.h, images.ctypes.data, w, h, w, w * h, nf, rects.ctypes.data, ncand.ctypes.data, nmax, int(topn_max_lines),
+                                            flags.ctypes.data, segs.ctypes.data, topn.ctypes.data)
+        return rc, (flags, segs, topn)
+
+    def __call__(self, images, rects, ncand, topn_max_lines=0):
+        rc, out = self.raw(images, rects, ncand, topn_max_lines)
+        if rc != 0:
+            raise SslamError("%s: %s" % (self.T.sslam_status_str(rc).decode(), self.T.sslam_last_error().decode()), rc)
+        return out
+
+    def last_forms(self):
+        """words 2 .. 6 of sslam_testing_lines_last_forms -> dict(fused_grad, sort_runs, nfa, eval_waves, count_waves); the tap runs no core"""
+        o = (C.c_int32 * 8)()
+        rc = self.T.sslam_testing_lines_last_forms(self.h, o)
+        if rc != 0:
+            raise SslamError("sslam_testing_lines_last_forms: %d" % rc, rc)
+        flag = lambda v: bool(v) if v >= 0 else None
+        return dict(core=LineExtractor.CORE_FORMS[o[0]] if o[0] >= 0 else None, fused_grad=flag(o[2]), sort_runs=flag(o[3]),
+                    nfa=LineExtractor.NFA_FORMS[o[4]] if o[4] >= 0 else None, eval_waves=o[5], count_waves=o[6])
+
+    def close(self):
+        if self.h:
+            self.T.sslam_lines_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 # ---- multi-GPU batch mode (include/sslam_frontend.h: sslam_group_*, record stream) ------------------------------------------------
 class FrontendParams(C.Structure):
     _fields_ = [("nfeatures", C.c_int32), ("scale_factor", C.c_float), ("nlevels", C.c_int32), ("ini_th_fast", C.c_int32),

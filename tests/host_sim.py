@@ -7,14 +7,14 @@ import numpy as np
 
 
 @functools.lru_cache(maxsize=None)
-def programs(src):
-    """(plain, sanitised): the two builds of the sim, in a directory that goes away with the process"""
+def programs(src, defines=()):
+    """(plain, sanitised): the two builds of the sim, in a directory that goes away with the process; defines: -D options of a build variant (a tuple of NAME=value)"""
     name = os.path.splitext(os.path.basename(src))[0]
     d = tempfile.mkdtemp(prefix=name + "_")
     atexit.register(shutil.rmtree, d, ignore_errors=True)
     plain, san = os.path.join(d, name), os.path.join(d, name + "_san")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", src, "-o", plain])
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", san])
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", src, "-o", plain] + ["-D" + d for d in defines])
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", san] + ["-D" + d for d in defines])
     return plain, san
 
 
@@ -30,9 +30,9 @@ def floats(tokens):
     return np.array([int(t) for t in tokens], np.uint64).astype(np.uint32).view(np.float32)
 
 
-def run_plain(src, text):
+def run_plain(src, text, defines=()):
     """the plain build alone -> its stdout"""
-    r = subprocess.run([programs(src)[0]], input=text, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([programs(src, tuple(defines))[0]], input=text, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-2000:])
     return r.stdout
 
