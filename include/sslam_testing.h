@@ -74,8 +74,8 @@ int sslam_testing_lines_tail(sslam_lines* ln, const uint8_t* gray, int w, int h,
  * form's grid (0 otherwise), out[2] = the gradient came from the fused blur + gradient kernel, out[3] = the seeds were sorted by the tile-sorted runs kernels, out[4] = the NFA
  * stage (0 streaming beside the core, 1 the 18 launches, 2 k_nfa_all), out[5] / out[6] = its evaluating / counting waves per frame (streaming: the consumer waves and 0),
  * out[7] = k_lbd's template argument.  Every call starts with -1 in all eight, so a word the call did not reach (before the first call; a call that failed early; out[3]
- * under sslam_lines_set_seed_order(1), where the host sorts) is -1 and never another call's choice.  The handle records these in plain fields where they are decided; nothing on the
- * product path reads them. */
+ * under sslam_lines_set_seed_order(1), where the host sorts) is -1 and never another call's choice; the three taps of this header start the same way.  The handle keeps what lines_forms
+ * (csrc/lines_form.h) decided for the call and how far the call got; this function alone turns that into the eight words. */
 int sslam_testing_lines_last_forms(sslam_lines* ln, int32_t out[8]);
 
 /* The line prologue -- k_blur7 + k_lsd_grad or k_lsd_grad_fused, the gradient table behind them, and the counting sort of the seeds as k_lsd_hist + k_lsd_scan +
@@ -85,7 +85,7 @@ int sslam_testing_lines_last_forms(sslam_lines* ln, int32_t out[8]);
  * `image_stride` bytes from frame to frame).  They are uploaded into the handle's image buffer in the layout the caller chooses: rows `dev_pitch` bytes apart (0: the
  * 64-byte-aligned pitch sslam_lines_extract and the tail tap use; otherwise >= w), frames dev_pitch * h apart, the first pixel `dev_offset` (0 .. 3) bytes behind the
  * buffer's 256-byte-aligned start -- the fused kernel takes dword-aligned layouts of its geometry only, so an offset of 1 sends such a frame through k_blur7 + k_lsd_grad.
- * The choice itself is lines_prologue()'s, unchanged.  The call sets the words of sslam_testing_lines_last_forms to -1, runs lines_prepare, k_zero_misc and lines_prologue()
+ * The choice itself is lines_prologue()'s, unchanged (the tile-sorted runs are lines_forms', csrc/lines_form.h).  The call sets the words of sslam_testing_lines_last_forms to -1, runs lines_prepare, k_zero_misc and lines_prologue()
  * -- the functions of sslam_lines_extract_batch_dev, nothing else -- which records words 2 (fused gradient) and 3 (tile-sorted runs; stays -1 under
  * sslam_lines_set_seed_order(1)) as on the product path.  sslam_lines_set_resize_variant / _seed_order / _blur_variant apply as they do there.
  * Outputs on the host, plane_cap pixels per frame (SSLAM_ERR_CAPACITY if the scaled image sw x sh = size_out[0] x size_out[1] holds more; size_out is valid then): with
@@ -111,8 +111,8 @@ int sslam_testing_lines_grad_table(sslam_lines* ln, float* tab_out, int32_t* smi
  * [0, sw - 1] x [0, sh - 1] and both end points within `width` of it (region2rect projects the region's pixels onto the axis: the core's own end points lie up to a few pixels
  * outside on ordinary frames, and the counters clip every row and column to the image); 0 < width <= max(sw, sh); |dx^2 + dy^2 - 1| <= 1e-9; prec and p equal to the plan's.  The call runs lines_prepare, k_zero_misc and
  * lines_prologue() as sslam_lines_extract_batch_dev does (the T plane is the product's own), fills every frame's flag, segment and NfaState regions with the byte 0xA5, writes
- * the records and Misc::nCand where the core leaves them and calls sslam::launch_nfa_stage with topn_max_lines, nothing else: the form is chosen as on the product path by
- * SSLAM_NFA_FUSED and the number of frames, and recorded for sslam_testing_lines_last_forms (words 2 .. 6; the core's words stay -1).  The streaming form takes its records
+ * the records and Misc::nCand where the core leaves them and calls lines_nfa_stage (sslam::launch_nfa_stage) with topn_max_lines, nothing else: the form is chosen as on the
+ * product path by lines_forms (csrc/lines_form.h) from SSLAM_NFA_FUSED and the number of frames, and recorded for sslam_testing_lines_last_forms (words 2 .. 6; the core's words stay -1).  The streaming form takes its records
  * from a cluster slot and is not reached from here.  Outputs on the host: flags_out[nframes][nmax] and segs_out[nframes][nmax][4] at EMISSION indices (flag 0 rejected,
  * 1 accepted with its segment written, 2 left out by the top-N form), topn_out[nframes] = Misc::topn.  Rows at or past ncand still hold the fill, and so does the segment
  * of every row that is not flagged 1 -- with ONE exception, documented rather than refused (a call may mix ranked frames with frames of more than 1024 rectangles): in a

@@ -16,14 +16,16 @@
 // This file: the per-frame workspace plan and the C-ABI entry points (sslam_lines_*).
 #include "common.h"
 #include "nfa_topn.h"
+#include "lines_form.h"
 #include <cmath>
 #include <cstdlib>
 #include <cfloat>
 #include <algorithm>
+#include <optional>
 
 namespace sslam { int launch_nfa_stream(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, uint8_t* clArea, size_t clFrameBytes,
                                         size_t stageOff, int nframes, int waves, long long spinTicks, bool besideCore); }      // lines_nfa.hip
-namespace sslam { int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes, int topnMaxLines, int* form3); }      // lines_nfa.hip
+namespace sslam { int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes, NfaForm form, int evalWaves, int countWaves, int topnMaxLines); }      // lines_nfa.hip
 
 using namespace sslam;
 
@@ -87,10 +89,13 @@ struct sslam_lines {
     int sMin = 0;                   // smallest |g|^2 of a defined pixel (k_grad_smin, with the gradient table)
     bool fusedGeometry = false;     // lines_build_plan: the plan admits k_lsd_grad_fused
     hipStream_t nfaStream = nullptr; hipEvent_t nfaFork = nullptr, nfaJoin = nullptr;      // the NFA stage next to the cluster form of the core (calls of up to 64 frames)
-    // what the last sslam_lines_extract_batch_dev chose, written where it is decided and read by sslam_testing_lines_last_forms alone (include/sslam_testing.h):
-    // CoreForm, the guest form's grid, fused gradient kernel, tile-sorted runs, NFA form (0 stream, 1 the 18 launches, 2 k_nfa_all) with its evaluating and counting waves
-    // per frame, k_lbd's template argument.  Every batch call starts with -1 in all of them.
-    int lastForms[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    // what the last batch call (or testing tap) of the handle chose and how far it got, read by sslam_testing_lines_last_forms alone (include/sslam_testing.h).  Every call
+    // starts with a fresh record: lines_forms' answer and nothing reached.
+    struct LastForms {
+        LinesForms forms{};
+        int fusedGrad = -1;                  // lines_prologue's own choice (pointer and pitch alignment, fusedGeometry); -1: not reached
+        bool seedSort = false, core = false, nfa = false, lbd = false;      // reached: the seed sort on the device, the core, the NFA stage, k_lbd
+    } last;
 };
 
 static std::vector<int> taps_q8(int n, double sigma) {
@@ -313,84 +318,22 @@ static int lines_host_seed_order(sslam_lines* L, uint8_t* ws, int nframes, hipSt
     return SSLAM_OK;
 }
 
-// The environment knobs of the line path, read on every call (tests and bench.py set them between calls), here and nowhere else in this unit.
-struct LinesKnobs {
-    int lone;                   // SSLAM_LSD_FLAVOUR: 1 = "cl" / "lat" (lone waves where the cluster form does not apply), 0 = "thr"; -1 (unset): lone waves below 1 024 frames
-    bool cluster;               // the cluster form where it applies; false under SSLAM_LSD_CLUSTER=0 or a SSLAM_LSD_FLAVOUR other than "cl"
-    int persist;                // SSLAM_LSD_PERSIST=g: the guest form's grid (0: lines_guest_form's own)
-    int clWgs, clWindow, clSmap;      // the cluster form (lsd_cluster.h): SSLAM_CL_WGS = workgroups per frame (4 waves each); SSLAM_CL_WINDOW = how many sub-chunks of 16 seed
-                                      // positions the helpers may run ahead (-1: no helpers at all, the main wave alone), + 1 << 20 under SSLAM_CL_NO_FEEDER (the main wave
-                                      // fetches everything itself); SSLAM_CL_SMAP = cell size (log2) of the shared map that steers the helpers' seed choice (-1: none)
-    int nfaStreamWaves;         // SSLAM_NFA_STREAM: consumer waves per frame of the NFA stage next to the cluster form (0: the stage behind the core, the round-4 default)
-    long long nfaSpinTicks;     // SSLAM_NFA_STREAM_TICKS: how long a consumer wave waits without progress before it leaves its blocks to the launch behind the core
-};
-static LinesKnobs lines_knobs() {
-    // 50 ms of the 100 MHz clock (ten single-frame cores) of waiting; 0.2 s in round 5: on a GPU shared with another process the consumers can be resident before the producer,
-    // and the wait was the spike
-    LinesKnobs K{-1, true, 0, 10, 640 / CL_SUB, 0, 16, 5000000};
-    if (const char* e = getenv("SSLAM_LSD_FLAVOUR")) { K.lone = e[0] == 'l' || e[0] == 'c'; K.cluster = e[0] == 'c'; }
-    if (const char* e = getenv("SSLAM_LSD_CLUSTER")) K.cluster = K.cluster && atoi(e) != 0;
-    if (const char* e = getenv("SSLAM_LSD_PERSIST")) { const int g = atoi(e) & ~7; if (g >= 8) K.persist = g; }
-    if (const char* e = getenv("SSLAM_CL_WGS")) K.clWgs = std::max(1, std::min(CL_MAXWG, atoi(e)));
-    if (const char* e = getenv("SSLAM_CL_WINDOW")) K.clWindow = std::max(-1, atoi(e));
-    if (getenv("SSLAM_CL_NO_FEEDER") && K.clWindow >= 0) K.clWindow |= 1 << 20;
-    if (const char* e = getenv("SSLAM_CL_SMAP")) K.clSmap = atoi(e);
-    if (const char* e = getenv("SSLAM_NFA_STREAM")) { const int n = atoi(e); K.nfaStreamWaves = std::max(0, std::min(64, n == 1 ? 16 : n)); }
-    if (const char* e = getenv("SSLAM_NFA_STREAM_TICKS")) K.nfaSpinTicks = std::max(0ll, atoll(e));
-    return K;
-}
+// The knobs and the form plan live in lines_form.h; this is the one place of the line path that reads the environment, on every call (tests and bench.py set knobs between calls)
+static LinesKnobs lines_knobs() { return lines_knobs_from([](const char* name) -> const char* { return getenv(name); }); }
 
-// Whether a batch of `nframes` runs the sequential core in its guest form (lsd_regions.h): a co-running branch was announced (sslam_lines_set_core_event) and the batch is
-// at least two rounds of the persistent grid of 20 (16 for smaller batches) workgroups per compute unit.
-// What a compute unit holds beside the core is decided by registers AND by LDS, which gfx950 hands out in granules of 1 280 B (tools/lds_granule_probe.hip).  A core
-// workgroup takes 94 VGPRs and four granules (5 120 B, lsd_regions.h), a k_fast_cells wave -- one per strip of three cells -- 32 VGPRs and eleven granules at 640 x 480 (orb.hip):
-//   20 per compute unit: five core waves on every SIMD (480 of 512 VGPRs), one FAST wave beside them; 100 KB of the 160 KB of LDS for the core, room for four FAST waves;
-//   18 per compute unit: two SIMDs hold five core waves, two hold four and keep 128 registers: ten FAST waves by registers, five by LDS.
-// Before the LDS budgets (core 5 648 B = five granules, FAST 7 290 B = six) 18 left six FAST waves and was the optimum (17 / 19 / 20: 150.8 / 149.4 / 150.0 ms per step against
-// 149.3).  With them it is not: ten FAST waves beside 18 core workgroups slow the core more (92 -> 96 ms) than they speed up FAST (76.4 -> 74.3), 151.4 ms per step; 20 with the
-// FAST waves the registers then leave gives 148.5.  Also measured, no better: k_lsd_regions<false, 6> (80 VGPRs) on the grid at 20 / 22 / 24 per compute unit -- the core
-// drops to 90 / 85 / 79 ms, FAST beside it stays at 76 - 77 ms whatever its slot count, and the step at 148 - 149 ms (profiles/guest_grid_lds_budgets.txt).
-// (Those figures are from k_fast_cells per cell at four granules.  Per strip FAST takes 73.0 ms beside the grid of 20 and the step 146.2 ms; 18 / 19 / 20 per compute unit
-// were run again with it, profiles/fast_strips.txt section 6.)
-static bool lines_guest_form(const sslam_lines* L, int nframes, const LinesKnobs& K, int* grid_out) {
-    int grid = 20 * L->ctx->num_cus;
-    if (2 * grid > nframes) grid = 16 * L->ctx->num_cus;
-    if (K.persist) grid = K.persist;
-    if (grid_out) *grid_out = grid;
-    // at least two full rounds of the persistent grid: a batch of 1.5 grids (sslam_frontend_batch's chunks of 6 144 frames) would run half of the slots twice and the
-    // other half once -- measured on the bench's frame sequence, 24 576 frames through host memory: 61.1 k frames/s in this form against 66.0 k in the other (profiles/r06g_*)
-    return L->coreEvent != nullptr && nframes >= 1024 && 2 * grid <= nframes;
-}
+// lines_form.h holds these limits as plain integers for the host-only tests: each is pinned to the constant the device code is built from
+static_assert(LINES_CLUSTER_MAX_SW == TorusGlobal::XMASK + 1 && LINES_CLUSTER_MAX_SH == TorusGlobal::YMASK + 1, "the cluster form's pixel map (lsd_regions.h TorusGlobal) bounds the scaled image of lines_forms' cluster form");
+static_assert(LINES_CLUSTER_LDS_SW == TorusFrame::XMASK + 1 && LINES_CLUSTER_LDS_SH == TorusFrame::YMASK + 1, "the main wave's LDS bitmap (lsd_regions.h TorusFrame) is lines_forms' bigFrame limit");
+constexpr int CL_MAXFRAMES = 8 * 8;      // the cluster form's grid (lines_core_cluster): eight XCDs, up to eight frames on each -- at four workgroups a frame they fill its 32 compute units
+static_assert(LINES_CLUSTER_MAX_FRAMES == CL_MAXFRAMES, "lines_forms sends no more frames to the cluster form than its grid is laid out for");
+static_assert(LINES_CL_MAXWG == CL_MAXWG && LINES_CL_SUB == CL_SUB, "lsd_cluster.h: lines_knobs_from clamps SSLAM_CL_WGS and sizes the default window with these");
+static_assert(LINES_SORT_RUNS_MAX_SIDE == 1 << SORT_XY_BITS, "a sorted entry packs x and y into SORT_XY_BITS bits each (lsd_front.h)");
+
+// Whether a batch of `nframes` would find room for the core's guest form (lines_forms' guestFits: the image size does not enter it).  sslam_frontend_batch and the pipeline ask
+// before they announce the co-running branch.
 extern "C" int sslam_lines_core_guest_form(sslam_lines* L, int nframes) {
     if (!L || nframes <= 0) return 0;
-    return lines_guest_form(L, nframes, lines_knobs(), nullptr) ? 1 : 0;
-}
-
-// The launch forms of the sequential core (lsd_regions.h, lsd_cluster.h)
-enum class CoreForm {
-    ClusterStream,      // k_lsd_regions_cl<1>, the NFA stage next to it on the side stream (k_nfa_stream)
-    Cluster,            // k_lsd_regions_cl<0>, the NFA stage behind it (SSLAM_NFA_STREAM=0)
-    Lone,               // k_lsd_regions<true, 4>, one wave per frame: the shortest chain
-    Guest,              // k_lsd_regions<false, 4> on a persistent grid (lines_guest_form)
-    PerFrame,           // k_lsd_regions<false, 4>, one workgroup per frame
-    SixWave,            // k_lsd_regions<false, 6>, one workgroup per frame
-};
-
-// Up to 64 frames (one to eight per XCD, four workgroups each) of up to 2 048 x 1 024 scaled pixels take the cluster form -- helper waves on several
-// compute units, results through global memory, monotonic pixel map (lsd_cluster.h).  Per call, cluster form against the multi-wave form of rounds 2-4 (tools/small_batch_probe.py,
-// round 3): 1 frame 5.9 / 7.9 ms, 8: 8.5 / 11.2, 16: 9.0 / 11.9, 24: 9.4 / 12.6, 32: 10.3 / 13.1, 64: 13.5 / 15.7, 96: 21.6 / 15.9
-constexpr int CL_MAXFRAMES = 64;
-
-// Which form a call takes.  Lone waves below 1 024 frames: at most one wave per SIMD is resident, so the instantiation that spills nothing costs no occupancy.  A caller that
-// announced a branch running beside the core (sslam_lines_set_core_event: the bench step's point branch waits for that event) gets the guest form: 16 - 20 persistent workgroups
-// per compute unit of the four-wave instantiation (lines_guest_form says what that leaves for the other branch's waves).  Otherwise up to 16 frames per compute unit (four waves per SIMD
-// anyway; BASELINE configs[3]: 3 072 frames) take the spill-free instantiation, larger batches the six-wave one.  grid: the guest form's grid.
-static CoreForm lines_core_form(const sslam_lines* L, const LsdPlan& P, int nframes, const LinesKnobs& K, int* grid) {
-    if (K.cluster && nframes <= CL_MAXFRAMES && P.sw <= TorusGlobal::XMASK + 1 && P.sh <= TorusGlobal::YMASK + 1)
-        return K.nfaStreamWaves ? CoreForm::ClusterStream : CoreForm::Cluster;
-    if (K.lone >= 0 ? K.lone != 0 : nframes < 1024) return CoreForm::Lone;
-    if (lines_guest_form(L, nframes, K, grid)) return CoreForm::Guest;
-    return nframes <= 16 * L->ctx->num_cus ? CoreForm::PerFrame : CoreForm::SixWave;
+    return lines_forms(0, 0, 0, 0, nframes, L->ctx->num_cus, L->coreEvent != nullptr, 0, lines_knobs()).guestFits ? 1 : 0;
 }
 
 extern "C" int sslam_lines_destroy(sslam_lines* L) {
@@ -405,10 +348,16 @@ extern "C" int sslam_lines_destroy(sslam_lines* L) {
     return SSLAM_OK;
 }
 
-// One call of sslam_lines_extract_batch_dev: what its stages share
+// One call of sslam_lines_extract_batch_dev: what its stages share.  F: what lines_forms decided for it -- the stages decide nothing from sizes themselves
 struct LinesCall {
-    sslam_lines* L; const LsdPlan& P; const uint8_t* images; size_t pitch, imageStride; int nframes; hipStream_t st; uint8_t* ws;
+    sslam_lines* L; const LsdPlan& P; const uint8_t* images; size_t pitch, imageStride; int nframes; hipStream_t st; uint8_t* ws; const LinesForms& F;
 };
+// lines_forms for a call of `nframes` frames on the handle's plan (after lines_prepare), kept in the handle's record of the call
+static const LinesForms& lines_call_forms(sslam_lines* L, int nframes, int topnMaxLines, const LinesKnobs& K) {
+    const LsdPlan& P = L->plan;
+    L->last.forms = lines_forms(P.w, P.h, P.sw, P.sh, nframes, L->ctx->num_cus, L->coreEvent != nullptr, topnMaxLines, K);
+    return L->last.forms;
+}
 
 // Work forked onto the side stream (L->nfaStream) is joined into `st` on EVERY way out of sslam_lines_extract_batch_dev -- also the early error returns: the caller may reuse
 // or free the workspace as soon as `st` is idle, and the side stream's kernels write into it
@@ -435,8 +384,8 @@ static void lines_blur_sobel(const LinesCall& c, hipStream_t s) {
                        (unsigned*)(c.ws + P.offDxy), P.frameBytes, c.L->dTaps.as<int>() + 8);
 }
 
-// The prologue: blur(7, 0.75) -> 0.8x -> gradient, then the seeds in order.  The fused blur + gradient kernel where the plan admits it (lines_build_plan) and the tile-sorted
-// runs where a sorted entry's packing fits (scaled image up to 2048 x 2048); k_blur7 + k_lsd_grad and k_lsd_hist + k_lsd_scatter for every other geometry.
+// The prologue: blur(7, 0.75) -> 0.8x -> gradient, then the seeds in order.  The fused blur + gradient kernel where the plan admits it (lines_build_plan) and the layout is
+// dword-aligned -- the one choice made here, from pointers and pitches -- and the tile-sorted runs where lines_forms says so; k_blur7 + k_lsd_grad and k_lsd_hist + k_lsd_scatter for every other geometry.
 // What it leaves per frame -- the T, S and Cs planes, Misc::maxS / nDefined and the ordered seed list at offOrder -- is read back by the testing library's
 // sslam_testing_lines_prologue (below; include/sslam_testing.h), which runs lines_prepare, k_zero_misc and this function and nothing else: tests/test_lsd_head_gpu.py
 // compares every pixel and every seed with the oracle.
@@ -446,7 +395,7 @@ static int lines_prologue(const LinesCall& c) {
     const int* tabX = L->dTabs.as<int>() + P.tabX; const int* tabY = L->dTabs.as<int>() + P.tabY;
     const int mode = (P.lsdResize ? 1 : 0) | (L->seedOrder ? 2 : 0);      // the gradient kernels' template argument
     const bool fused = L->fusedGeometry && GRAD_ROWS == 8 && ((uintptr_t)c.images & 3) == 0 && (c.pitch & 3) == 0 && (c.imageStride & 3) == 0 && c.pitch <= 0x7FFFFFFF;
-    L->lastForms[2] = fused;
+    L->last.fusedGrad = fused;
     if (fused) {
         static decltype(&k_lsd_grad_fused<0>) const kGradFused[4] = {k_lsd_grad_fused<0>, k_lsd_grad_fused<1>, k_lsd_grad_fused<2>, k_lsd_grad_fused<3>};
         sslam::ProfScope _ps(L->ctx, "k_lsd_grad", st);
@@ -462,8 +411,8 @@ static int lines_prologue(const LinesCall& c) {
           hipLaunchKernelGGL(kGrad[mode], gg, dim3(64, 4), 0, st, c.ws, P, L->dGtab.as<float4>(), bpitch, tabX, tabY); }
     }
     if (L->seedOrder) return lines_host_seed_order(L, c.ws, c.nframes, st);
-    const bool runs = P.sw <= (1 << SORT_XY_BITS) && P.sh <= (1 << SORT_XY_BITS);
-    L->lastForms[3] = runs;
+    const bool runs = c.F.sortRuns;
+    L->last.seedSort = true;
     const dim3 sg(sort_grid(P.nTiles, c.nframes));
     { sslam::ProfScope _ps(L->ctx, "k_lsd_hist", st); hipLaunchKernelGGL(runs ? k_lsd_hist_sort : k_lsd_hist, sg, dim3(64), 0, st, c.ws, P, c.nframes); }
     { sslam::ProfScope _ps(L->ctx, "k_lsd_scan", st); hipLaunchKernelGGL(k_lsd_scan, dim3(c.nframes), dim3(1024), 0, st, c.ws, P); }
@@ -471,19 +420,16 @@ static int lines_prologue(const LinesCall& c) {
     return SSLAM_OK;
 }
 
-// The cluster form of the core.  streamNfa: the NFA stage runs NEXT TO the core on the side stream, on the rectangles the main wave has published so far (lsd_nfa.h,
-// k_nfa_stream) -- the default since round 5 (whole GPU suite with the knob exported, single frames 6.02 / 7.18 -> 5.76 / 6.89 ms p50 / p90, calls of 2 .. 64 frames
-// -8 .. -24 %: profiles/r05a_*).  *nfaStageOff: where the frames' rectangles for that stage lie in a cluster slot.
-static int lines_core_cluster(const LinesCall& c, const LinesKnobs& K, bool streamNfa, SideJoin& side, size_t* nfaStageOff) {
-    sslam_lines* L = c.L; const LsdPlan& P = c.P; const int nframes = c.nframes; hipStream_t st = c.st;
+// The cluster form of the core.  Under CoreForm::ClusterStream the NFA stage runs NEXT TO the core on the side stream, on the rectangles the main wave has published so far
+// (lsd_nfa.h, k_nfa_stream).  *nfaStageOff: where the frames' rectangles for that stage lie in a cluster slot.
+static int lines_core_cluster(const LinesCall& c, SideJoin& side, size_t* nfaStageOff) {
+    sslam_lines* L = c.L; const LsdPlan& P = c.P; const LinesForms& F = c.F; const int nframes = c.nframes; hipStream_t st = c.st;
     int rc;
-    const bool bigFrame = P.sw > TorusFrame::XMASK + 1 || P.sh > TorusFrame::YMASK + 1;      // the main wave's bitmap in global memory instead of LDS
-    const int window = K.clWindow, clShift = K.clSmap;
-    int nWG = K.clWgs;
+    const bool streamNfa = F.core == CoreForm::ClusterStream, bigFrame = F.bigFrame;
+    const int window = F.clWindow, clShift = F.clSmap, nWG = F.clWgs;
     const int clSpecWords = clShift < 0 ? 0 : (((P.sw + (1 << clShift) - 1) >> clShift) * ((P.sh + (1 << clShift) - 1) >> clShift) + 31) / 32;
     const size_t maxSubs = ((size_t)P.npx + CL_SUB - 1) / CL_SUB;
     const size_t zeroBytes = 512 + ((maxSubs * sizeof(ClSub) + 511) & ~(size_t)511) + 4 * (size_t)((clSpecWords + 127) & ~127) + (bigFrame ? 4 * (size_t)TorusGlobal::WORDS : 0);      // control block, sub-chunk states / flags, shared map (+ the main wave's bitmap)
-    if (nframes > 8) nWG = std::max(2, std::min(nWG, 32 / ((nframes + 7) / 8)));      // the frames of an XCD share its 32 compute units
     // per frame: the zeroed head, two result records per seed position, one 256 KB list arena per HELPER THAT EXISTS ((nWG - 1) x CL_HPW: 27 by default;
     // rounds 1-3 sized it for 64), and the rectangles of the streaming NFA stage.  One slot per frame of the call: blocks with b >= nframes return at once, so the
     // XCD-aligned grid needs no padding slots (a single 640x480 frame held 8 slots of 30 MB before).
@@ -509,15 +455,16 @@ static int lines_core_cluster(const LinesCall& c, const LinesKnobs& K, bool stre
     // LBD's gradient image depends on the source alone: on the second stream it runs under the core instead of behind the NFA stage (28 us of a single frame's
     // 5.4 ms; the join in the tail orders it before k_lbd.  Behind the NFA stage instead: 5.43 -> 5.38 ms p50, GPU call I)
     lines_blur_sobel(c, L->nfaStream);
-    if ((rc = sslam::launch_nfa_stream(L->ctx, L->nfaStream, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), clFrame, stageOff, nframes, K.nfaStreamWaves, K.nfaSpinTicks, true))) return rc;
-    L->lastForms[4] = 0; L->lastForms[5] = K.nfaStreamWaves; L->lastForms[6] = 0;
+    if ((rc = sslam::launch_nfa_stream(L->ctx, L->nfaStream, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), clFrame, stageOff, nframes, F.streamWaves, F.spinTicks, true))) return rc;
+    L->last.nfa = true;
     *nfaStageOff = stageOff;
     return SSLAM_OK;
 }
 
-// The sequential core in the form lines_core_form chose, between the core gate / event of the caller
-static int lines_core(const LinesCall& c, const LinesKnobs& K, CoreForm form, int grid, SideJoin& side, size_t* nfaStageOff) {
+// The sequential core in the form lines_forms chose, between the core gate / event of the caller
+static int lines_core(const LinesCall& c, SideJoin& side, size_t* nfaStageOff) {
     sslam_lines* L = c.L; const LsdPlan& P = c.P; const int nframes = c.nframes; hipStream_t st = c.st;
+    L->last.core = true;
     static_assert(LSD_CORE_LDS <= 48 * 1024, "k_lsd_regions: the region queue must fit the default dynamic LDS limit (SSLAM_LSD_QCAP)");
     const size_t lds = LSD_CORE_LDS;      // queue, fp64 addends, seed cos / sin: four allocation granules of 1 280 B (lsd_regions.h)
     if (L->coreWait) SSLAM_HIP(hipStreamWaitEvent(st, L->coreWait, 0));      // (sslam_lines_set_core_gate: another extractor's core has the wave slots until then)
@@ -525,17 +472,24 @@ static int lines_core(const LinesCall& c, const LinesKnobs& K, CoreForm form, in
     {
         sslam::ProfScope _ps(L->ctx, "k_lsd_regions", st);
         const double* lgam = L->dLgam.as<double>();
-        switch (form) {
+        switch (c.F.core) {
             case CoreForm::ClusterStream:
-            case CoreForm::Cluster: { const int rc = lines_core_cluster(c, K, form == CoreForm::ClusterStream, side, nfaStageOff); if (rc) return rc; break; }
+            case CoreForm::Cluster: { const int rc = lines_core_cluster(c, side, nfaStageOff); if (rc) return rc; break; }
             case CoreForm::Lone: hipLaunchKernelGGL((k_lsd_regions<true, 4>), dim3(nframes), dim3(64), lds, st, c.ws, P, lgam, nframes); break;
-            case CoreForm::Guest: hipLaunchKernelGGL((k_lsd_regions<false, 4>), dim3(grid), dim3(64), lds, st, c.ws, P, lgam, nframes); break;
+            case CoreForm::Guest: hipLaunchKernelGGL((k_lsd_regions<false, 4>), dim3(c.F.guestGrid), dim3(64), lds, st, c.ws, P, lgam, nframes); break;
             case CoreForm::PerFrame: hipLaunchKernelGGL((k_lsd_regions<false, 4>), dim3(nframes), dim3(64), lds, st, c.ws, P, lgam, nframes); break;
             case CoreForm::SixWave: hipLaunchKernelGGL((k_lsd_regions<false, 6>), dim3(nframes), dim3(64), lds, st, c.ws, P, lgam, nframes); break;
         }
     }
     if (L->coreDone) SSLAM_HIP(hipEventRecord(L->coreDone, st));
     return SSLAM_OK;
+}
+
+// The NFA stage behind the core, in the form and with the waves lines_forms chose (lines_tail and the testing library's sslam_testing_lines_nfa)
+static int lines_nfa_stage(const LinesCall& c) {
+    sslam_lines* L = c.L; const LinesForms& F = c.F;
+    L->last.nfa = true;
+    return sslam::launch_nfa_stage(L->ctx, c.st, c.ws, &c.P, sizeof(c.P), L->dLgam.as<double>(), c.nframes, F.nfa, F.evalWaves, F.countWaves, F.topnMaxLines);
 }
 
 // Behind the NFA stage: the output lines (KeyLine fill, top-N, line equations), LBD's gradient image unless the side stream has it, and the descriptors.  What lines_tail
@@ -545,25 +499,20 @@ static void lines_describe(const LinesCall& c, SideJoin& side, sslam_keyline* d_
     { sslam::ProfScope _ps(L->ctx, "k_keylines", st); hipLaunchKernelGGL(k_keylines, dim3(nframes), dim3(256), 0, st, c.ws, P, L->maxLines, d_kl, d_linefn, d_counts, cap); }
     if (!side.forked) lines_blur_sobel(c, st);
     side.join();
-    {   // the walk's conversion form (lbd.h): images of up to 16 384 pixels a side; the previous form beyond
-        const bool rpi = P.w <= 16384 && P.h <= 16384;
-        L->lastForms[7] = rpi;
+    {
+        L->last.lbd = true;
         sslam::ProfScope _ps(L->ctx, "k_lbd", st);
-        hipLaunchKernelGGL(rpi ? k_lbd<true> : k_lbd<false>, dim3(std::min(L->maxLines, cap), nframes), dim3(64), 0, st, c.ws, P, d_kl, d_counts, d_ldesc, cap);
+        hipLaunchKernelGGL(c.F.lbdRpi ? k_lbd<true> : k_lbd<false>, dim3(std::min(L->maxLines, cap), nframes), dim3(64), 0, st, c.ws, P, d_kl, d_counts, d_ldesc, cap);
     }
 }
 
 // The tail: the NFA stage, the output lines, LBD's gradient image and the descriptors
-static int lines_tail(const LinesCall& c, CoreForm form, size_t nfaStageOff, SideJoin& side, sslam_keyline* d_kl, uint8_t* d_ldesc, double* d_linefn, int32_t* d_counts, int cap) {
-    sslam_lines* L = c.L; const LsdPlan& P = c.P; const int nframes = c.nframes; hipStream_t st = c.st;
+static int lines_tail(const LinesCall& c, size_t nfaStageOff, SideJoin& side, sslam_keyline* d_kl, uint8_t* d_ldesc, double* d_linefn, int32_t* d_counts, int cap) {
+    sslam_lines* L = c.L; const LsdPlan& P = c.P; const LinesForms& F = c.F; const int nframes = c.nframes; hipStream_t st = c.st;
     int rc;
-    // LBD's gradient image needs the source alone and is bandwidth-bound; the NFA stage behind the core is latency-bound (a third of the vector pipes busy): on the side
-    // stream the one runs beside the other instead of behind it -- for a caller WITHOUT a branch of its own beside this one (no core event): 187.5 against 190.1 ms per
-    // one-stream step.  With the point branch still running there (two-stream step) the pair costs 3.5 ms instead (164.1 against 160.2: k_blur_sobel and k_nfa_all are 56 KB
-    // and 54 KB of code, together more than the 64 KB instruction cache two compute units share, beside a third kernel); profiles/r06f_*.  (LBD's blur + Sobel as one more
-    // guest under the core, on the side stream, was measured too: its 126-VGPR waves take the slots FAST needs -- 167.7 ms per step against 160.8 with the kernel in the
-    // tail; profiles/r06d_*.)  The side stream runs k_blur_sobel whenever it was forked: here, or under the streaming NFA stage (lines_core_cluster).
-    if (!side.forked && nframes >= 1024 && !L->coreEvent) {
+    // k_blur_sobel beside the NFA stage where lines_forms says that pays (lines_form.h has the measurements).  The side stream runs it whenever it was forked: here, or under
+    // the streaming NFA stage (lines_core_cluster).
+    if (F.forkBlurSobel) {
         if ((rc = lines_side_stream_ready(L))) return rc;
         SSLAM_HIP(hipEventRecord(L->nfaFork, st));
         SSLAM_HIP(hipStreamWaitEvent(L->nfaStream, L->nfaFork, 0));
@@ -571,10 +520,10 @@ static int lines_tail(const LinesCall& c, CoreForm form, size_t nfaStageOff, Sid
         lines_blur_sobel(c, L->nfaStream);
     }
     // the NFA stage: its kernels and launch forms live in lines_nfa.hip, a translation unit of its own (compiled with -mllvm -disable-machine-licm)
-    if (form == CoreForm::ClusterStream) {      // what the concurrent consumers left (nothing, unless they gave up waiting): the same kernel behind both, everything published, no waiting
+    if (F.nfa == NfaForm::Stream) {      // what the concurrent consumers left (nothing, unless they gave up waiting): the same kernel behind both, everything published, no waiting
         side.join();
-        if ((rc = sslam::launch_nfa_stream(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), L->clFrame, nfaStageOff, nframes, 16, 0, false))) return rc;
-    } else if ((rc = sslam::launch_nfa_stage(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), nframes, L->topnOnly ? L->maxLines : 0, L->lastForms + 4))) return rc;
+        if ((rc = sslam::launch_nfa_stream(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), L->clFrame, nfaStageOff, nframes, LINES_NFA_BEHIND_WAVES, 0, false))) return rc;
+    } else if ((rc = lines_nfa_stage(c))) return rc;
     lines_describe(c, side, d_kl, d_ldesc, d_linefn, d_counts, cap);
     return SSLAM_OK;
 }
@@ -620,22 +569,19 @@ extern "C" int sslam_lines_extract_batch_dev(sslam_lines* L, const uint8_t* d_im
     if (nframes > 1 && image_stride < pitch * (size_t)(h - 1) + (size_t)w) { set_error("sslam_lines_extract_batch_dev: the frames overlap (image_stride < pitch * (h - 1) + w)"); return SSLAM_ERR_INVALID; }
     const LinesKnobs K = lines_knobs();
     std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);      // plan, workspace and profile records are shared state
-    for (int& f : L->lastForms) f = -1;      // (sslam_testing_lines_last_forms: nothing of an earlier call; what this call does not reach stays -1)
+    L->last = {};      // (sslam_testing_lines_last_forms: nothing of an earlier call; what this call does not reach stays -1)
     SSLAM_HIP(hipSetDevice(L->ctx->device));
     hipStream_t st = stream_ ? (hipStream_t)stream_ : L->ctx->stream;
     int rc;
     if ((rc = lines_prepare(L, w, h, nframes, st))) return rc;
     const LsdPlan& P = L->plan;
-    const LinesCall c{L, P, d_images, pitch, image_stride, nframes, st, L->dWs.as<uint8_t>()};
+    const LinesCall c{L, P, d_images, pitch, image_stride, nframes, st, L->dWs.as<uint8_t>(), lines_call_forms(L, nframes, L->topnOnly ? L->maxLines : 0, K)};
     { sslam::ProfScope _ps(L->ctx, "k_zero_misc", st); hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c.ws, P); }
     SideJoin side{L, st};
     if ((rc = lines_prologue(c))) return rc;
-    int grid = 0;
-    const CoreForm form = lines_core_form(L, P, nframes, K, &grid);
-    L->lastForms[0] = (int)form; L->lastForms[1] = form == CoreForm::Guest ? grid : 0;
     size_t nfaStageOff = 0;
-    if ((rc = lines_core(c, K, form, grid, side, &nfaStageOff))) return rc;
-    if ((rc = lines_tail(c, form, nfaStageOff, side, d_kl, d_ldesc, d_linefn, d_counts, cap))) return rc;
+    if ((rc = lines_core(c, side, &nfaStageOff))) return rc;
+    if ((rc = lines_tail(c, nfaStageOff, side, d_kl, d_ldesc, d_linefn, d_counts, cap))) return rc;
     SSLAM_HIP(hipGetLastError());
     L->lastFrames = nframes;
     return SSLAM_OK;
@@ -767,11 +713,41 @@ extern "C" int sslam_lines_debug_cluster(sslam_lines* L, int frame, long long* o
     return SSLAM_OK;
 }
 
-// what the last sslam_lines_extract_batch_dev of the handle chose (sslam_lines::lastForms)
+// what the last batch call of the handle chose (sslam_lines::last) as the eight words of include/sslam_testing.h; -1 for what the call did not reach
 extern "C" int sslam_testing_lines_last_forms(sslam_lines* L, int32_t* out8) {
     if (!L || !out8) { set_error("sslam_testing_lines_last_forms: invalid arguments"); return SSLAM_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
-    for (int i = 0; i < 8; ++i) out8[i] = L->lastForms[i];
+    const LinesForms& F = L->last.forms;
+    for (int i = 0; i < 8; ++i) out8[i] = -1;
+    if (L->last.core) { out8[0] = (int)F.core; out8[1] = F.core == CoreForm::Guest ? F.guestGrid : 0; }
+    out8[2] = L->last.fusedGrad;
+    if (L->last.seedSort) out8[3] = F.sortRuns;
+    if (L->last.nfa) { out8[4] = F.nfa == NfaForm::TopN ? (int)NfaForm::All : (int)F.nfa; out8[5] = F.evalWaves; out8[6] = F.countWaves; }      // (k_nfa_topn reads as k_nfa_all: 2)
+    if (L->last.lbd) out8[7] = F.lbdRpi;
+    return SSLAM_OK;
+}
+
+// What the three taps below do before their own work, as sslam_lines_extract_batch_dev does it: a fresh form record, the frames uploaded at `dev_pitch` (0: the 64-byte-aligned
+// pitch of sslam_lines_extract) and `dev_offset` bytes into the handle's image buffer, lines_prepare, lines_forms, the LinesCall and k_zero_misc.  No tap runs the core, so
+// the NFA stage -- where a tap reaches it -- is the one BEHIND the core whatever SSLAM_NFA_STREAM says.  The caller holds the context's lock.
+static int lines_tap_begin(sslam_lines* L, const char* who, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, size_t dev_pitch, int dev_offset,
+                           int topnMaxLines, std::optional<LinesCall>& c) {
+    if (nframes > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w) { set_error("%s: the frames overlap", who); return SSLAM_ERR_INVALID; }
+    L->last = {};
+    SSLAM_HIP(hipSetDevice(L->ctx->device));
+    hipStream_t st = L->ctx->stream;
+    int rc;
+    const size_t dpitch = dev_pitch ? dev_pitch : (((size_t)w + 63) & ~(size_t)63), dframe = dpitch * h;
+    if ((rc = L->dImg.ensure((size_t)dev_offset + dframe * nframes + 64))) return rc;      // (64: the offset and a dword read that starts inside the last row stay in the buffer)
+    L->lastN = -1;      // (the buffers of the last sslam_lines_extract are overwritten)
+    uint8_t* dimg = L->dImg.as<uint8_t>() + dev_offset;
+    for (int b = 0; b < nframes; ++b)
+        SSLAM_HIP(hipMemcpy2DAsync(dimg + (size_t)b * dframe, dpitch, gray + (size_t)b * image_stride, stride, w, h, hipMemcpyHostToDevice, st));
+    if ((rc = lines_prepare(L, w, h, nframes, st))) return rc;
+    LinesKnobs K = lines_knobs();
+    K.nfaStreamWaves = 0;
+    c.emplace(LinesCall{L, L->plan, dimg, dpitch, dframe, nframes, st, L->dWs.as<uint8_t>(), lines_call_forms(L, nframes, topnMaxLines, K)});
+    hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c->ws, c->P);
     return SSLAM_OK;
 }
 
@@ -784,26 +760,18 @@ extern "C" int sslam_testing_lines_tail(sslam_lines* L, const uint8_t* gray, int
         stride < (size_t)w || (nmax > 0 && !segs)) {
         set_error("sslam_testing_lines_tail: invalid arguments"); return SSLAM_ERR_INVALID;
     }
-    if (nframes > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w) { set_error("sslam_testing_lines_tail: the frames overlap"); return SSLAM_ERR_INVALID; }
     for (int b = 0; b < nframes; ++b)
         if (nsegs[b] < 0 || nsegs[b] > MAX_SEG || nsegs[b] > nmax) { set_error("sslam_testing_lines_tail: frame %d holds %d segments (at most %d)", b, nsegs[b], std::min(nmax, MAX_SEG)); return SSLAM_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
-    SSLAM_HIP(hipSetDevice(L->ctx->device));
-    hipStream_t st = L->ctx->stream;
     int rc;
-    const size_t dpitch = ((size_t)w + 63) & ~(size_t)63, dframe = dpitch * h, rows = (size_t)nframes * cap;
-    if ((rc = L->dImg.ensure(dframe * nframes))) return rc;
+    std::optional<LinesCall> call;
+    if ((rc = lines_tap_begin(L, "sslam_testing_lines_tail", gray, w, h, stride, image_stride, nframes, 0, 0, 0, call))) return rc;
+    const LinesCall& c = *call; const LsdPlan& P = c.P; hipStream_t st = c.st;
+    const size_t rows = (size_t)nframes * cap;
     if ((rc = L->dKl.ensure(sizeof(sslam_keyline) * rows))) return rc;
     if ((rc = L->dDesc.ensure(32 * rows))) return rc;
     if ((rc = L->dFn.ensure(24 * rows))) return rc;
     if ((rc = L->dCounts.ensure(std::max<size_t>(16, sizeof(int32_t) * nframes)))) return rc;
-    L->lastN = -1;      // (the buffers of the last sslam_lines_extract are overwritten)
-    for (int b = 0; b < nframes; ++b)
-        SSLAM_HIP(hipMemcpy2DAsync(L->dImg.as<uint8_t>() + (size_t)b * dframe, dpitch, gray + (size_t)b * image_stride, stride, w, h, hipMemcpyHostToDevice, st));
-    if ((rc = lines_prepare(L, w, h, nframes, st))) return rc;
-    const LsdPlan& P = L->plan;
-    const LinesCall c{L, P, L->dImg.as<uint8_t>(), dpitch, dframe, nframes, st, L->dWs.as<uint8_t>()};
-    hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c.ws, P);
     std::vector<int> flags((size_t)nframes * std::max(nmax, 1), 1);      // (alive until the stream is idle)
     if (accept) for (size_t i = 0; i < (size_t)nframes * nmax; ++i) flags[i] = accept[i] ? 1 : 0;
     for (int b = 0; b < nframes; ++b) {
@@ -844,24 +812,14 @@ extern "C" int sslam_testing_lines_prologue(sslam_lines* L, const uint8_t* gray,
         (dev_pitch != 0 && dev_pitch < (size_t)w) || dev_offset < 0 || dev_offset > 3) {
         set_error("sslam_testing_lines_prologue: invalid arguments"); return SSLAM_ERR_INVALID;
     }
-    if (nframes > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w) { set_error("sslam_testing_lines_prologue: the frames overlap"); return SSLAM_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
-    for (int& f : L->lastForms) f = -1;
-    SSLAM_HIP(hipSetDevice(L->ctx->device));
-    hipStream_t st = L->ctx->stream;
     int rc;
-    const size_t dpitch = dev_pitch ? dev_pitch : (((size_t)w + 63) & ~(size_t)63), dframe = dpitch * h;
-    if ((rc = L->dImg.ensure((size_t)dev_offset + dframe * nframes + 64))) return rc;      // (64: the offset and a dword read that starts inside the last row stay in the buffer)
-    L->lastN = -1;      // (the buffers of the last sslam_lines_extract are overwritten)
-    uint8_t* dimg = L->dImg.as<uint8_t>() + dev_offset;
-    for (int b = 0; b < nframes; ++b)
-        SSLAM_HIP(hipMemcpy2DAsync(dimg + (size_t)b * dframe, dpitch, gray + (size_t)b * image_stride, stride, w, h, hipMemcpyHostToDevice, st));
-    if ((rc = lines_prepare(L, w, h, nframes, st))) return rc;
-    const LsdPlan& P = L->plan;
+    std::optional<LinesCall> call;
+    if ((rc = lines_tap_begin(L, "sslam_testing_lines_prologue", gray, w, h, stride, image_stride, nframes, dev_pitch, dev_offset, 0, call))) return rc;
+    const LinesCall& c = *call; const LsdPlan& P = c.P; hipStream_t st = c.st;
     size_out[0] = P.sw; size_out[1] = P.sh;
     const size_t npx = (size_t)P.npx;
     if (npx > plane_cap) { (void)hipStreamSynchronize(st); set_error("sslam_testing_lines_prologue: %d x %d scaled pixels per frame, the output planes hold %zu", P.sw, P.sh, plane_cap); return SSLAM_ERR_CAPACITY; }
-    const LinesCall c{L, P, dimg, dpitch, dframe, nframes, st, L->dWs.as<uint8_t>()};
     for (int b = 0; b < nframes; ++b) {      // what a kernel does not write still holds 0xA5 afterwards
         uint8_t* base = c.ws + (size_t)b * P.frameBytes;
         SSLAM_HIP(hipMemsetAsync(base + P.offT, 0xA5, sizeof(float) * npx, st));
@@ -869,7 +827,6 @@ extern "C" int sslam_testing_lines_prologue(sslam_lines* L, const uint8_t* gray,
         SSLAM_HIP(hipMemsetAsync(base + P.offCs, 0xA5, sizeof(float2) * npx, st));
         SSLAM_HIP(hipMemsetAsync(base + P.offOrder, 0xA5, sizeof(unsigned) * npx, st));
     }
-    hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c.ws, P);
     if ((rc = lines_prologue(c))) return rc;
     SSLAM_HIP(hipGetLastError());
     L->lastFrames = nframes;
@@ -901,7 +858,7 @@ extern "C" int sslam_testing_lines_grad_table(sslam_lines* L, float* tab_out, in
 }
 
 // The NFA stage on rectangles the caller supplies (include/sslam_testing.h): the upload of sslam_testing_lines_tail, then lines_prepare, k_zero_misc and lines_prologue() --
-// the product path's functions: the T plane is the product's own --, the records and Misc::nCand written where the core leaves them, and sslam::launch_nfa_stage, the one
+// the product path's functions: the T plane is the product's own --, the records and Misc::nCand written where the core leaves them, and lines_nfa_stage, the one
 // function lines_tail calls.  The core does not run (no pixel of T carries the used bit, which the stage masks off anyway), nor does anything behind the stage.
 extern "C" int sslam_testing_lines_nfa(sslam_lines* L, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, const double* rects,
                                        const int32_t* ncand, int nmax, int topn_max_lines, int32_t* flags_out, float* segs_out, int32_t* topn_out) {
@@ -909,7 +866,6 @@ extern "C" int sslam_testing_lines_nfa(sslam_lines* L, const uint8_t* gray, int 
         (nmax > 0 && (!rects || !flags_out || !segs_out))) {
         set_error("sslam_testing_lines_nfa: invalid arguments"); return SSLAM_ERR_INVALID;
     }
-    if (nframes > 1 && image_stride < stride * (size_t)(h - 1) + (size_t)w) { set_error("sslam_testing_lines_nfa: the frames overlap"); return SSLAM_ERR_INVALID; }
     {   // a record the core could not have emitted is refused before anything is launched (the plan's sizes and tolerances as lines_build_plan computes them)
         const int sw = (int)lrint(w * 0.8), sh = (int)lrint(h * 0.8);
         const double prec = kPI * LSD_ANG_TH / 180, p = LSD_ANG_TH / 180;
@@ -931,19 +887,10 @@ extern "C" int sslam_testing_lines_nfa(sslam_lines* L, const uint8_t* gray, int 
         }
     }
     std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
-    for (int& f : L->lastForms) f = -1;
-    SSLAM_HIP(hipSetDevice(L->ctx->device));
-    hipStream_t st = L->ctx->stream;
     int rc;
-    const size_t dpitch = ((size_t)w + 63) & ~(size_t)63, dframe = dpitch * h;
-    if ((rc = L->dImg.ensure(dframe * nframes))) return rc;
-    L->lastN = -1;      // (the buffers of the last sslam_lines_extract are overwritten)
-    for (int b = 0; b < nframes; ++b)
-        SSLAM_HIP(hipMemcpy2DAsync(L->dImg.as<uint8_t>() + (size_t)b * dframe, dpitch, gray + (size_t)b * image_stride, stride, w, h, hipMemcpyHostToDevice, st));
-    if ((rc = lines_prepare(L, w, h, nframes, st))) return rc;
-    const LsdPlan& P = L->plan;
-    const LinesCall c{L, P, L->dImg.as<uint8_t>(), dpitch, dframe, nframes, st, L->dWs.as<uint8_t>()};
-    hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c.ws, P);
+    std::optional<LinesCall> call;
+    if ((rc = lines_tap_begin(L, "sslam_testing_lines_nfa", gray, w, h, stride, image_stride, nframes, 0, 0, topn_max_lines, call))) return rc;
+    const LinesCall& c = *call; const LsdPlan& P = c.P; hipStream_t st = c.st;
     if ((rc = lines_prologue(c))) return rc;
     for (int b = 0; b < nframes; ++b) {      // what the stage does not write still holds 0xA5 afterwards
         uint8_t* base = c.ws + (size_t)b * P.frameBytes;
@@ -953,7 +900,7 @@ extern "C" int sslam_testing_lines_nfa(sslam_lines* L, const uint8_t* gray, int 
         if (ncand[b] > 0) SSLAM_HIP(hipMemcpyAsync(base + P.offCand, rects + (size_t)b * nmax * 12, sizeof(double) * 12 * (size_t)ncand[b], hipMemcpyHostToDevice, st));
         SSLAM_HIP(hipMemcpyAsync(base + P.offMisc + offsetof(Misc, nCand), &ncand[b], sizeof(int), hipMemcpyHostToDevice, st));
     }
-    if ((rc = sslam::launch_nfa_stage(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), nframes, topn_max_lines, L->lastForms + 4))) return rc;
+    if ((rc = lines_nfa_stage(c))) return rc;
     SSLAM_HIP(hipGetLastError());
     L->lastFrames = nframes;
     for (int b = 0; b < nframes; ++b) {

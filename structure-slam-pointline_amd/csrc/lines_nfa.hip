@@ -4,11 +4,11 @@
 // not have at four waves per SIMD, spills them, and reloads them from scratch one at a time with a wait each -- 208 bytes of scratch and 213
 // scratch loads in k_nfa_all.  Without it the constants are rematerialised where they are used: 16 bytes of scratch, 28.4 -> 26.8 ms per
 // 12 288 frames.  The sequential core in lines.hip is the other way round (78.9 -> 79.4 ms without the hoisting), hence two units
-// (docs/history/DESIGN_rounds_1-4.md 5g).  The kernels are launched from here; lines.hip calls sslam::launch_nfa_stage.
+// (docs/history/DESIGN_rounds_1-4.md 5g).  The kernels are launched from here, in the form lines_forms (lines_form.h) chose; lines.hip calls sslam::launch_nfa_stage.
 #include "common.h"
 #include "nfa_topn.h"
+#include "lines_form.h"
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <cfloat>
 #include <algorithm>
@@ -21,37 +21,20 @@ namespace {
 #include "lsd_plan.h"
 #include "lsd_nfa.h"
 
-// The knob of this unit, read on every call (tests set it between calls).  fused: SSLAM_NFA_FUSED=0 forces the 18 launches, =2 the one-wave form, 1 (unset): by batch size.
-struct NfaKnobs { int fused; };
-NfaKnobs nfa_knobs() {
-    NfaKnobs K{1};
-    if (const char* e = getenv("SSLAM_NFA_FUSED")) K.fused = atoi(e) == 2 ? 2 : atoi(e) == 0 ? 0 : 1;
-    return K;
-}
-
 }  // namespace
 
 namespace sslam {
 
-// form3 (unless null): what was chosen -- {1: the 18 launches, 2: k_nfa_all}, evaluating waves per frame, counting waves per frame (sslam_testing_lines_last_forms)
-// topnMaxLines > 0 (sslam_lines_set_topn_only): only that many lines leave a frame, and the one-launch form validates no more candidates than that takes (k_nfa_topn,
-// lsd_nfa.h); the 18 launches validate everything as before.
-int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes, int topnMaxLines, int* form3) {
+// The stage behind the core in the form lines_forms chose (lines_form.h): the 18 launches with countWaves / evalWaves waves per frame, k_nfa_all, or k_nfa_topn with the
+// topnMaxLines lines that leave a frame (sslam_lines_set_topn_only).  Nothing is decided here and no environment is read.
+int launch_nfa_stage(sslam_ctx* ctx, hipStream_t st, uint8_t* ws, const void* plan, size_t planBytes, const double* lgam, int nframes, NfaForm form, int evalWaves, int countWaves, int topnMaxLines) {
     if (planBytes != sizeof(LsdPlan)) { set_error("launch_nfa_stage: plan layout mismatch between translation units"); return SSLAM_ERR_INVALID; }
+    if (form == NfaForm::Stream || evalWaves < 1 || countWaves < 1) { set_error("launch_nfa_stage: not a form of the stage behind the core"); return SSLAM_ERR_INVALID; }
     LsdPlan P; memcpy(&P, plan, sizeof(P));
-    const NfaKnobs K = nfa_knobs();
-    const int evalWaves = nframes >= 1024 ? 1 : nframes >= 64 ? 4 : nframes >= 16 ? 16 : 32;      // waves per frame walking the NFA evaluations
-    const int countWaves = nframes >= 2048 ? 1 : nframes >= 128 ? 8 : nframes >= 16 ? 64 : 128;   // waves per frame walking the rectangle counts (round 4: 128 / 32 for a handful of frames, 6.25 -> 6.09 ms per frame)
-    // The whole NFA stage as ONE launch (lsd_nfa.h): one wave per frame when the frames themselves fill the chip (k_nfa_all, calls of >= 2048 frames).
-    // Below that the 18 launches stay: a single frame's stage is bound by the work of each wave, not by launch boundaries (kernel durations add up
-    // to the stage's 0.6 ms; a one-workgroup form with sixteen waves was measured at 6.42 / 7.70 ms p50 / p90 per frame against 6.25 / 7.40 and removed in round 5).
-    // What helped instead: 128 counting and 32 evaluating waves per frame (6.09 / 7.16).
-    const bool nfaFused = K.fused == 2 || (K.fused != 0 && countWaves == 1 && evalWaves == 1);
-    if (form3) { form3[0] = nfaFused ? 2 : 1; form3[1] = nfaFused ? 1 : evalWaves; form3[2] = nfaFused ? 1 : countWaves; }
-    if (nfaFused && topnMaxLines > 0) {
+    if (form == NfaForm::TopN) {
         sslam::ProfScope _ps(ctx, "k_nfa_all", st);
         hipLaunchKernelGGL(k_nfa_topn<768>, dim3(nframes), dim3(64), 0, st, ws, P, lgam, topnMaxLines);
-    } else if (nfaFused) {
+    } else if (form == NfaForm::All) {
         sslam::ProfScope _ps(ctx, "k_nfa_all", st);
         hipLaunchKernelGGL(k_nfa_all<768>, dim3(nframes), dim3(64), 0, st, ws, P, lgam);
     } else {

@@ -847,15 +847,8 @@ class LineExtractor:
     NFA_FORMS = ("stream", "launches", "all")
 
     def last_forms(self):
-        """sslam_testing_lines_last_forms (include/sslam_testing.h): what the last batch call of this handle chose -> dict(core, grid, fused_grad, sort_runs, nfa, eval_waves,
-        count_waves, lbd_rpi).  The testing library reads the handle's plain fields, whichever of the two libraries made it."""
-        o = (C.c_int32 * 8)()
-        rc = testing_lib().sslam_testing_lines_last_forms(self.h, o)
-        if rc != 0:
-            raise SslamError("sslam_testing_lines_last_forms: %d" % rc, rc)
-        flag = lambda v: bool(v) if v >= 0 else None          # -1: the call did not get there
-        return dict(core=self.CORE_FORMS[o[0]] if o[0] >= 0 else None, grid=o[1], fused_grad=flag(o[2]), sort_runs=flag(o[3]),
-                    nfa=self.NFA_FORMS[o[4]] if o[4] >= 0 else None, eval_waves=o[5], count_waves=o[6], lbd_rpi=o[7])
+        """what the last batch call of this handle chose (line_last_forms).  The testing library reads the handle's plain fields, whichever of the two libraries made it."""
+        return line_last_forms(self.h)
 
     def batch_status(self, cap, stream=None):
         """sslam_lines_batch_status -> (status code, frames over capacity, frames over the LSD limit, first such frame or -1)"""
@@ -867,6 +860,18 @@ class LineExtractor:
         if self.h:
             lib().sslam_lines_destroy(self.h)
             self.h = C.c_void_p()
+
+
+def line_last_forms(handle):
+    """sslam_testing_lines_last_forms (include/sslam_testing.h) of a sslam_lines handle -> dict(core, grid, fused_grad, sort_runs, nfa, eval_waves, count_waves, lbd_rpi);
+    core, fused_grad, sort_runs and nfa are None where the call did not get there (-1 in the other words)"""
+    o = (C.c_int32 * 8)()
+    rc = testing_lib().sslam_testing_lines_last_forms(handle, o)
+    if rc != 0:
+        raise SslamError("sslam_testing_lines_last_forms: %d" % rc, rc)
+    flag = lambda v: bool(v) if v >= 0 else None
+    return dict(core=LineExtractor.CORE_FORMS[o[0]] if o[0] >= 0 else None, grid=o[1], fused_grad=flag(o[2]), sort_runs=flag(o[3]),
+                nfa=LineExtractor.NFA_FORMS[o[4]] if o[4] >= 0 else None, eval_waves=o[5], count_waves=o[6], lbd_rpi=o[7])
 
 
 class LinePrologue:
@@ -914,9 +919,8 @@ class LinePrologue:
 
     def last_forms(self):
         """words 2 and 3 of sslam_testing_lines_last_forms as (fused_grad, sort_runs): True / False, None where the call did not get there"""
-        o = (C.c_int32 * 8)()
-        self._chk(self.T.sslam_testing_lines_last_forms(self.h, o))
-        return tuple(bool(v) if v >= 0 else None for v in (o[2], o[3]))
+        f = line_last_forms(self.h)
+        return f["fused_grad"], f["sort_runs"]
 
     def set_resize_variant(self, variant): self._chk(self.T.sslam_lines_set_resize_variant(self.h, int(variant)))
 
@@ -974,14 +978,9 @@ class LineNfaStage:
         return out
 
     def last_forms(self):
-        """words 2 .. 6 of sslam_testing_lines_last_forms -> dict(fused_grad, sort_runs, nfa, eval_waves, count_waves); the tap runs no core"""
-        o = (C.c_int32 * 8)()
-        rc = self.T.sslam_testing_lines_last_forms(self.h, o)
-        if rc != 0:
-            raise SslamError("sslam_testing_lines_last_forms: %d" % rc, rc)
-        flag = lambda v: bool(v) if v >= 0 else None
-        return dict(core=LineExtractor.CORE_FORMS[o[0]] if o[0] >= 0 else None, fused_grad=flag(o[2]), sort_runs=flag(o[3]),
-                    nfa=LineExtractor.NFA_FORMS[o[4]] if o[4] >= 0 else None, eval_waves=o[5], count_waves=o[6])
+        """words 0 and 2 .. 6 of sslam_testing_lines_last_forms -> dict(core, fused_grad, sort_runs, nfa, eval_waves, count_waves); the tap runs no core"""
+        f = line_last_forms(self.h)
+        return {k: f[k] for k in ("core", "fused_grad", "sort_runs", "nfa", "eval_waves", "count_waves")}
 
     def close(self):
         if self.h:
