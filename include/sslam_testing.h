@@ -74,7 +74,7 @@ int sslam_testing_lines_tail(sslam_lines* ln, const uint8_t* gray, int w, int h,
  * form's grid (0 otherwise), out[2] = the gradient came from the fused blur + gradient kernel, out[3] = the seeds were sorted by the tile-sorted runs kernels, out[4] = the NFA
  * stage (0 streaming beside the core, 1 the 18 launches, 2 k_nfa_all), out[5] / out[6] = its evaluating / counting waves per frame (streaming: the consumer waves and 0),
  * out[7] = k_lbd's template argument.  Every call starts with -1 in all eight, so a word the call did not reach (before the first call; a call that failed early; out[3]
- * under sslam_lines_set_seed_order(1), where the host sorts) is -1 and never another call's choice; the three taps of this header start the same way.  The handle keeps what lines_forms
+ * under sslam_lines_set_seed_order(1), where the host sorts) is -1 and never another call's choice; the four line taps of this header start the same way.  The handle keeps what lines_forms
  * (csrc/lines_form.h) decided for the call and how far the call got; this function alone turns that into the eight words. */
 int sslam_testing_lines_last_forms(sslam_lines* ln, int32_t out[8]);
 
@@ -120,6 +120,27 @@ int sslam_testing_lines_grad_table(sslam_lines* ln, float* tab_out, int32_t* smi
  * meaningful there.  The handle must have been created by THIS library. */
 int sslam_testing_lines_nfa(sslam_lines* ln, const uint8_t* gray, int w, int h, size_t stride, size_t image_stride, int nframes, const double* rects, const int32_t* ncand,
                             int nmax, int topn_max_lines, int32_t* flags_out, float* segs_out, int32_t* topn_out);
+
+/* The sequential LSD core -- region growing, region2rect, refine() and reduce_region_radius() of LineSegmentDetectorImpl::flsd's seed loop (OpenCV imgproc lsd.cpp, reached from
+ * src/ExtractLineSegment.cpp:38-40) as k_lsd_regions (csrc/lsd_regions.h: lone wave, guest, four- and six-wave workgroups) or k_lsd_regions_cl (csrc/lsd_cluster.h) -- ALONE, with
+ * everything it leaves copied back, so that a test can compare EVERY candidate rectangle (also those the NFA stage rejects) in all twelve doubles, and the used map, with the
+ * oracle instead of through the float32 segments that survive two stages later.  Two steps.
+ * sslam_testing_lines_core, the run step: `nframes` gray images of one size ON THE DEVICE, the layout arguments of sslam_lines_extract_batch_dev (a batch form needs thousands
+ * of frames).  It sets the words of sslam_testing_lines_last_forms to -1 and runs lines_prepare, k_zero_misc, lines_prologue() and lines_core() -- the functions of
+ * sslam_lines_extract_batch_dev, the core's launch included: the form is lines_forms' (csrc/lines_form.h) from the knobs as they stand, `nframes` and the core event, and is
+ * recorded as on the product path (words 0 .. 3) -- and nothing behind the core: words 4 .. 7 stay -1.  ONE exception: CoreForm::ClusterStream is coupled to its consumers, so
+ * for it the step runs what the product runs, k_nfa_stream beside the core and behind it (one shared function), and words 4 .. 6 read as on the product path.  After the prologue and
+ * before the core's launch every frame's candidate region (and, under the streaming form, the staged rectangles of its cluster slot) is filled with the byte 0xA5.  The step runs
+ * on the context's stream and returns with it idle.
+ * sslam_testing_lines_core_frame, the copy-back step, for frame `frame` of the last run step (SSLAM_ERR_INVALID if the handle's last call was anything else): size_out[2] = the
+ * scaled size sw x sh, *ncand_out = Misc::nCand, rects_out[nmax][12] = the first min(nmax, 8192) RectD records in emission order, copied WHOLE from where the form leaves them
+ * -- the frame's candidate region; under the streaming form the staging array of the frame's cluster slot, which the main wave alone writes (k_nfa_stream copies a record into
+ * the workspace before rect_improve changes it there, so the staged records are still the core's own after the stage) -- so rows at or past nCand still hold the fill; t_out
+ * (may be NULL; plane_cap pixels, SSLAM_ERR_CAPACITY if sw * sh is more) = the T plane as [sh][sw] floats: the level-line angle with the USED bit in the sign (a pixel is used
+ * iff it is defined, i.e. not -1024, and its sign bit is set).  A frame of more than 8 192 candidates returns SSLAM_ERR_UNSUPPORTED naming the limit, as sslam_lines_extract
+ * does, with every output filled.  The handle must have been created by THIS library. */
+int sslam_testing_lines_core(sslam_lines* ln, const uint8_t* d_images, int w, int h, size_t pitch, size_t image_stride, int nframes);
+int sslam_testing_lines_core_frame(sslam_lines* ln, int frame, int nmax, size_t plane_cap, int32_t size_out[2], int32_t* ncand_out, double* rects_out, float* t_out);
 
 /* The ORB tail -- k_octree (DistributeOctTree, src/ORBextractor.cc:539-763) and k_describe (IC_Angle, the 7x7 blur, computeOrbDescriptor and the KeyPoint fill, :77-147,
  * :835-847, :1085-1101) -- on FAST candidates the CALLER supplies in place of k_fast_cells', so that a test can drive the two kernels at their own edges.  `nframes` gray

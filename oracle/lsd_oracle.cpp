@@ -78,6 +78,23 @@ struct LsdTrace {
 };
 static_assert(sizeof(LsdTrace) == 64 * sizeof(int), "LsdTrace is 64 ints");
 
+// What the sequential core of a run of Lsd::detect -- the seed loop, region_grow, region2rect, refine, reduce_region_radius -- did and left (orc_lsd_core): filled by the
+// detector's own functions when Lsd::core is set, so the export is the loop itself and no restatement of it.  tests/lsd_core_cases.py and tests/test_lsd_core_gpu.py
+// compare the device's core with it record for record and pixel for pixel.
+struct LsdCoreCand { double rec[12]; int x, y, points, reach, regrew, reduced, bx0, by0, bx1, by1; };      // the record as region2rect / refine left it, the seed, the points the record was made of,
+                                                                                       // the largest Chebyshev distance from the seed of any point the region ever held (first
+                                                                                       // growth and every regrowth), whether refine() regrew and whether reduce_region_radius ran,
+                                                                                       // the box of the points the record was made of
+struct LsdCoreSeed { int x, y, first, listLen; };      // every seed that grew a region: the points of its first growth; those plus the points of refine()'s regrowth, if it regrew
+                                                       // (csrc/lsd_regions.h MwRes: nA + nB, the length the cluster form's feeder compares with CL_STG)
+struct LsdCore {
+    std::vector<LsdCoreCand> cands;
+    std::vector<LsdCoreSeed> seeds;
+    long long blockedJoins = 0;      // (region, neighbour) tests of region_grow in which the neighbour was USED by an EARLIER seed and isAligned accepts it: where the sequential order decides
+    std::vector<int> owner;          // per pixel: the ordinal (from 1) of the seed whose growth marked it last
+    int cur = 0, reach = 0, regrew = 0, reduced = 0;      // the seed in progress
+};
+
 // ll_angle's per-pixel expressions, ONE copy for the detector and for the exports orc_lsd_prologue / orc_lsd_grad_table: the gradient magnitude |g| / 2 of the 2 x 2
 // differences (gx, gy), whether it is above the threshold, and then the level-line angle in DEGREES (fast_atan2's value; ll_angle stores it times DEG_TO_RADS)
 struct LlPixel { double norm; bool defined; float deg; };
@@ -88,12 +105,33 @@ static inline LlPixel ll_pixel(int gx, int gy, double threshold) {
     q.deg = q.defined ? fast_atan2(float(gx), float(-gy)) : float(NOTDEF);
     return q;
 }
+// region2rect's dx = cos(theta), dy = sin(theta), CORRECTLY ROUNDED (decision D18).  The reference calls libm's cos and sin on a double, whose results are the correctly
+// rounded ones in all but about one argument in 750 (glibc, measured on random arguments of [0, 10]) but are not specified to be; the device library's are merely faithful (one theta in fifteen rounds the other way).  No
+// two implementations agree on every argument unless both round correctly, so that is the contract here and in csrc/sincos_cr.h: evaluated in binary128 (compiler
+// arithmetic: no library), theta in [0, 10], by the series after the reduction by a multiple of pi/2 -- about 2^-108 before the one rounding to double.
+static inline void cr_sincos(double x, double& sn, double& cs) {
+    typedef __float128 Q;
+    static const Q PIO2 = (Q)0x1.921fb54442d18p+0 + (Q)0x1.1a62633145c07p-54 + (Q)-0x1.f1976b7ed8fbcp-110;      // three doubles: their sum is pi/2 to binary128's last bit
+    const int k = (int)(x * 0.63661977236758134308 + 0.5);
+    const Q r = (Q)x - (Q)k * PIO2, z = r * r;
+    Q s = 0, c = 0, ts = r, tc = 1;
+    for (int i = 1; i <= 40; ++i) { s += ts; c += tc; tc = -tc * z / (Q)((2 * i - 1) * (2 * i)); ts = -ts * z / (Q)((2 * i) * (2 * i + 1)); }
+    const double sd = (double)s, cd = (double)c;
+    switch (k & 3) {
+        case 0: sn = sd; cs = cd; break;
+        case 1: sn = cd; cs = -sd; break;
+        case 2: sn = -sd; cs = -cd; break;
+        default: sn = -cd; cs = sd; break;
+    }
+}
+extern "C" void orc_cr_sincos(double x, double* sn, double* cs) { cr_sincos(x, *sn, *cs); }
 // the direction region_grow adds to its sums for a pixel it accepts, from the angle ll_angle stored for it (radians): decision D5
 static inline void grow_direction(double angle, float& c, float& s) { c = cr_cosf(float(angle)); s = cr_sinf(float(angle)); }
 
 struct Lsd {
     LsdTrace* tr = nullptr;               // orc_lsd_trace
     std::vector<int>* segCand = nullptr;  // per emitted segment, the ordinal of its candidate rectangle (regions past refine, seed order)
+    LsdCore* core = nullptr;              // orc_lsd_core
     // LSD_REFINE_ADV defaults of createLineSegmentDetector
     const double SCALE = 0.8, SIGMA_SCALE = 0.6, QUANT = 2.0, ANG_TH = 22.5, LOG_EPS = 0, DENSITY_TH = 0.7;
     const int N_BINS = 1024;
@@ -171,6 +209,7 @@ struct Lsd {
         reg.push_back(seed);
         float sumdx = float(std::cos(reg_angle)), sumdy = float(std::sin(reg_angle));
         used[(size_t)sy * w + sx] = 1;
+        if (core) core->owner[(size_t)sy * w + sx] = core->cur;
         for (size_t i = 0; i < reg.size(); ++i) {
             const int px = reg[i].x, py = reg[i].y;
             int xx_min = std::max(px - 1, 0), xx_max = std::min(px + 1, w - 1);
@@ -181,13 +220,14 @@ struct Lsd {
                     if (is_used != 1 && isAligned(xx, yy, reg_angle, prec)) {
                         const double angle = angles[(size_t)yy * w + xx];
                         is_used = 1;
+                        if (core) { core->owner[(size_t)yy * w + xx] = core->cur; core->reach = std::max(core->reach, std::max(std::abs(xx - sx), std::abs(yy - sy))); }
                         RegionPoint rp; rp.x = xx; rp.y = yy; rp.modgrad = modgrad[(size_t)yy * w + xx]; rp.angle = angle;
                         reg.push_back(rp);
                         float dc, ds; grow_direction(angle, dc, ds);       // D5
                         sumdx += dc;
                         sumdy += ds;
                         reg_angle = fast_atan2(sumdy, sumdx) * DEG_TO_RADS;
-                    }
+                    } else if (core && is_used == 1 && core->owner[(size_t)yy * w + xx] != core->cur && isAligned(xx, yy, reg_angle, prec)) ++core->blockedJoins;
                 }
         }
     }
@@ -215,7 +255,8 @@ struct Lsd {
         }
         x /= sum; y /= sum;
         double theta = get_theta(reg, x, y, reg_angle, prec);
-        double dx = std::cos(theta), dy = std::sin(theta);
+        double dx, dy;
+        cr_sincos(theta, dy, dx);          // D18 (std::cos, std::sin upstream)
         double l_min = 0, l_max = 0, w_min = 0, w_max = 0;
         for (size_t i = 0; i < reg.size(); ++i) {
             double regdx = double(reg[i].x) - x, regdy = double(reg[i].y) - y;
@@ -234,6 +275,7 @@ struct Lsd {
         double radSq = radSq1 > radSq2 ? radSq1 : radSq2;
         while (density < density_th) {
             if (tr) { ++tr->reduceIters; if (reg.size() > 768) ++tr->reduceItersBig; }
+            if (core) core->reduced = 1;
             radSq *= 0.75 * 0.75;
             for (size_t i = 0; i < reg.size(); ++i) {
                 if (distSq(xc, yc, double(reg[i].x), double(reg[i].y)) > radSq) {
@@ -270,6 +312,7 @@ struct Lsd {
         int sx = reg[0].x, sy = reg[0].y;
         region_grow(sx, sy, reg, reg_angle, tau);
         if (tr && (int)reg.size() > tr->regrownMax) tr->regrownMax = (int)reg.size();
+        if (core) { core->regrew = 1; core->seeds.back().listLen += (int)reg.size(); }
         if (reg.size() < 2) return false;
         region2rect(reg, reg_angle, prec, p, rec);
         density = double(reg.size()) / (dist(rec.x1, rec.y1, rec.x2, rec.y2) * rec.width);
@@ -444,11 +487,14 @@ struct Lsd {
         int cand = 0;
         if (tr) { *tr = LsdTrace(); tr->sw = w; tr->sh = h; tr->minRegSize = (int)min_reg_size; for (double a : angles) if (a != NOTDEF) ++tr->defined; }
         if (segCand) segCand->clear();
+        if (core) { *core = LsdCore(); core->owner.assign((size_t)w * h, 0); }
         for (size_t i = 0; i < order.size(); ++i) {
             const int idx = order[i], px = idx % w, py = idx / w;
             if (used[idx] == 0 && angles[idx] != NOTDEF) {
                 double reg_angle;
+                if (core) { ++core->cur; core->reach = core->regrew = core->reduced = 0; }
                 region_grow(px, py, reg, reg_angle, prec);
+                if (core) core->seeds.push_back({px, py, (int)reg.size(), (int)reg.size()});
                 if (tr) {
                     const int n = (int)reg.size();
                     ++tr->seeds;
@@ -470,6 +516,15 @@ struct Lsd {
                 if (!refine(reg, reg_angle, prec, p, rec, DENSITY_TH)) { if (tr) ++tr->refineFalse; continue; }
                 const int ordinal = cand++;
                 if (tr) ++tr->candidates;
+                if (core) {
+                    LsdCoreCand c;
+                    static_assert(sizeof(Rect) == sizeof(c.rec), "a record is twelve doubles");
+                    std::memcpy(c.rec, &rec, sizeof(rec));
+                    c.x = px; c.y = py; c.points = (int)reg.size(); c.reach = core->reach; c.regrew = core->regrew; c.reduced = core->reduced;
+                    c.bx0 = c.bx1 = reg[0].x; c.by0 = c.by1 = reg[0].y;
+                    for (const RegionPoint& q : reg) { c.bx0 = std::min(c.bx0, q.x); c.bx1 = std::max(c.bx1, q.x); c.by0 = std::min(c.by0, q.y); c.by1 = std::max(c.by1, q.y); }
+                    core->cands.push_back(c);
+                }
                 double log_nfa = rect_improve(rec);
                 if (log_nfa <= LOG_EPS) continue;
                 if (tr) ++tr->segments;
@@ -550,6 +605,29 @@ extern "C" int orc_lsd_trace(const uint8_t* gray, int w, int h, size_t stride, i
         if (cand_out) cand_out[i] = sc[i];
     }
     return n;
+}
+// Lsd::detect with its core record (LsdCore): size_out[2] = the scaled size; with the outputs null a first call asks for the sizes.  rects_out[ccap][12] and
+// cand_out[ccap][10] = per candidate in emission order the first record and {seed x, seed y, points, reach, regrew, reduced, the points' box x0, y0, x1, y1}; seed_out[scap][4] = per seed that grew a region
+// {x, y, points of the first growth, list length}; used_out[sh * sw] = the detector's used map when the loop ends (1 = USED: also a region below min_reg_size and a region
+// refine() gave up on); stat_out[4] = candidates, seeds, blocked joins, min_reg_size.  Rows past a capacity are dropped; returns the number of candidates.
+extern "C" int orc_lsd_core(const uint8_t* gray, int w, int h, size_t stride, int32_t* size_out, double* rects_out, int32_t* cand_out, int ccap, int32_t* seed_out, int scap,
+                            uint8_t* used_out, int64_t* stat_out) {
+    Img8 im(w, h);
+    for (int y = 0; y < h; ++y) std::memcpy(im.row(y), gray + (size_t)y * stride, (size_t)w);
+    Lsd lsd; LsdCore c; std::vector<Seg4f> segs;
+    lsd.core = &c;
+    lsd.detect(im, segs);
+    if (size_out) { size_out[0] = lsd.w; size_out[1] = lsd.h; }
+    const int nc = (int)c.cands.size(), ns = (int)c.seeds.size();
+    for (int i = 0; i < nc && i < ccap; ++i) {
+        const LsdCoreCand& q = c.cands[i];
+        if (rects_out) std::memcpy(rects_out + (size_t)i * 12, q.rec, sizeof(q.rec));
+        if (cand_out) { int32_t* o = cand_out + (size_t)i * 10; o[0] = q.x; o[1] = q.y; o[2] = q.points; o[3] = q.reach; o[4] = q.regrew; o[5] = q.reduced; o[6] = q.bx0; o[7] = q.by0; o[8] = q.bx1; o[9] = q.by1; }
+    }
+    if (seed_out) for (int i = 0; i < ns && i < scap; ++i) { int32_t* o = seed_out + (size_t)i * 4; o[0] = c.seeds[i].x; o[1] = c.seeds[i].y; o[2] = c.seeds[i].first; o[3] = c.seeds[i].listLen; }
+    if (used_out) for (size_t i = 0; i < lsd.used.size(); ++i) used_out[i] = lsd.used[i] == 1;
+    if (stat_out) { stat_out[0] = nc; stat_out[1] = ns; stat_out[2] = c.blockedJoins; stat_out[3] = (int64_t)size_t(-lsd.LOG_NT / std::log10(lsd.ANG_TH / 180)); }
+    return nc;
 }
 // What flsd leaves for region growing (Lsd::prologue), under orc_set_lsd_resize / orc_set_lsd_seed_sort as every other entry.  size_out[2] = scaled width and height; with
 // planes to fill (any of them may be null; a first call with all null asks for the size): per scaled pixel deg_out = the level-line angle in degrees (fast_atan2's value

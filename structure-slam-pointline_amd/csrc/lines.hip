@@ -17,6 +17,7 @@
 #include "common.h"
 #include "nfa_topn.h"
 #include "lines_form.h"
+#include "sincos_cr.h"
 #include <cmath>
 #include <cstdlib>
 #include <cfloat>
@@ -95,6 +96,7 @@ struct sslam_lines {
         LinesForms forms{};
         int fusedGrad = -1;                  // lines_prologue's own choice (pointer and pitch alignment, fusedGeometry); -1: not reached
         bool seedSort = false, core = false, nfa = false, lbd = false;      // reached: the seed sort on the device, the core, the NFA stage, k_lbd
+        bool coreTap = false; size_t coreTapStageOff = 0;      // the call was sslam_testing_lines_core; where a cluster slot holds the streaming form's rectangles
     } last;
 };
 
@@ -327,6 +329,7 @@ static_assert(LINES_CLUSTER_LDS_SW == TorusFrame::XMASK + 1 && LINES_CLUSTER_LDS
 constexpr int CL_MAXFRAMES = 8 * 8;      // the cluster form's grid (lines_core_cluster): eight XCDs, up to eight frames on each -- at four workgroups a frame they fill its 32 compute units
 static_assert(LINES_CLUSTER_MAX_FRAMES == CL_MAXFRAMES, "lines_forms sends no more frames to the cluster form than its grid is laid out for");
 static_assert(LINES_CL_MAXWG == CL_MAXWG && LINES_CL_SUB == CL_SUB, "lsd_cluster.h: lines_knobs_from clamps SSLAM_CL_WGS and sizes the default window with these");
+static_assert(CL_STG == 32 && ClTorus::REACH == 254 && QCAP == 768, "tests/lsd_core_cases.py holds these as CL_STG and TORUS_REACH and places frames on both sides of each (reach 253 / 254 / 255, list lengths 32 / 33, regions around 768 points): move the frames with the constants");
 static_assert(LINES_SORT_RUNS_MAX_SIDE == 1 << SORT_XY_BITS, "a sorted entry packs x and y into SORT_XY_BITS bits each (lsd_front.h)");
 
 // Whether a batch of `nframes` would find room for the core's guest form (lines_forms' guestFits: the image size does not enter it).  sslam_frontend_batch and the pipeline ask
@@ -420,6 +423,22 @@ static int lines_prologue(const LinesCall& c) {
     return SSLAM_OK;
 }
 
+// A cluster slot (one per frame of the call, in sslam_lines::dCl): the zeroed head -- control block, sub-chunk states / flags, shared map (+ the main wave's bitmap) --, two
+// result records per seed position, one 256 KB list arena per HELPER THAT EXISTS ((nWG - 1) x CL_HPW: 27 by default; rounds 1-3 sized it for 64), and under
+// CoreForm::ClusterStream the rectangles of the streaming NFA stage (k_lsd_regions_cl<1>: cl.candStage).  lines_core_cluster lays the slots out by it; the testing library's
+// sslam_testing_lines_core fills the staged rectangles before the launch and sslam_testing_lines_core_frame reads them back.
+struct ClLayout { int specWords; size_t zeroBytes, stageOff, frameBytes; };
+static ClLayout lines_cluster_layout(const LsdPlan& P, const LinesForms& F) {
+    ClLayout y;
+    const int clShift = F.clSmap;
+    y.specWords = clShift < 0 ? 0 : (((P.sw + (1 << clShift) - 1) >> clShift) * ((P.sh + (1 << clShift) - 1) >> clShift) + 31) / 32;
+    const size_t maxSubs = ((size_t)P.npx + CL_SUB - 1) / CL_SUB;
+    y.zeroBytes = 512 + ((maxSubs * sizeof(ClSub) + 511) & ~(size_t)511) + 4 * (size_t)((y.specWords + 127) & ~127) + (F.bigFrame ? 4 * (size_t)TorusGlobal::WORDS : 0);
+    y.stageOff = y.zeroBytes + maxSubs * CL_RES * sizeof(ClRec) + 4 * (size_t)CL_ARENA * (size_t)std::max(1, (F.clWgs - 1) * CL_HPW);
+    y.frameBytes = align_up(y.stageOff + (F.core == CoreForm::ClusterStream ? sizeof(double) * 12 * (size_t)MAX_SEG : 0), 4096);
+    return y;
+}
+
 // The cluster form of the core.  Under CoreForm::ClusterStream the NFA stage runs NEXT TO the core on the side stream, on the rectangles the main wave has published so far
 // (lsd_nfa.h, k_nfa_stream).  *nfaStageOff: where the frames' rectangles for that stage lie in a cluster slot.
 static int lines_core_cluster(const LinesCall& c, SideJoin& side, size_t* nfaStageOff) {
@@ -427,14 +446,10 @@ static int lines_core_cluster(const LinesCall& c, SideJoin& side, size_t* nfaSta
     int rc;
     const bool streamNfa = F.core == CoreForm::ClusterStream, bigFrame = F.bigFrame;
     const int window = F.clWindow, clShift = F.clSmap, nWG = F.clWgs;
-    const int clSpecWords = clShift < 0 ? 0 : (((P.sw + (1 << clShift) - 1) >> clShift) * ((P.sh + (1 << clShift) - 1) >> clShift) + 31) / 32;
-    const size_t maxSubs = ((size_t)P.npx + CL_SUB - 1) / CL_SUB;
-    const size_t zeroBytes = 512 + ((maxSubs * sizeof(ClSub) + 511) & ~(size_t)511) + 4 * (size_t)((clSpecWords + 127) & ~127) + (bigFrame ? 4 * (size_t)TorusGlobal::WORDS : 0);      // control block, sub-chunk states / flags, shared map (+ the main wave's bitmap)
-    // per frame: the zeroed head, two result records per seed position, one 256 KB list arena per HELPER THAT EXISTS ((nWG - 1) x CL_HPW: 27 by default;
-    // rounds 1-3 sized it for 64), and the rectangles of the streaming NFA stage.  One slot per frame of the call: blocks with b >= nframes return at once, so the
-    // XCD-aligned grid needs no padding slots (a single 640x480 frame held 8 slots of 30 MB before).
-    const size_t stageOff = zeroBytes + maxSubs * CL_RES * sizeof(ClRec) + 4 * (size_t)CL_ARENA * (size_t)std::max(1, (nWG - 1) * CL_HPW);      // (k_lsd_regions_cl<1>: cl.candStage)
-    const size_t clFrame = align_up(stageOff + (streamNfa ? sizeof(double) * 12 * (size_t)MAX_SEG : 0), 4096);
+    // One slot per frame of the call: blocks with b >= nframes return at once, so the XCD-aligned grid needs no padding slots (a single 640x480 frame held 8 slots of 30 MB before).
+    const ClLayout lay = lines_cluster_layout(P, F);
+    const int clSpecWords = lay.specWords;
+    const size_t zeroBytes = lay.zeroBytes, stageOff = lay.stageOff, clFrame = lay.frameBytes;
     L->clFrame = clFrame; L->clSlots = nframes;
     const size_t clSlots = (size_t)nframes;
     if (L->dCl.cap < clFrame * clSlots) { SSLAM_HIP(hipStreamSynchronize(st)); if ((rc = L->dCl.ensure(clFrame * clSlots))) return rc; }
@@ -492,6 +507,14 @@ static int lines_nfa_stage(const LinesCall& c) {
     return sslam::launch_nfa_stage(L->ctx, c.st, c.ws, &c.P, sizeof(c.P), L->dLgam.as<double>(), c.nframes, F.nfa, F.evalWaves, F.countWaves, F.topnMaxLines);
 }
 
+// Behind the STREAMING core: what the concurrent consumers left (nothing, unless they gave up waiting) -- the same kernel behind both, everything published, no waiting
+// (lines_tail and the testing library's sslam_testing_lines_core)
+static int lines_nfa_stream_behind(const LinesCall& c, size_t nfaStageOff, SideJoin& side) {
+    sslam_lines* L = c.L;
+    side.join();
+    return sslam::launch_nfa_stream(L->ctx, c.st, c.ws, &c.P, sizeof(c.P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), L->clFrame, nfaStageOff, c.nframes, LINES_NFA_BEHIND_WAVES, 0, false);
+}
+
 // Behind the NFA stage: the output lines (KeyLine fill, top-N, line equations), LBD's gradient image unless the side stream has it, and the descriptors.  What lines_tail
 // and the testing library's sslam_testing_lines_tail (segments injected in place of the NFA stage's) share.
 static void lines_describe(const LinesCall& c, SideJoin& side, sslam_keyline* d_kl, uint8_t* d_ldesc, double* d_linefn, int32_t* d_counts, int cap) {
@@ -520,10 +543,8 @@ static int lines_tail(const LinesCall& c, size_t nfaStageOff, SideJoin& side, ss
         lines_blur_sobel(c, L->nfaStream);
     }
     // the NFA stage: its kernels and launch forms live in lines_nfa.hip, a translation unit of its own (compiled with -mllvm -disable-machine-licm)
-    if (F.nfa == NfaForm::Stream) {      // what the concurrent consumers left (nothing, unless they gave up waiting): the same kernel behind both, everything published, no waiting
-        side.join();
-        if ((rc = sslam::launch_nfa_stream(L->ctx, st, c.ws, &P, sizeof(P), L->dLgam.as<double>(), L->dCl.as<uint8_t>(), L->clFrame, nfaStageOff, nframes, LINES_NFA_BEHIND_WAVES, 0, false))) return rc;
-    } else if ((rc = lines_nfa_stage(c))) return rc;
+    if (F.nfa == NfaForm::Stream) { if ((rc = lines_nfa_stream_behind(c, nfaStageOff, side))) return rc; }
+    else if ((rc = lines_nfa_stage(c))) return rc;
     lines_describe(c, side, d_kl, d_ldesc, d_linefn, d_counts, cap);
     return SSLAM_OK;
 }
@@ -915,6 +936,73 @@ extern "C" int sslam_testing_lines_nfa(sslam_lines* L, const uint8_t* gray, int 
     return SSLAM_OK;
 }
 
+// The sequential core alone (include/sslam_testing.h): the preparation of sslam_lines_extract_batch_dev (lines_prepare, lines_forms from the knobs as they stand, k_zero_misc),
+// lines_prologue() and lines_core() -- the product path's own functions, the launch form included -- on frames that are on the device already; under CoreForm::ClusterStream
+// also the consumers the product runs behind the core (lines_nfa_stream_behind).  Nothing of the tail.
+extern "C" int sslam_testing_lines_core(sslam_lines* L, const uint8_t* d_images, int w, int h, size_t pitch, size_t image_stride, int nframes) {
+    if (!L || !d_images || w <= 0 || h <= 0 || nframes <= 0 || pitch < (size_t)w) { set_error("sslam_testing_lines_core: invalid arguments"); return SSLAM_ERR_INVALID; }
+    if (nframes > 1 && image_stride < pitch * (size_t)(h - 1) + (size_t)w) { set_error("sslam_testing_lines_core: the frames overlap (image_stride < pitch * (h - 1) + w)"); return SSLAM_ERR_INVALID; }
+    const LinesKnobs K = lines_knobs();
+    std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
+    L->last = {};
+    SSLAM_HIP(hipSetDevice(L->ctx->device));
+    hipStream_t st = L->ctx->stream;
+    int rc;
+    if ((rc = lines_prepare(L, w, h, nframes, st))) return rc;
+    const LsdPlan& P = L->plan;
+    const LinesCall c{L, P, d_images, pitch, image_stride, nframes, st, L->dWs.as<uint8_t>(), lines_call_forms(L, nframes, L->topnOnly ? L->maxLines : 0, K)};
+    hipLaunchKernelGGL(k_zero_misc, dim3(nframes), dim3(64), 0, st, c.ws, P);
+    SideJoin side{L, st};
+    if ((rc = lines_prologue(c))) return rc;
+    // what the core does not write still holds 0xA5 afterwards: the frames' candidate regions, and under the streaming form the staged rectangles of their cluster slots
+    // (the slots are sized here as lines_core_cluster sizes them, so that it finds them in place)
+    const bool streamNfa = c.F.core == CoreForm::ClusterStream;
+    const size_t candBytes = sizeof(double) * 12 * (size_t)MAX_SEG;
+    for (int b = 0; b < nframes; ++b) SSLAM_HIP(hipMemsetAsync(c.ws + (size_t)b * P.frameBytes + P.offCand, 0xA5, candBytes, st));
+    size_t stageOff = 0;
+    if (streamNfa) {
+        const ClLayout lay = lines_cluster_layout(P, c.F);
+        if (L->dCl.cap < lay.frameBytes * (size_t)nframes) { SSLAM_HIP(hipStreamSynchronize(st)); if ((rc = L->dCl.ensure(lay.frameBytes * (size_t)nframes))) return rc; }
+        for (int b = 0; b < nframes; ++b) SSLAM_HIP(hipMemsetAsync(L->dCl.as<uint8_t>() + (size_t)b * lay.frameBytes + lay.stageOff, 0xA5, candBytes, st));
+        stageOff = lay.stageOff;
+    }
+    size_t nfaStageOff = 0;
+    if ((rc = lines_core(c, side, &nfaStageOff))) return rc;
+    if (streamNfa) {
+        if (nfaStageOff != stageOff) { (void)hipStreamSynchronize(st); set_error("sslam_testing_lines_core: the cluster slot's layout changed under the tap"); return SSLAM_ERR_UNSUPPORTED; }
+        if ((rc = lines_nfa_stream_behind(c, nfaStageOff, side))) return rc;
+    }
+    side.join();
+    SSLAM_HIP(hipGetLastError());
+    L->lastFrames = nframes;
+    SSLAM_HIP(hipStreamSynchronize(st));
+    L->last.coreTap = true; L->last.coreTapStageOff = streamNfa ? stageOff : 0;
+    return SSLAM_OK;
+}
+
+// One frame of the last sslam_testing_lines_core: Misc::nCand, the first records from where the form leaves them, the T plane
+extern "C" int sslam_testing_lines_core_frame(sslam_lines* L, int frame, int nmax, size_t plane_cap, int32_t* size_out, int32_t* ncand_out, double* rects_out, float* t_out) {
+    if (!L || !size_out || !ncand_out || nmax < 0 || (nmax > 0 && !rects_out)) { set_error("sslam_testing_lines_core_frame: invalid arguments"); return SSLAM_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lk(L->ctx->mu);
+    if (!L->last.coreTap || frame < 0 || frame >= L->lastFrames) { set_error("sslam_testing_lines_core_frame: frame %d of no sslam_testing_lines_core call", frame); return SSLAM_ERR_INVALID; }
+    SSLAM_HIP(hipSetDevice(L->ctx->device));
+    SSLAM_HIP(hipStreamSynchronize(L->ctx->stream));
+    const LsdPlan& P = L->plan;
+    size_out[0] = P.sw; size_out[1] = P.sh;
+    if (t_out && (size_t)P.npx > plane_cap) { set_error("sslam_testing_lines_core_frame: %d x %d scaled pixels, the output plane holds %zu", P.sw, P.sh, plane_cap); return SSLAM_ERR_CAPACITY; }
+    const uint8_t* base = L->dWs.as<uint8_t>() + (size_t)frame * P.frameBytes;
+    Misc m;
+    SSLAM_HIP(hipMemcpy(&m, base + P.offMisc, sizeof(m), hipMemcpyDeviceToHost));
+    *ncand_out = m.nCand;
+    const bool streamNfa = L->last.forms.core == CoreForm::ClusterStream;
+    const uint8_t* recs = streamNfa ? L->dCl.as<uint8_t>() + (size_t)frame * L->clFrame + L->last.coreTapStageOff : base + P.offCand;
+    const int rows = std::min(nmax, (int)MAX_SEG);
+    if (rows > 0) SSLAM_HIP(hipMemcpy(rects_out, recs, sizeof(double) * 12 * (size_t)rows, hipMemcpyDeviceToHost));
+    if (t_out) SSLAM_HIP(hipMemcpy2D(t_out, sizeof(float) * (size_t)P.sw, base + P.offT, sizeof(float) * (size_t)P.tW, sizeof(float) * (size_t)P.sw, (size_t)P.sh, hipMemcpyDeviceToHost));
+    if (m.overflow) { set_error("sslam_testing_lines_core_frame: more than %d candidate rectangles in frame %d", MAX_SEG, frame); return SSLAM_ERR_UNSUPPORTED; }
+    return SSLAM_OK;
+}
+
 // Self-test of the table-based exact division used in the NFA tail (tests/test_lines_gpu.py): returns the number of
 // random (a, b) pairs, 1 <= a, b < n, whose quotient differs from the hardware IEEE division (must be 0).
 namespace {
@@ -1122,23 +1210,6 @@ extern "C" int sslam_frame_from_lines(sslam_lines* L, const float bounds[4], ssl
     return sslam_frame_from_device(L->ctx, 1, L->dKl.p, L->dDesc.as<uint8_t>(), L->lastN, bounds, out);
 }
 
-#if defined(SSLAM_LBD_DEBUG) || defined(SSLAM_NFA_DEBUG)
-// development aid: candidate rectangles (12 doubles) and their NfaState after the last stage (SSLAM_NFA_DEBUG: the LBD dump of
-// SSLAM_LBD_DEBUG reuses the candidate buffer)
-extern "C" int sslam_lines_debug_nfa(sslam_lines* L, int frame, double* rects_out, void* state_out, int cap, int* n_out, int* state_size) {
-    if (!L || frame < 0 || frame >= L->lastFrames) return SSLAM_ERR_INVALID;
-    SSLAM_HIP(hipSetDevice(L->ctx->device));
-    SSLAM_HIP(hipStreamSynchronize(L->ctx->stream));
-    const LsdPlan& P = L->plan;
-    const uint8_t* base = L->dWs.as<uint8_t>() + (size_t)frame * P.frameBytes;
-    Misc m; SSLAM_HIP(hipMemcpy(&m, base + P.offMisc, sizeof(m), hipMemcpyDeviceToHost));
-    const int n = std::min(m.nCand, cap);
-    *n_out = n; *state_size = (int)sizeof(NfaState);
-    SSLAM_HIP(hipMemcpy(rects_out, base + P.offCand, sizeof(double) * 12 * (size_t)n, hipMemcpyDeviceToHost));
-    SSLAM_HIP(hipMemcpy(state_out, base + P.offNfa, sizeof(NfaState) * (size_t)n, hipMemcpyDeviceToHost));
-    return SSLAM_OK;
-}
-#endif
 #ifdef SSLAM_LBD_DEBUG
 // development aid: the normalised 72-float LBD vectors of the last extraction (k_lbd parks them in the candidate buffer)
 extern "C" int sslam_lines_debug_lbd_floats(sslam_lines* L, int frame, float* out, int nlines) {

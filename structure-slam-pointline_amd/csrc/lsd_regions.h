@@ -143,6 +143,16 @@ __global__ void k_selftest_region_div(unsigned long long seed, int iters, unsign
 #ifndef SSLAM_LSD_DRIFT
 #define SSLAM_LSD_DRIFT 1
 #endif
+
+// sin and cos of region2rect's theta, CORRECTLY ROUNDED (sincos_cr.h says why and how).  A function of its own, not inlined: inside region2rect its temporaries took
+// the core's kernels from five waves per SIMD to four (94 -> 114 vector registers); called, they live in the registers a call may clobber anyway.
+struct SinCos { double s, c; };
+__device__ __attribute__((noinline)) SinCos sincos_cr_dev(double x) {
+    SinCos o;
+    sslam::crt::sincos(x, o.s, o.c);
+    return o;
+}
+
 // SPEC (helper waves of the cluster form, lsd_cluster.h): a helper wave grows a region AHEAD of the frame's main wave.  It never writes the pixel map: the
 // pixels it takes are marked in its own bitmap `bm` (LDS), and it gives up (returns -n) when the list would outgrow `capN` points.
 template <bool LAT, bool WIDE, int MARK = MARK_MAP, class G = TorusHelper>
@@ -388,7 +398,8 @@ __device__ void region2rect_m(const RegQ& rq, int n, int sw, const int* __restri
                                            : (double)fast_atan2_deg((float)Ixy, (float)(lambda - Iyy));
     theta *= DEG2RAD;
     if (fabs(angle_diff_signed(theta, regAngle)) > prec) theta += kPI;
-    const double dx = cos(theta), dy = sin(theta);
+    const SinCos sc = sincos_cr_dev(theta);      // (the library's cos / sin are faithful, not correctly rounded: their last bit differed from the reference's for one theta in fifteen)
+    const double dx = sc.c, dy = sc.s;
     double l_min = 0, l_max = 0, w_min = 0, w_max = 0;       // running min/max from 0: order independent
     for (int i = lane; i < n; i += 64) {
         const unsigned e = rq.get_n(i, n);

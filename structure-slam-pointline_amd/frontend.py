@@ -988,6 +988,55 @@ class LineNfaStage:
             self.h = C.c_void_p()
 
 
+class LineCore:
+    """A sslam_lines handle of the TESTING library with the tap of the sequential LSD core, sslam_testing_lines_core / _core_frame (include/sslam_testing.h): the product
+    path's prologue and core launch on device frames, then per frame the candidate count, the first records and the T plane."""
+    FILL = 0xA5A5A5A5A5A5A5A5          # the 64 bits of a record field the core did not write (view the records as uint64)
+
+    def __init__(self, ctx, max_lines=40):
+        self.T = testing_lib()
+        self.T.sslam_testing_lines_core.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int]
+        self.T.sslam_testing_lines_core_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t] + [C.c_void_p] * 4
+        self.h = C.c_void_p()
+        self._chk(self.T.sslam_lines_create(ctx.h, int(max_lines), C.byref(self.h)))
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise SslamError("%s: %s" % (self.T.sslam_status_str(rc).decode(), self.T.sslam_last_error().decode()), rc)
+
+    def __enter__(self): return self
+
+    def __exit__(self, *a): self.close()
+
+    def run(self, d_images, w, h, pitch, image_stride, nframes):
+        """the run step on frames that are on the device (a torch tensor or a pointer)"""
+        self._chk(self.T.sslam_testing_lines_core(self.h, _p(d_images), int(w), int(h), C.c_size_t(pitch), C.c_size_t(image_stride), int(nframes)))
+
+    def frame_raw(self, frame, nmax, want_t=True):
+        """the copy-back step -> (status, dict(sw, sh, ncand, rects [nmax, 12] float64 copied back WHOLE, T [sh, sw] float32 or None))"""
+        size = np.zeros(2, np.int32); n = np.full(1, -1, np.int32); rects = np.zeros((max(nmax, 1), 12), np.float64)
+        rc = self.T.sslam_testing_lines_core_frame(self.h, int(frame), int(nmax), 0, size.ctypes.data, n.ctypes.data, rects.ctypes.data, None)
+        T = None
+        if want_t and rc in (0, SSLAM_ERR_UNSUPPORTED):
+            T = np.zeros((int(size[1]), int(size[0])), np.float32)
+            rc = self.T.sslam_testing_lines_core_frame(self.h, int(frame), int(nmax), T.size, size.ctypes.data, n.ctypes.data, rects.ctypes.data, T.ctypes.data)
+        return rc, dict(sw=int(size[0]), sh=int(size[1]), ncand=int(n[0]), rects=rects[:nmax], T=T)
+
+    def frame(self, frame, nmax, want_t=True):
+        rc, out = self.frame_raw(frame, nmax, want_t)
+        self._chk(rc)
+        return out
+
+    def last_forms(self): return line_last_forms(self.h)
+
+    def set_core_event(self, hip_event): self._chk(self.T.sslam_lines_set_core_event(self.h, C.c_void_p(int(hip_event or 0))))
+
+    def close(self):
+        if self.h:
+            self.T.sslam_lines_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 # ---- multi-GPU batch mode (include/sslam_frontend.h: sslam_group_*, record stream) ------------------------------------------------
 class FrontendParams(C.Structure):
     _fields_ = [("nfeatures", C.c_int32), ("scale_factor", C.c_float), ("nlevels", C.c_int32), ("ini_th_fast", C.c_int32),

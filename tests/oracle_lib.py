@@ -327,6 +327,10 @@ LSD_TRACE = ("sw", "sh", "min_reg_size", "defined", "seeds", "reg_min_m1", "reg_
              "nfa_zero", "nfa_all", "nfa_term0_above", "nfa_term0_below", "nfa_break", "nfa_full", "rows_outside", "cols_outside",
              "touch_row0", "touch_row_last", "touch_col0", "touch_col_last", "segments")
 
+# oracle/lsd_oracle.cpp orc_lsd_core: a candidate's and a grown seed's row
+CORE_CAND = np.dtype([(k, "<i4") for k in ("x", "y", "points", "reach", "regrew", "reduced", "x0", "y0", "x1", "y1")])
+CORE_SEED = np.dtype([(k, "<i4") for k in ("x", "y", "first", "list_len")])
+
 
 def _orc_line_methods():
     def lines_extract(self, gray, max_lines=40, want_float=False):
@@ -385,6 +389,24 @@ def _orc_line_methods():
         assert 0 <= n <= cap
         return {k: int(v) for k, v in zip(LSD_TRACE, tr)}, seg[:n].copy(), cand[:n].copy()
 
+    def lsd_core(self, gray):
+        """Lsd::detect with its core record (oracle/lsd_oracle.cpp LsdCore, orc_lsd_core): what the sequential core did and left -> dict(sw, sh, min_reg_size, rects [n, 12]
+        float64 = every candidate's first record in emission order, cand [n] of CORE_CAND (seed, points, reach, regrew, reduced, the box of the points), seeds [m] of CORE_SEED (every seed that grew
+        a region: first growth and list length), used [sh, sw] bool = the final used map, blocked_joins)"""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        h, w = gray.shape
+        self.L.orc_lsd_core.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        size = np.zeros(2, np.int32); st = np.zeros(4, np.int64)
+        n = self.L.orc_lsd_core(_p(gray), w, h, gray.strides[0], _p(size), None, None, 0, None, 0, None, _p(st))
+        sw, sh = int(size[0]), int(size[1]); m = int(st[1])
+        rects = np.zeros((max(n, 1), 12), np.float64); cand = np.zeros((max(n, 1), len(CORE_CAND.names)), np.int32); seeds = np.zeros((max(m, 1), 4), np.int32); used = np.zeros((sh, sw), np.uint8)
+        st2 = np.zeros(4, np.int64)
+        assert self.L.orc_lsd_core(_p(gray), w, h, gray.strides[0], _p(size), _p(rects), _p(cand), n, _p(seeds), m, _p(used), _p(st2)) == n and (st == st2).all()
+        out = dict(sw=sw, sh=sh, min_reg_size=int(st[3]), rects=rects[:n].copy(), cand=np.ascontiguousarray(cand[:n]).view(CORE_CAND).reshape(n),
+                   seeds=np.ascontiguousarray(seeds[:m]).view(CORE_SEED).reshape(m), used=used.astype(bool), blocked_joins=int(st[2]))
+        for k in ("rects", "cand", "seeds", "used"): out[k].setflags(write=False)
+        return out
+
     def set_lsd_resize(self, v):
         """0: decision D7 (INTER_LINEAR_EXACT); 1: INTER_LINEAR.  Process-global; returns the previous value."""
         return int(self.L.orc_set_lsd_resize(int(v)))
@@ -417,7 +439,7 @@ def _orc_line_methods():
         assert self.L.orc_lsd_grad_table(_p(tab), C.byref(smin)) == 0
         return tab, smin.value
 
-    for f in (lines_extract, lsd_scaled, lines_tail, lbd_from_keylines, lsd_trace, set_lsd_resize, set_lsd_seed_sort, lsd_prologue, lsd_grad_table):
+    for f in (lines_extract, lsd_scaled, lines_tail, lbd_from_keylines, lsd_trace, lsd_core, set_lsd_resize, set_lsd_seed_sort, lsd_prologue, lsd_grad_table):
         setattr(Oracle, f.__name__, f)
 
 
