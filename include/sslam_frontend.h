@@ -179,8 +179,8 @@ int sslam_orb_search_for_initialization_batch_dev(sslam_ctx* ctx,
 /* The model selection of Initializer::Initialize (src/Initializer.cc:55-118, reached from src/Tracking.cc:366 right behind SearchForInitialization): `iterations` RANSAC
  * hypotheses, each one homography and one fundamental matrix from eight matches (FindHomography / FindFundamental :155-253, ComputeH21 / ComputeF21 :255-332 on the points of
  * Normalize :784-830), scored against every match (CheckHomography / CheckFundamental :334-497), the best of each and RH = SH / (SH + SF) (:118).  What follows in the
- * reference -- ReconstructH / ReconstructF, CheckRT, Triangulate (:499-782, :833 on) -- are poses and map points and stay with the tracker: H21 / F21 and the inlier bits
- * below are their inputs.  kp1 / kp2 are the UNDISTORTED keypoints (mvKeysUn: sslam_undistort_keypoints_batch_dev); matches12[i] is the keypoint of frame 2 matched to keypoint i
+ * reference -- ReconstructH / ReconstructF, CheckRT, Triangulate (:499-782, :833 on) -- has its batch form on the device too (sslam_two_view_reconstruct_batch_dev below,
+ * which takes H21 / F21 and the inlier bits where this call leaves them); map creation and g2o stay with the caller.  kp1 / kp2 are the UNDISTORTED keypoints (mvKeysUn: sslam_undistort_keypoints_batch_dev); matches12[i] is the keypoint of frame 2 matched to keypoint i
  * of frame 1 or negative (vnMatches12: sslam_orb_search_for_initialization_batch_dev's d_matches12); a row counts as matched when 0 <= matches12[i] < n2, and the matched rows in
  * ascending i are the match list (mvMatches12, :67-76).  sigma is mSigma (1.0 in Tracking), iterations mMaxIterations (200).
  *   sets  NULL: iteration `it` of pair p draws its eight matches as :93-108 do, with randi = hash32(seed, p, it, j) % remaining (csrc/ransac_draw.h states hash32; the
@@ -214,6 +214,57 @@ int sslam_two_view_ransac_batch_dev(sslam_ctx* ctx, const sslam_keypoint* d_kp1,
         const sslam_keypoint* d_kp2, const int32_t* d_n2, int cap, int npairs, const int32_t* d_matches12,
         const int32_t* d_sets /* NULL or [npairs*iterations*8] */, int iterations, float sigma, uint32_t seed,
         sslam_two_view_result* d_result, uint8_t* d_inliers /* [npairs*cap] */, void* stream);
+
+/* The second half of Initializer::Initialize (src/Initializer.cc:143-152): ReconstructH (:611-781, Faugeras' eight hypotheses) when the model is 1, ReconstructF (:500-608 with
+ * DecomposeE :964-984, four hypotheses) when it is 2, each hypothesis checked by CheckRT (:833-961) over every inlier match with Triangulate (:987-1000), the reference's choice
+ * among them, and with the winning R21 / t21 the line half of this fork: ReconstructLine (:1059-1171) with LineTriangulate (:1003-1055) and the two MADs of vector_mad
+ * (include/auxiliar.h:91-106).  Together with sslam_two_view_ransac* this is all of Initialize (:55-153): (:499-782, :833-1171) are this call.
+ * Pair layout and counts are sslam_two_view_ransac_batch_dev's; d_result and d_inliers are that call's outputs where they lie (model 1 reads H21 and bit 0 of the inlier
+ * bytes, model 2 F21 and bit 1; any other model is a skipped pair).  d_K[p*4 .. +4) = fx fy cx cy of mK (the reference frame's); sigma is mSigma (th2 = 4 sigma^2, :527),
+ * min_parallax and min_triangulated the 1.0 and 50 of :146 / :150.
+ *   pose, one per pair.  ok is Initialize's return value.  reason: 0 ok, 1 skipped (model 0), 2 H: singular values not separated (:639), 3 no clear winner or too few points
+ *         (:550; :763 without its parallax term), 4 parallax below min_parallax (:559-604; :763).  hypothesis: the candidate the reference settled on -- F: 0 .. 3 = (R1, t1),
+ *         (R2, t1), (R1, t2), (R2, t2), the FIRST whose nGood equals maxGood, once :550 let it through; H: bestSolutionIdx 0 .. 7 -- and -1 when there is none; with reason 4
+ *         it names the candidate that failed.  n_inliers is N (:504-507).  n_good / parallax: CheckRT's return and parallax per hypothesis, 0 for entries that were not run.
+ *         R21 (row-major) / t21: zeros when !ok.  n_triangulated: true entries of vbTriangulated.  n_lines: line pairs that passed the index filter; n_lines_triangulated:
+ *         true entries of vbLineTriangulated (0 when !ok).
+ *   p3d / triangulated, by keypoint 1 (vP3D, vbTriangulated): rows [0, n1) are always written, zeros and 0 for a row that is not triangulated and for every row of a pair
+ *         that fails; rows [n1, cap) are not written.
+ *   lines, all NULL or none NULL: d_kl1 / d_kl2 [npairs*lcap] with counts d_nl1 / d_nl2, d_linefn1 / d_linefn2 [npairs*lcap*3] (mvKeyLineFunctions), d_line_pairs
+ *         [(p*lcap + r)*2 + {0, 1}] = (line of frame 1, line of frame 2) for r < d_line_npairs[p], as sslam_frontend_batch_match leaves them.  The line outputs are indexed by
+ *         that row r: rows [0, min(max(d_line_npairs[p], 0), lcap)) are always written.  A pair with an index outside [0, nl) is left out as the reference's >= 0 filter
+ *         (:133) leaves it out: written as zeros and 0, not part of the MADs.  A row whose endpoints are not finite keeps zero endpoints, error 0 and stays triangulated
+ *         (:1102-1106).  With !ok every line output is zero.  The line of frame 2 enters through its function alone, as in the reference (d_kl2 is not read).
+ * What the reference leaves to OpenCV, Eigen and libm here (cv::SVD::compute of the 3 x 3 and 4 x 4, the float products, acos, the sorts) is restated by decision D18 of
+ * DESIGN.md; everything else is the reference's arithmetic operation for operation.
+ * One launch on `stream` (NULL: the context's stream), one workgroup per pair, no scratch, no synchronise, no host memory read or written; every output word has one writer.
+ * SSLAM_ERR_INVALID (nothing enqueued): a NULL pointer other than the line arguments, line arguments given in part, cap or npairs < 1, lcap < 1 with lines, sigma <= 0 or
+ * NaN, min_triangulated < 0, a pointer that is not 4-byte aligned (d_linefn1 / d_linefn2: 8), npairs * cap >= 2^31 or npairs * lcap >= 2^31.  SSLAM_ERR_UNSUPPORTED (nothing
+ * enqueued): cap > 5120 or lcap > 1024 (a pair's rows sit in LDS).  The single call is pair 0 of the same kernel (cap = max(n1, n2), lcap = max(nl1, nl2, line_npairs)) and
+ * synchronises; its line arguments are absent when line_pairs is NULL (line_npairs 0 and the other line arguments NULL then); with lines, kl2 may be NULL (it is
+ * not read). */
+typedef struct sslam_two_view_pose {      /* 144 bytes */
+    int32_t ok;                     /* Initialize's return value */
+    int32_t reason;                 /* 0 ok, 1 skipped, 2 H: singular values not separated, 3 no clear winner or too few points, 4 parallax below min */
+    int32_t model, hypothesis;      /* 1 H / 2 F as in the result; the candidate hypothesis, -1 if none */
+    int32_t n_inliers;              /* N */
+    int32_t n_good[8]; float parallax[8];      /* CheckRT per hypothesis; unused entries 0 */
+    float R21[9], t21[3];           /* zeros when !ok */
+    int32_t n_triangulated, n_lines, n_lines_triangulated;
+} sslam_two_view_pose;
+int sslam_two_view_reconstruct_batch_dev(sslam_ctx* ctx, const sslam_keypoint* d_kp1, const int32_t* d_n1, const sslam_keypoint* d_kp2, const int32_t* d_n2,
+        int cap, int npairs, const int32_t* d_matches12, const sslam_two_view_result* d_result, const uint8_t* d_inliers, const float* d_K /* [npairs*4] */,
+        float sigma, float min_parallax, int min_triangulated,
+        const sslam_keyline* d_kl1, const int32_t* d_nl1, const sslam_keyline* d_kl2, const int32_t* d_nl2, const double* d_linefn1, const double* d_linefn2, int lcap,
+        const int32_t* d_line_pairs, const int32_t* d_line_npairs,
+        sslam_two_view_pose* d_pose, float* d_p3d /* [npairs*cap*3] */, uint8_t* d_triangulated /* [npairs*cap] */,
+        float* d_line_s3d, float* d_line_e3d /* [npairs*lcap*3] */, uint8_t* d_line_triangulated /* [npairs*lcap] */, void* stream);
+int sslam_two_view_reconstruct(sslam_ctx* ctx, const sslam_keypoint* kp1, int n1, const sslam_keypoint* kp2, int n2, const int32_t* matches12,
+        const sslam_two_view_result* result, const uint8_t* inliers /* [n1] */, const float K[4], float sigma, float min_parallax, int min_triangulated,
+        const sslam_keyline* kl1, int nl1, const sslam_keyline* kl2, int nl2, const double* linefn1, const double* linefn2,
+        const int32_t* line_pairs /* NULL or [line_npairs*2] */, int line_npairs,
+        sslam_two_view_pose* pose, float* p3d /* [n1*3] */, uint8_t* triangulated /* [n1] */,
+        float* line_s3d, float* line_e3d /* [line_npairs*3] */, uint8_t* line_triangulated /* [line_npairs] */);
 
 /* Sim3Solver (src/Sim3Solver.cc), the RANSAC of LoopClosing::ComputeSim3 (src/LoopClosing.cc:279-306) between SearchByBoW (:269: sslam_orb_search_by_bow_keyframes_batch_dev) and
  * SearchBySim3 (:328: sslam_fuse_search_batch_dev, which takes the s, R, t found here): the constructor (:37-112), SetRansacParameters (:114-138) and iterate (:140-207) with

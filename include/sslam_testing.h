@@ -192,6 +192,19 @@ int sslam_testing_pnp_hypotheses(sslam_ctx* ctx, const sslam_keypoint* f_kp, int
                                  float th2, int new_iterations, const int32_t* sets, int nsets, uint32_t seed, int pair, sslam_pnp_state* state, uint8_t* inliers,
                                  int tap_rows, int32_t* sets_out, double* poses_out, int32_t* counts_out, double* trace_out);
 
+/* sslam_two_view_reconstruct for one host pair with EVERY hypothesis copied back, so that a wrong hypothesis that does not win is visible: the same kernel with its stores
+ * enabled, run as pair 0.  hyp_out[h*15 .. +15) = R (row-major), t and, for ReconstructH, the plane normal n of hypothesis h (zeros for one that was not built);
+ * sel_out[h] = the cosine CheckRT selected (vCosParallax[min(50, size - 1)] after the sort; 0 when nGood is 0).  Per hypothesis and match row r (the match list in
+ * ascending keypoint-1 order; rows_cap = max(n1, n2, 1) rows per hypothesis): stage_out[h*rows_cap + r] = 0 not an inlier, 1 not finite, 2 z1 <= 0, 3 z2 <= 0,
+ * 4 error 1, 5 error 2, 6 good; p3d_rows_out[(h*rows_cap + r)*3 .. +3) = the triangulated point (from stage 1 on), cos_out[h*rows_cap + r] = cosParallax (from stage 2
+ * on).  line_err_out[r*2 .. +2) (NULL without lines) = errorC1, errorC2 of line row r.  Rows past the match list and hypotheses that were not run are zero. */
+int sslam_testing_two_view_reconstruct(sslam_ctx* ctx, const sslam_keypoint* kp1, int n1, const sslam_keypoint* kp2, int n2, const int32_t* matches12,
+                                       const sslam_two_view_result* result, const uint8_t* inliers, const float K[4], float sigma, float min_parallax, int min_triangulated,
+                                       const sslam_keyline* kl1, int nl1, const sslam_keyline* kl2, int nl2, const double* linefn1, const double* linefn2,
+                                       const int32_t* line_pairs, int line_npairs, sslam_two_view_pose* pose, float* p3d, uint8_t* triangulated,
+                                       float* line_s3d, float* line_e3d, uint8_t* line_triangulated,
+                                       float* hyp_out, float* sel_out, int32_t* stage_out, float* p3d_rows_out, float* cos_out, double* line_err_out);
+
 #ifdef __cplusplus
 }
 #endif

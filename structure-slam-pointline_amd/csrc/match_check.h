@@ -46,5 +46,18 @@ inline bool pnp_sizes_ok(int npairs, int cap, int nframes, int nkeyframes, int k
 // Injected sets of a RANSAC batch (d_sets: iterations sets per pair): their rows are indexed pair * iterations + it, which stays below 2^28 so that the index times the
 // words of a set fits 31 bits.  Without sets the rule asks nothing.
 inline bool injected_sets_ok(const void* d_sets, int npairs, int iterations) { return !d_sets || (long long)npairs * (long long)iterations < (1ll << 28); }
+// The parameters sslam_two_view_reconstruct and sslam_two_view_reconstruct_batch_dev share (reconstruct.hip): mSigma above 0 (a NaN fails the comparison) and a
+// minTriangulated that is a count.  minParallax is compared as the reference compares it, whatever it is.
+inline bool reconstruct_params_ok(float sigma, int min_triangulated) { return sigma > 0.f && min_triangulated >= 0; }
+// The line arguments of a reconstruct batch come all or none: 0 = none (every pointer NULL; lcap is not looked at), 1 = all (no pointer NULL, lcap >= 1), -1 = in part
+inline int reconstruct_lines_given(const void* kl1, const void* nl1, const void* kl2, const void* nl2, const void* fn1, const void* fn2, const void* pairs, const void* npairs,
+                                   const void* s3d, const void* e3d, const void* tri, int lcap) {
+    const void* p[11] = {kl1, nl1, kl2, nl2, fn1, fn2, pairs, npairs, s3d, e3d, tri};
+    int given = 0;
+    for (const void* q : p) given += q ? 1 : 0;
+    return given == 0 ? 0 : given == 11 && lcap >= 1 ? 1 : -1;
+}
+// The sizes of a reconstruct batch: rows are indexed pair * cap + i and line rows pair * lcap + r in 31 bits (lcap 0: a batch without lines)
+inline bool reconstruct_sizes_ok(int npairs, int cap, int lcap) { return npairs >= 1 && cap >= 1 && lcap >= 0 && fits_31_bits(npairs, cap) && fits_31_bits(npairs, lcap); }
 
 }  // namespace sslam

@@ -293,6 +293,36 @@ constexpr int PNP_MAX_CAP = ransac_max_cap(PNP_ROW_BYTES, PNP_FIXED_BYTES, LDS_P
 static_assert(PNP_MAX_CAP == 2048 && PNP_MAX_CAP <= 8 * PNP_MASK_BYTES, "the capacity include/sslam_frontend.h promises (the c2 configuration extracts 2000 keypoints); one mask bit per row");
 inline RansacPlan pnp_plan(int cap) { return ransac_plan(PNP_ROW_BYTES, PNP_FIXED_BYTES, PNP_MAX_CAP, cap); }
 
+// -------------------------------------------------------------- ReconstructH / ReconstructF over the rows of a pair (sslam_two_view_reconstruct*, reconstruct.hip)
+// One workgroup of RECON_WAVES waves per pair; all lanes walk the match rows of one hypothesis after the other.  Dynamic LDS: the Jacobi workspace of the 4 x 4 solves,
+// RECON_WS_DOUBLES doubles per lane (reconstruct_math.h: WS4_DOUBLES), lane-interleaved; per line row of the capacity the two errors (doubles); per match row of the
+// capacity (u1, v1, u2, v2), the key of its cosine and the inlier byte.  The line capacity is bounded by RECON_MAX_LCAP; the row capacity is what the compute unit's LDS
+// leaves beside that, the workspace and RECON_STATIC_LDS of static words, in whole steps of RANSAC_CAP_STEP: no less than the RANSAC call's own bound, so every batch it takes
+// goes on.  Two waves: a pair at the RANSAC call's bound then takes 110 KB, one at half of it 68 KB, so that two such pairs share a compute unit.
+constexpr int RECON_WAVES = 2, RECON_THREADS = 64 * RECON_WAVES, RECON_WS_DOUBLES = 10 + 16, RECON_ROW_BYTES = 16 + 4 + 1, RECON_LINE_ROW_BYTES = 16, RECON_MAX_LCAP = 1024;
+constexpr size_t RECON_WS_BYTES = sizeof(double) * RECON_WS_DOUBLES * RECON_THREADS, RECON_STATIC_LDS = 2048;
+constexpr int RECON_MAX_CAP = (int)((LDS_PER_CU - RECON_STATIC_LDS - RECON_WS_BYTES - (size_t)RECON_LINE_ROW_BYTES * RECON_MAX_LCAP) / RECON_ROW_BYTES / RANSAC_CAP_STEP) * RANSAC_CAP_STEP;
+static_assert(RECON_MAX_CAP == 5120 && RECON_MAX_CAP >= TWO_VIEW_MAX_CAP, "the capacity include/sslam_frontend.h promises; no less than the RANSAC call's");
+struct ReconstructPlan {
+    int rowBytes, lineRowBytes;
+    size_t wsOff, lineOff, rowOff, keyOff, flagOff, ldsBytes;      // offsets into the dynamic LDS and its size
+    int ldsOptIn; unsigned threads; int maxCap, maxLcap;            // ldsBytes means nothing beyond the bounds
+};
+inline ReconstructPlan reconstruct_plan(int cap, int lcap) {
+    ReconstructPlan P{};
+    P.rowBytes = RECON_ROW_BYTES; P.lineRowBytes = RECON_LINE_ROW_BYTES; P.threads = RECON_THREADS; P.maxCap = RECON_MAX_CAP; P.maxLcap = RECON_MAX_LCAP;
+    const size_t c = (size_t)std::max(cap, 0), l = (size_t)std::max(lcap, 0);
+    P.wsOff = 0;
+    P.lineOff = RECON_WS_BYTES;
+    P.rowOff = P.lineOff + RECON_LINE_ROW_BYTES * l;
+    P.keyOff = P.rowOff + 16 * c;
+    P.flagOff = P.keyOff + 4 * c;
+    P.ldsBytes = (P.flagOff + c + 15) & ~(size_t)15;
+    P.ldsOptIn = P.ldsBytes > DYNAMIC_LDS_DEFAULT_MAX ? 1 : 0;
+    return P;
+}
+static_assert(RECON_WS_BYTES + (size_t)RECON_LINE_ROW_BYTES * RECON_MAX_LCAP + (size_t)RECON_ROW_BYTES * RECON_MAX_CAP + 16 + RECON_STATIC_LDS <= LDS_PER_CU, "the bounds fit the compute unit");
+
 // arena of search_proj_core.  occ | q | qdesc go up in ONE copy (occ .. assigned), assigned | count come back in one (assigned .. count + 4);
 // only that head (.. count + 256) has a pinned mirror.  projK = list length of k_proj_topk (PROJ_K).
 struct ProjArena {

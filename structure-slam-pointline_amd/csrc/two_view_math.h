@@ -83,31 +83,32 @@ TV_FN void transpose3(const float m[9], float o[9]) {
 
 // Working storage of one solve: W::at(k) is a reference to double k of WS_DOUBLES.  The device keeps it in LDS, lane-interleaved (two_view.hip), so that the
 // run-time indices below never make a private array; the host uses a plain array.
-TV_FN int sym_index(int i, int j) {      // upper triangle of a 9-wide symmetric matrix, any order of (i, j)
+// LD is the width the storage is laid out for: 9 here; a caller with a smaller matrix may lay it out as narrow as that matrix (LD * (LD + 1) / 2 + LD * LD doubles).
+template <int LD = 9> TV_FN int sym_index(int i, int j) {      // upper triangle of an LD-wide symmetric matrix, any order of (i, j)
     const int lo = i < j ? i : j, hi = i < j ? j : i;
-    return lo * 9 - lo * (lo - 1) / 2 + (hi - lo);
+    return lo * LD - lo * (lo - 1) / 2 + (hi - lo);
 }
-template <class W> TV_FN double& ws_a(W& w, int i, int j) { return w.at(sym_index(i, j)); }
-template <class W> TV_FN double& ws_v(W& w, int i, int j) { return w.at(45 + i * 9 + j); }
+template <int LD = 9, class W> TV_FN double& ws_a(W& w, int i, int j) { return w.at(sym_index<LD>(i, j)); }
+template <int LD = 9, class W> TV_FN double& ws_v(W& w, int i, int j) { return w.at(LD * (LD + 1) / 2 + i * LD + j); }
 
-// D15 solver, second half: cyclic Jacobi on the symmetric N x N matrix in ws_a (N = 9 or 3); returns the column of ws_v that belongs to the smallest diagonal entry
+// D15 solver, second half: cyclic Jacobi on the symmetric N x N matrix in ws_a (N <= LD); returns the column of ws_v that belongs to the smallest diagonal entry
 // (the first of equals).  Fixed trip counts: NaNs and infinities pass through and end.  The loop over k is unrolled and loads rows p and q of every k before it stores
 // any (the two it must not change are loaded too and not stored), so that the loads of a rotation are in flight together.
-template <int N, class W>
+template <int N, int LD = 9, class W>
 TV_FN int jacobi_smallest(W& w) {
-    for (int i = 0; i < N; ++i) for (int j = 0; j < N; ++j) ws_v(w, i, j) = i == j ? 1.0 : 0.0;
+    for (int i = 0; i < N; ++i) for (int j = 0; j < N; ++j) ws_v<LD>(w, i, j) = i == j ? 1.0 : 0.0;
     TV_NOUNROLL
     for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
         TV_NOUNROLL
         for (int p = 0; p < N - 1; ++p) {
             TV_NOUNROLL
             for (int q = p + 1; q < N; ++q) {
-                const double apq = ws_a(w, p, q);
+                const double apq = ws_a<LD>(w, p, q);
                 if (apq == 0.0) continue;
-                const double app = ws_a(w, p, p), aqq = ws_a(w, q, q);
+                const double app = ws_a<LD>(w, p, p), aqq = ws_a<LD>(w, q, q);
                 double akp[N], akq[N], vkp[N], vkq[N];
                 TV_UNROLL
-                for (int k = 0; k < N; ++k) { akp[k] = ws_a(w, k, p); akq[k] = ws_a(w, k, q); vkp[k] = ws_v(w, k, p); vkq[k] = ws_v(w, k, q); }
+                for (int k = 0; k < N; ++k) { akp[k] = ws_a<LD>(w, k, p); akq[k] = ws_a<LD>(w, k, q); vkp[k] = ws_v<LD>(w, k, p); vkq[k] = ws_v<LD>(w, k, q); }
                 const double theta = (aqq - app) / (2.0 * apq);
                 const double at = theta < 0.0 ? -theta : theta;
                 double t = 1.0 / (at + __builtin_sqrt(theta * theta + 1.0));
@@ -116,21 +117,21 @@ TV_FN int jacobi_smallest(W& w) {
                 TV_UNROLL
                 for (int k = 0; k < N; ++k) {
                     if (k != p && k != q) {
-                        ws_a(w, k, p) = c * akp[k] - s * akq[k];
-                        ws_a(w, k, q) = s * akp[k] + c * akq[k];
+                        ws_a<LD>(w, k, p) = c * akp[k] - s * akq[k];
+                        ws_a<LD>(w, k, q) = s * akp[k] + c * akq[k];
                     }
-                    ws_v(w, k, p) = c * vkp[k] - s * vkq[k];
-                    ws_v(w, k, q) = s * vkp[k] + c * vkq[k];
+                    ws_v<LD>(w, k, p) = c * vkp[k] - s * vkq[k];
+                    ws_v<LD>(w, k, q) = s * vkp[k] + c * vkq[k];
                 }
-                ws_a(w, p, p) = app - t * apq;
-                ws_a(w, q, q) = aqq + t * apq;
-                ws_a(w, p, q) = 0.0;
+                ws_a<LD>(w, p, p) = app - t * apq;
+                ws_a<LD>(w, q, q) = aqq + t * apq;
+                ws_a<LD>(w, p, q) = 0.0;
             }
         }
     }
     int best = 0;
-    double lowest = ws_a(w, 0, 0);
-    for (int i = 1; i < N; ++i) { const double d = ws_a(w, i, i); if (d < lowest) { lowest = d; best = i; } }
+    double lowest = ws_a<LD>(w, 0, 0);
+    for (int i = 1; i < N; ++i) { const double d = ws_a<LD>(w, i, i); if (d < lowest) { lowest = d; best = i; } }
     return best;
 }
 

@@ -36,6 +36,10 @@ assert OBS_DTYPE.itemsize == 8
 TWO_VIEW_RESULT_DTYPE = np.dtype([("nmatches", "<i4"), ("model", "<i4"), ("best_it_h", "<i4"), ("best_it_f", "<i4"), ("score_h", "<f4"), ("score_f", "<f4"),
                                   ("rh", "<f4"), ("H21", "<f4", (9,)), ("F21", "<f4", (9,))])      # sslam_two_view_result
 assert TWO_VIEW_RESULT_DTYPE.itemsize == 100
+TWO_VIEW_POSE_DTYPE = np.dtype([("ok", "<i4"), ("reason", "<i4"), ("model", "<i4"), ("hypothesis", "<i4"), ("n_inliers", "<i4"), ("n_good", "<i4", (8,)),
+                                ("parallax", "<f4", (8,)), ("R21", "<f4", (9,)), ("t21", "<f4", (3,)), ("n_triangulated", "<i4"), ("n_lines", "<i4"),
+                                ("n_lines_triangulated", "<i4")])      # sslam_two_view_pose
+assert TWO_VIEW_POSE_DTYPE.itemsize == 144
 
 SIM3_STATE_DTYPE = np.dtype([("its_done", "<i4"), ("best_inliers", "<i4"), ("best_it", "<i4"), ("n", "<i4"), ("max_its", "<i4"), ("found_it", "<i4"), ("n_inliers", "<i4"),
                              ("no_more", "<i4"), ("s12", "<f4"), ("R12", "<f4", (9,)), ("t12", "<f4", (3,))])      # sslam_sim3_state
@@ -199,6 +203,48 @@ class Context:
         enqueues on `stream` (None: the context's) and returns without synchronising"""
         _chk(lib().sslam_two_view_ransac_batch_dev(self.h, _p(d_kp1), _p(d_n1), _p(d_kp2), _p(d_n2), int(cap), int(npairs), _p(d_matches12), _p(d_sets), int(iterations),
                                                    C.c_float(sigma), C.c_uint32(seed), _p(d_result), _p(d_inliers), C.c_void_p(stream or 0)))
+
+    def two_view_reconstruct(self, kp1, kp2, matches12, result, inliers, K, sigma=1.0, min_parallax=1.0, min_triangulated=50, lines=None):
+        """The second half of Initializer::Initialize (sslam_two_view_reconstruct) for one pair: kp1 / kp2, matches12 as two_view_ransac took them, result / inliers as it
+        returned them, K = (fx, fy, cx, cy).  lines: None or (kl1, kl2, linefn1, linefn2, line_pairs) with KL_DTYPE rows, float64 [nl, 3] functions and int32 [np, 2] pairs.
+        Returns (pose: a TWO_VIEW_POSE_DTYPE record, p3d float32 [n1, 3], triangulated uint8 [n1]) and, with lines, (line_s3d, line_e3d float32 [np, 3],
+        line_triangulated uint8 [np]) behind them"""
+        kp1 = np.ascontiguousarray(kp1, KP_DTYPE); kp2 = np.ascontiguousarray(kp2, KP_DTYPE)
+        m12 = np.ascontiguousarray(matches12, np.int32); inl = np.ascontiguousarray(inliers, np.uint8)
+        res = np.ascontiguousarray(np.asarray(result, TWO_VIEW_RESULT_DTYPE).reshape(1))
+        assert len(m12) == len(kp1) == len(inl)
+        Kf = np.ascontiguousarray(K, np.float32); assert Kf.shape == (4,)
+        pose = np.zeros(1, TWO_VIEW_POSE_DTYPE); p3d = np.zeros((len(kp1), 3), np.float32); tri = np.zeros(len(kp1), np.uint8)
+        la = [None, 0, None, 0, None, None, None, 0]; lo = [None, None, None]
+        if lines is not None:
+            kl1, kl2, f1, f2, lp = lines
+            kl1 = np.ascontiguousarray(kl1, KL_DTYPE); kl2 = np.ascontiguousarray(kl2, KL_DTYPE)
+            f1 = np.ascontiguousarray(f1, np.float64).reshape(-1, 3); f2 = np.ascontiguousarray(f2, np.float64).reshape(-1, 3)
+            lp = np.ascontiguousarray(lp, np.int32).reshape(-1, 2)
+            assert len(f1) == len(kl1) and len(f2) == len(kl2)
+            pairs = lp if len(lp) else np.zeros((1, 2), np.int32)      # line_pairs != NULL is what says "with lines", also with no pair
+            la = [kl1, len(kl1), kl2, len(kl2), f1, f2, pairs, len(lp)]
+            lo = [np.zeros((len(lp), 3), np.float32), np.zeros((len(lp), 3), np.float32), np.zeros(len(lp), np.uint8)]
+        ptr = lambda a: _p(a if a is not None and len(a) else None)      # an empty array travels as NULL
+        _chk(lib().sslam_two_view_reconstruct(self.h, _p(kp1), len(kp1), _p(kp2), len(kp2), _p(m12), _p(res), _p(inl), _p(Kf), C.c_float(sigma), C.c_float(min_parallax),
+                                              int(min_triangulated), ptr(la[0]), la[1], ptr(la[2]), la[3], ptr(la[4]), ptr(la[5]), _p(la[6]), la[7], _p(pose), _p(p3d),
+                                              _p(tri), ptr(lo[0]), ptr(lo[1]), ptr(lo[2])))
+        if lines is None:
+            return pose[0], p3d, tri
+        return pose[0], p3d, tri, lo[0], lo[1], lo[2]
+
+    def two_view_reconstruct_batch_dev(self, d_kp1, d_n1, d_kp2, d_n2, cap, npairs, d_matches12, d_result, d_inliers, d_K, d_pose, d_p3d, d_triangulated,
+                                       sigma=1.0, min_parallax=1.0, min_triangulated=50, lines=None, lcap=0, stream=None):
+        """sslam_two_view_reconstruct_batch_dev on device tensors / pointers in two_view_ransac_batch_dev's layout, d_result and d_inliers as that call left them; d_K
+        [npairs, 4] float32; d_pose receives npairs TWO_VIEW_POSE_DTYPE records (144 bytes each), d_p3d [npairs, cap, 3] float32, d_triangulated [npairs, cap] uint8.  lines:
+        None or the eleven device arrays (d_kl1, d_nl1, d_kl2, d_nl2, d_linefn1, d_linefn2, d_line_pairs, d_line_npairs, d_line_s3d, d_line_e3d, d_line_triangulated) of
+        capacity lcap.  Enqueues on `stream` (None: the context's) and returns without synchronising"""
+        l = [None] * 11 if lines is None else list(lines)
+        assert len(l) == 11
+        _chk(lib().sslam_two_view_reconstruct_batch_dev(self.h, _p(d_kp1), _p(d_n1), _p(d_kp2), _p(d_n2), int(cap), int(npairs), _p(d_matches12), _p(d_result), _p(d_inliers),
+                                                        _p(d_K), C.c_float(sigma), C.c_float(min_parallax), int(min_triangulated), _p(l[0]), _p(l[1]), _p(l[2]), _p(l[3]),
+                                                        _p(l[4]), _p(l[5]), int(lcap), _p(l[6]), _p(l[7]), _p(d_pose), _p(d_p3d), _p(d_triangulated), _p(l[8]), _p(l[9]),
+                                                        _p(l[10]), C.c_void_p(stream or 0)))
 
     def sim3_ransac(self, kp1, x3dc1, valid1, K1, kp2, x3dc2, valid2, K2, level_sigma2, matches12, state=None, fix_scale=False, probability=0.99, min_inliers=20,
                     max_iterations=300, new_iterations=5, sets=None, seed=0):
