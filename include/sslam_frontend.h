@@ -574,6 +574,76 @@ int sslam_orb_search_for_triangulation_batch_dev(sslam_ctx* ctx,
                                                  int only_stereo, int check_orientation,
                                                  int32_t* d_matches12, int32_t* d_nmatches, void* stream);
 
+/* The geometry behind that matcher: the loop body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:456-635) for every match of `npairs` pairs of
+ * device-resident keyframes, asynchronously, with the first MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:335-376) of every new point.  It reads d_matches12 where
+ * sslam_orb_search_for_triangulation_batch_dev left it and clears the free flags of the rows it turns into points, so THE LIMIT above needs no host round trip any more:
+ * per round r enqueue the matcher and then this call on ONE stream with the SAME d_free (one pair per session per round), enqueue all 20 rounds back to back and
+ * synchronise once.  The caller then creates the MapPoints from the rows with d_stage == 0 in row order -- ascending keypoint-1 index, the order of the reference's
+ * vMatchedIndices -- and keeps AddObservation, AddMapPoint and the map as host bookkeeping; sslam_distinctive_descriptors_batch_dev takes it from there.  The baseline /
+ * median-depth gate of :413-431 stays with the caller, in front of the matcher: such a pair is simply not listed.
+ * The pool is the matcher's: keyframe slot k owns rows [k*cap, k*cap + d_n[k]) of d_kp (mvKeysUn) and, where given, of d_free; d_pose[k] is what KeyFrame::SetPose and
+ * the constructor keep for it.  Pair p = d_pairs[p]: kf1 is mpCurrentKeyFrame, kf2 is pKF2 (median_depth2 is not read here).  scale_factors / level_sigma2 are HOST
+ * arrays of nlevels floats, 1 <= nlevels <= 64 (mvScaleFactors / mvLevelSigma2: one extractor), read before the call returns; scale_factor is mfScaleFactor
+ * (ratioFactor = 1.5f * scale_factor, :400).  An octave outside [0, nlevels) is clamped into it, as the matchers clamp it.  This fork is monocular (only
+ * GrabImageMonocularWithPL exists), so every mvuRight is negative and the bStereo branches (:488-491, :518-525, :560-570, :587-597) do not exist here: there is no d_uright.
+ * Row i1 < n[kf1] of pair p (outputs are indexed p*cap + i1; rows at or past the count are not touched):
+ *   d_stage   0 created
+ *             1 no match (d_matches12 < 0 or >= n[kf2])
+ *             2 parallax (:497 false, the continue of :527)        3 x3D(3) == 0 (:511)
+ *             4 z1 <= 0 (:534)        5 z2 <= 0 (:538)        6 reprojection in keyframe 1 (:557)        7 reprojection in keyframe 2 (:584)
+ *             8 dist1 == 0 || dist2 == 0 (:607)        9 scale consistency (:615)
+ *   d_x3d     x3D (:515); d_normal, d_dist = mNormalVector and (mfMaxDistance, mfMinDistance) of UpdateNormalAndDepth for the observations {kf1: i1, kf2: i2} with
+ *             mpRefKF = keyframe 1 (level = kp1.octave, min = max / scale_factors[nlevels - 1]).  All of them are zero for a row that is not created.
+ * d_nnew[p] = the number of created rows (nnew).  When d_free is given, a created row stores 0 to d_free[kf1*cap + i1] and d_free[kf2*cap + i2] (AddMapPoint, :624-625);
+ * d_free is not read.  A NaN behaves as the reference's comparisons make it behave.  A pair with a slot outside [0, nkeyframes) or with kf1 == kf2 (the reference never
+ * pairs a keyframe with itself) is skipped: d_nnew[p] = -1 and nothing else of the pair is written.
+ * Every pointer but the two level tables is a device pointer, the 4-byte typed buffers 4-byte aligned.  One launch on `stream` (NULL: the context's stream), no
+ * scratch, no synchronise.  SSLAM_ERR_INVALID (nothing enqueued): a NULL ctx or pointer other than d_free, a misaligned buffer, a negative cap, nkeyframes or npairs,
+ * nlevels outside 1..64, npairs * cap or nkeyframes * cap >= 2^31.  npairs == 0 is SSLAM_OK and enqueues nothing. */
+typedef struct sslam_kf_pose {    /* 84 bytes: what KeyFrame::SetPose and the constructor keep, per pool slot */
+    float Rcw[9], tcw[3], Ow[3];  /* GetRotation (row-major), GetTranslation, GetCameraCenter */
+    float fx, fy, cx, cy, invfx, invfy;
+} sslam_kf_pose;
+typedef struct sslam_newmap_pair {
+    int32_t kf1, kf2;             /* keyframe slots: mpCurrentKeyFrame, pKF2 */
+    float   median_depth2;        /* pKF2->ComputeSceneMedianDepth(2); read by the line call only */
+} sslam_newmap_pair;              /* 12 bytes, no padding */
+int sslam_new_map_points_batch_dev(sslam_ctx* ctx, const sslam_keypoint* d_kp, const int32_t* d_n, int cap, int nkeyframes, const sslam_kf_pose* d_pose,
+                                   const sslam_newmap_pair* d_pairs, int npairs, const int32_t* d_matches12,
+                                   const float* scale_factors, const float* level_sigma2, int nlevels, float scale_factor,
+                                   uint8_t* d_free, float* d_x3d, uint8_t* d_stage, float* d_normal, float* d_dist, int32_t* d_nnew, void* stream);
+/* The same for one host pair, synchronously: pair 0 of the same kernel on a pool of two slots.  Outputs [n1] rows; *nnew = the number of created rows. */
+int sslam_new_map_points(sslam_ctx* ctx, const sslam_keypoint* kp1, int n1, const sslam_keypoint* kp2, int n2, const sslam_kf_pose* pose1, const sslam_kf_pose* pose2,
+                         const int32_t* matches12, const float* scale_factors, const float* level_sigma2, int nlevels, float scale_factor,
+                         float* x3d, uint8_t* stage, float* normal, float* dist, int* nnew);
+
+/* The loop body of LocalMapping::CreateNewMapLines2 (src/LocalMapping.cc:1005-1170) with the GetMapLine filter of LSDmatcher::SearchForTriangulation
+ * (src/LSDmatcher.cpp:403) and the first MapLine::UpdateAverageDir (src/MapLine.cpp:325-372) of every new line.  SearchForTriangulation computes its MAD over all knn rows
+ * and applies the filter afterwards, so the filter moves into this call with no change of result: sslam_line_match_batch_dev(gate_scale = 0.1) plus this call is the
+ * whole of src/LSDmatcher.cpp:382-415 and the loop behind it.  The exact use: ONE sslam_line_match_batch_dev for all neighbours of a round set, then one of these calls per
+ * round with the same d_lfree on one stream (one pair per session per round).  The gate of :955-979 stays with the caller: such a pair is not listed.
+ * Keyframe slot k owns rows [k*lcap, k*lcap + d_nl[k]) of d_kl (mvKeyLines), d_linefn (mvKeyLineFunctions, 3 doubles per row) and, where given, d_lfree
+ * (= !GetMapLine(i)); a NULL d_lfree means every line is free.  Pair p reads rows r < d_line_npairs[p] of d_line_pairs: (idx1, idx2) = d_line_pairs[(p*lcap + r)*2 + {0, 1}],
+ * as sslam_line_match_batch_dev leaves them for a batch with cap = lcap; outputs are indexed p*lcap + r and rows at or past the count are not touched.
+ * The reference's quirks stay: the endpoints of key line 2 are normalised with keyframe 1's cx, invfx, cy, invfy (:1032-1035), s3D / e3D come from line 1's endpoints and
+ * both line functions, and all five ratios divide by the neighbour's median depth.
+ *   d_stage   0 created        1 an index outside [0, nl)        2 not free: GetMapLine(qdx) || GetMapLine(tdx), with the flags as they stand before the pair creates anything
+ *             3 parallax (:1053)        4 s3D(3) == 0 (:1066)        5 e3D(3) == 0 (:1084)
+ *             6 .. 10 ratio1, ratio2, ratio3, ratio4, ratio5 (:1102-1131)        11 .. 14 SZC1, SZC2, EZC1, EZC2 (:1135-1148)
+ *   d_s3d, d_e3d   the endpoints (:1070, :1088); d_normal (double) and d_dist = mNormalVector and (mfMaxDistance, mfMinDistance) of UpdateAverageDir with mpRefKF =
+ *             keyframe 1 (level = keyline1.octave, clamped).  All of them are zero for a row that is not created.
+ * d_nnew[p] = the number of created rows; a created row stores 0 to d_lfree[kf1*lcap + idx1] and d_lfree[kf2*lcap + idx2] (AddMapLine, :1159-1160).  In one launch two
+ * pairs that share a slot may or may not see each other's creations in d_lfree; one pair per session per round never shares one.  Skipped pairs, streams, alignment (the
+ * double buffers 8 bytes) and SSLAM_ERR_INVALID are as above. */
+int sslam_new_map_lines_batch_dev(sslam_ctx* ctx, const sslam_keyline* d_kl, const double* d_linefn, const int32_t* d_nl, int lcap, int nkeyframes,
+                                  const sslam_kf_pose* d_pose, const sslam_newmap_pair* d_pairs, int npairs, const int32_t* d_line_pairs, const int32_t* d_line_npairs,
+                                  const float* scale_factors, int nlevels, uint8_t* d_lfree,
+                                  float* d_s3d, float* d_e3d, uint8_t* d_stage, double* d_normal, float* d_dist, int32_t* d_nnew, void* stream);
+/* The same for one host pair, synchronously (every line is free).  Outputs [line_npairs] rows. */
+int sslam_new_map_lines(sslam_ctx* ctx, const sslam_keyline* kl1, const double* linefn1, int nl1, const sslam_keyline* kl2, const double* linefn2, int nl2,
+                        const sslam_kf_pose* pose1, const sslam_kf_pose* pose2, float median_depth2, const int32_t* line_pairs, int line_npairs,
+                        const float* scale_factors, int nlevels, float* s3d, float* e3d, uint8_t* stage, double* normal, float* dist, int* nnew);
+
 /* ---- DBoW2 vocabulary descent: Frame::ComputeBoW, src/Frame.cc:474-481 ->
  * ORBVocabulary::transform(vCurrentDesc, mBowVec, mFeatVec, 4), whose per-feature work is
  * TemplatedVocabulary::transform(feature, word_id, weight, nid, levelsup), Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1216-1259.

@@ -205,6 +205,18 @@ int sslam_testing_two_view_reconstruct(sslam_ctx* ctx, const sslam_keypoint* kp1
                                        float* line_s3d, float* line_e3d, uint8_t* line_triangulated,
                                        float* hyp_out, float* sel_out, int32_t* stage_out, float* p3d_rows_out, float* cos_out, double* line_err_out);
 
+/* sslam_new_map_points / sslam_new_map_lines for one host pair with what the gates consumed copied back: the same kernels with the stores of their tap enabled, run as
+ * pair 0.  Per row: cos_out[row] = cosParallaxRays (:482, :1041; zero for a row without a match or, for a line, one that is not free) and the homogeneous vt.row(3)
+ * before the division -- hom_out[row*4 .. +4) of x3D for a point (:509), hom_out[row*8 .. +4) of s3D and [row*8 + 4 .. +4) of e3D for a line (:1065, :1082) -- zeros
+ * where the row ended before the decomposition. */
+int sslam_testing_new_map_points(sslam_ctx* ctx, const sslam_keypoint* kp1, int n1, const sslam_keypoint* kp2, int n2, const sslam_kf_pose* pose1, const sslam_kf_pose* pose2,
+                                 const int32_t* matches12, const float* scale_factors, const float* level_sigma2, int nlevels, float scale_factor,
+                                 float* x3d, uint8_t* stage, float* normal, float* dist, int* nnew, float* cos_out, float* hom_out);
+int sslam_testing_new_map_lines(sslam_ctx* ctx, const sslam_keyline* kl1, const double* linefn1, int nl1, const sslam_keyline* kl2, const double* linefn2, int nl2,
+                                const sslam_kf_pose* pose1, const sslam_kf_pose* pose2, float median_depth2, const int32_t* line_pairs, int line_npairs,
+                                const float* scale_factors, int nlevels, float* s3d, float* e3d, uint8_t* stage, double* normal, float* dist, int* nnew,
+                                float* cos_out, float* hom_out);
+
 #ifdef __cplusplus
 }
 #endif

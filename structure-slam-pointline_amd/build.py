@@ -34,7 +34,7 @@ def needs_build():
 # libsslam_frontend_testing.so = the same sources with -DSSLAM_TESTING: the product's entry points plus the self-tests, probes and the RCCL stand-in declared in
 # include/sslam_testing.h.  Only these units hold SSLAM_TESTING code and are compiled a second time; the other objects are shared.
 TEST_LIB = os.path.join(LIBDIR, "libsslam_frontend_testing.so")
-TESTING_UNITS = ("lines.hip", "group.hip", "match.hip", "orb.hip", "two_view.hip", "sim3.hip", "pnp.hip", "reconstruct.hip")
+TESTING_UNITS = ("lines.hip", "group.hip", "match.hip", "orb.hip", "two_view.hip", "sim3.hip", "pnp.hip", "reconstruct.hip", "newmap.hip")
 
 
 def build(force=False, verbose=True):

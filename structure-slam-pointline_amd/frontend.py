@@ -27,6 +27,11 @@ assert PQ_DTYPE.itemsize == 44
 TRI_PAIR_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("F12", "<f4", (9,)), ("ex", "<f4"), ("ey", "<f4")])      # sslam_tri_pair
 assert TRI_PAIR_DTYPE.itemsize == 52
 
+KF_POSE_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("invfx", "<f4"),
+                          ("invfy", "<f4")])      # sslam_kf_pose
+NEWMAP_PAIR_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("median_depth2", "<f4")])      # sslam_newmap_pair
+assert KF_POSE_DTYPE.itemsize == 84 and NEWMAP_PAIR_DTYPE.itemsize == 12
+
 FUSE_JOB_DTYPE = np.dtype([("kf", "<i4"), ("nq", "<i4"), ("qdesc0", "<i4")])      # sslam_fuse_job
 assert FUSE_JOB_DTYPE.itemsize == 12
 
@@ -395,6 +400,79 @@ class Context:
                                                                 int(nkeyframes), _p(d_pairs), int(npairs), _p(sf), _p(sg), int(nlevels),
                                                                 int(bool(only_stereo)), int(bool(check_orientation)), _p(d_matches12), _p(d_nmatches),
                                                                 C.c_void_p(stream or 0)))
+
+    def new_map_points_batch_dev(self, d_kp, d_n, cap, nkeyframes, d_pose, d_pairs, npairs, d_matches12, scale_factors, level_sigma2, scale_factor,
+                                 d_x3d, d_stage, d_normal, d_dist, d_nnew, d_free=None, nlevels=None, stream=None):
+        """sslam_new_map_points_batch_dev on device tensors / pointers: the loop body of CreateNewMapPoints for pair p = d_pairs[p] (NEWMAP_PAIR_DTYPE rows on the
+        device) of the pool d_kp / d_n with d_pose (KF_POSE_DTYPE rows) on d_matches12 [npairs, cap] as search_for_triangulation_batch_dev left it; scale_factors /
+        level_sigma2 are HOST arrays (nlevels: their length unless given), scale_factor is mfScaleFactor; d_x3d / d_normal [npairs, cap, 3] float32, d_stage
+        [npairs, cap] uint8, d_dist [npairs, cap, 2] float32, d_nnew [npairs] int32; d_free (uint8 [nkeyframes, cap]) is cleared for created rows; enqueues on
+        `stream` (None: the context's) and returns without synchronising"""
+        sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, np.float32)
+        sg = None if level_sigma2 is None else np.ascontiguousarray(level_sigma2, np.float32)
+        if nlevels is None: nlevels = 0 if sf is None else len(sf)
+        _chk(lib().sslam_new_map_points_batch_dev(self.h, _p(d_kp), _p(d_n), int(cap), int(nkeyframes), _p(d_pose), _p(d_pairs), int(npairs), _p(d_matches12), _p(sf), _p(sg),
+                                                  int(nlevels), C.c_float(scale_factor), _p(d_free), _p(d_x3d), _p(d_stage), _p(d_normal), _p(d_dist), _p(d_nnew),
+                                                  C.c_void_p(stream or 0)))
+
+    def new_map_lines_batch_dev(self, d_kl, d_linefn, d_nl, lcap, nkeyframes, d_pose, d_pairs, npairs, d_line_pairs, d_line_npairs, scale_factors,
+                                d_s3d, d_e3d, d_stage, d_normal, d_dist, d_nnew, d_lfree=None, nlevels=None, stream=None):
+        """sslam_new_map_lines_batch_dev on device tensors / pointers: the loop body of CreateNewMapLines2 for pair p = d_pairs[p] of the line pool d_kl (KL_DTYPE) /
+        d_linefn (float64 [nkeyframes, lcap, 3]) / d_nl on rows [p, r] of d_line_pairs [npairs, lcap, 2] as line_match_batch_dev left them; scale_factors is a HOST
+        array; d_s3d / d_e3d [npairs, lcap, 3] float32, d_stage [npairs, lcap] uint8, d_normal [npairs, lcap, 3] float64, d_dist [npairs, lcap, 2] float32, d_nnew
+        [npairs] int32; d_lfree (uint8 [nkeyframes, lcap]) filters and is cleared for created rows; enqueues on `stream` and returns without synchronising"""
+        sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, np.float32)
+        if nlevels is None: nlevels = 0 if sf is None else len(sf)
+        _chk(lib().sslam_new_map_lines_batch_dev(self.h, _p(d_kl), _p(d_linefn), _p(d_nl), int(lcap), int(nkeyframes), _p(d_pose), _p(d_pairs), int(npairs), _p(d_line_pairs),
+                                                 _p(d_line_npairs), _p(sf), int(nlevels), _p(d_lfree), _p(d_s3d), _p(d_e3d), _p(d_stage), _p(d_normal), _p(d_dist), _p(d_nnew),
+                                                 C.c_void_p(stream or 0)))
+
+    def new_map_points(self, kp1, kp2, pose1, pose2, matches12, scale_factors, level_sigma2, scale_factor, tap=False):
+        """sslam_new_map_points for one host pair (tap: sslam_testing_new_map_points of the testing library, which also returns what the gates consumed): kp1 / kp2
+        KP_DTYPE rows (mvKeysUn), pose1 / pose2 KF_POSE_DTYPE records, matches12 int32 [n1].  Returns dict(x3d, normal float32 [n1, 3], stage uint8 [n1], dist
+        float32 [n1, 2], nnew) and, with tap, cos float32 [n1] and hom float32 [n1, 4]"""
+        kp1 = np.ascontiguousarray(kp1, KP_DTYPE); kp2 = np.ascontiguousarray(kp2, KP_DTYPE); m12 = np.ascontiguousarray(matches12, np.int32)
+        p1 = np.ascontiguousarray(np.asarray(pose1).view(KF_POSE_DTYPE).reshape(1)); p2 = np.ascontiguousarray(np.asarray(pose2).view(KF_POSE_DTYPE).reshape(1))
+        sf = np.ascontiguousarray(scale_factors, np.float32); sg = np.ascontiguousarray(level_sigma2, np.float32)
+        n1 = len(kp1)
+        assert len(m12) == n1 and len(sf) == len(sg)
+        o = dict(x3d=np.zeros((n1, 3), np.float32), stage=np.zeros(n1, np.uint8), normal=np.zeros((n1, 3), np.float32), dist=np.zeros((n1, 2), np.float32))
+        nnew = C.c_int(0)
+        ptr = lambda a: _p(a if len(a) else None)      # an empty array travels as NULL
+        args = [self.h, ptr(kp1), n1, ptr(kp2), len(kp2), _p(p1), _p(p2), ptr(m12), _p(sf), _p(sg), len(sf), C.c_float(scale_factor), ptr(o["x3d"]), ptr(o["stage"]),
+                ptr(o["normal"]), ptr(o["dist"]), C.byref(nnew)]
+        if tap:
+            o["cos"] = np.zeros(n1, np.float32); o["hom"] = np.zeros((n1, 4), np.float32)
+            _chk(testing_lib().sslam_testing_new_map_points(*args, ptr(o["cos"]), ptr(o["hom"])))
+        else:
+            _chk(lib().sslam_new_map_points(*args))
+        o["nnew"] = nnew.value
+        return o
+
+    def new_map_lines(self, kl1, linefn1, kl2, linefn2, pose1, pose2, median_depth2, line_pairs, scale_factors, tap=False):
+        """sslam_new_map_lines for one host pair (tap: sslam_testing_new_map_lines): kl1 / kl2 KL_DTYPE rows, linefn1 / linefn2 float64 [nl, 3], line_pairs int32
+        [nrows, 2].  Returns dict(s3d, e3d float32 [nrows, 3], stage uint8 [nrows], normal float64 [nrows, 3], dist float32 [nrows, 2], nnew) and, with tap, cos
+        float32 [nrows] and hom float32 [nrows, 8] (s3D, e3D)"""
+        kl1 = np.ascontiguousarray(kl1, KL_DTYPE); kl2 = np.ascontiguousarray(kl2, KL_DTYPE)
+        f1 = np.ascontiguousarray(linefn1, np.float64).reshape(-1, 3); f2 = np.ascontiguousarray(linefn2, np.float64).reshape(-1, 3)
+        lp = np.ascontiguousarray(line_pairs, np.int32).reshape(-1, 2)
+        p1 = np.ascontiguousarray(np.asarray(pose1).view(KF_POSE_DTYPE).reshape(1)); p2 = np.ascontiguousarray(np.asarray(pose2).view(KF_POSE_DTYPE).reshape(1))
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        nr = len(lp)
+        assert len(f1) == len(kl1) and len(f2) == len(kl2)
+        o = dict(s3d=np.zeros((nr, 3), np.float32), e3d=np.zeros((nr, 3), np.float32), stage=np.zeros(nr, np.uint8), normal=np.zeros((nr, 3), np.float64),
+                 dist=np.zeros((nr, 2), np.float32))
+        nnew = C.c_int(0)
+        ptr = lambda a: _p(a if len(a) else None)
+        args = [self.h, ptr(kl1), ptr(f1), len(kl1), ptr(kl2), ptr(f2), len(kl2), _p(p1), _p(p2), C.c_float(median_depth2), ptr(lp), nr, _p(sf), len(sf), ptr(o["s3d"]),
+                ptr(o["e3d"]), ptr(o["stage"]), ptr(o["normal"]), ptr(o["dist"]), C.byref(nnew)]
+        if tap:
+            o["cos"] = np.zeros(nr, np.float32); o["hom"] = np.zeros((nr, 8), np.float32)
+            _chk(testing_lib().sslam_testing_new_map_lines(*args, ptr(o["cos"]), ptr(o["hom"])))
+        else:
+            _chk(lib().sslam_new_map_lines(*args))
+        o["nnew"] = nnew.value
+        return o
 
     def fuse_search_batch_dev(self, kind, chi2_mode, d_feats, d_desc, d_n, cap, nkeyframes, d_queries, qcap, d_qdesc, nqdesc, d_jobs, njobs,
                               d_best_idx, d_best_dist, d_nfound, d_uright=None, inv_level_sigma2=None, nlevels=None, bounds=(0.0, 640.0, 0.0, 480.0),
